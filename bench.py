@@ -10,7 +10,14 @@ text embeddings, random-init weights (no checkpoints offline).
 One "step" = one denoise step of the sampler = MMDiT forward on the CFG triple + CFG combine + Euler update.
 `value` = latent frames per second for a 30-step sampling = T_lat / (30 * step_time), inputs resident in HBM.
 
+A plain run does only what `value` needs: set up, warm up, time EXACTLY --steps steps, print the line.  Everything else the
+benchmark measures (CPU baselines, the per-kernel rooflines, the batch-1 / processor / attention-dispatch side runs, the VAE,
+11B and fp8 sub-objects, the rank shapes, exposed communication) runs only with --full.  --dump-outputs DIR writes what the
+timed path returned after its last step as DIR/<name>.npy (float32; a fixed, seeded sample of the elements where the whole
+would exceed 64 MB; the inputs are seeded: the same arguments give the same inputs in every run).
+
   python bench.py --gpus 1 --steps 30 --warmup 3
+  python bench.py --gpus 1 --steps 30 --warmup 3 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W          (sequence parallel over the token axis, RCCL)
 """
@@ -50,12 +57,37 @@ def parse():
     ap.add_argument("--fp8", action="store_true",
                     help="opt-in reduced precision (BASELINE configs[4]): block Linears on the fp8 (e4m3) MFMA; "
                          "never the default line -- the reference computes in bf16")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-b1", action="store_true", help="skip the extra CFG-batch-1 timing")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-b1", action="store_true", help="with --full: skip the extra CFG-batch-1 timing")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the `vae` (BASELINE configs[2]) and `11b` (the shipped 11B geometry) sub-objects of the default line")
+                    help="with --full: skip the `vae` (BASELINE configs[2]) and `11b` (the shipped 11B geometry) sub-objects")
     ap.add_argument("--cpu-budget-s", type=float, default=45.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (CPU baselines, rooflines, b1 / processors / attention-dispatch runs, "
+                         "the vae / 11b / fp8 / rank_shapes sub-objects, exposed communication); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32; a fixed "
+                         "sample of the elements where the whole would exceed 64 MB)")
     return ap.parse_args()
+
+
+def dump_outputs(out_dir, arrays, limit_bytes=64 << 20):
+    """arrays: name -> tensor; written as out_dir/<name>.npy in float32.  When all of them together exceed limit_bytes, each
+    is replaced by a fixed sample of its flattened elements (ascending indices drawn from a generator seeded with 0 and the
+    array's size, so two runs with the same arguments sample the same positions), its share of the limit in proportion to its size;
+    the size is checked before anything is written."""
+    import numpy as np
+
+    total = sum(t.numel() for t in arrays.values()) * 4
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if total > limit_bytes:
+            n = t.numel()
+            k = max(1, n * limit_bytes // total)
+            idx = np.unique(np.random.default_rng([0, n]).integers(0, n, size=k))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(t.float().cpu().numpy(), dtype=np.float32))
 
 
 def cpu_baseline(cfg, L_img, L_txt, cfg_batch, budget_s):
@@ -224,9 +256,11 @@ def vae_cpu_baseline(budget_s):
     return fl / dt, ncores, dt
 
 
-def vae_line(dev, T, S, steps, warmup, cpu_budget_s):
+def vae_line(dev, T, S, steps, warmup, cpu_budget_s, full=True, outputs=None):
     """BASELINE configs[2]: 3D-VAE (CausalConv3d) encode + decode of a [1,3,T,256,256] video, 1x MI355X.  Returns the JSON
-    object (`python bench.py --workload vae` prints it as its line; the default line carries it as `vae`)."""
+    object (`python bench.py --workload vae` prints it as its line; the --full default line carries it as `vae`).
+    full=False: the timed steps only (no per-launch events, no GroupNorm-fold run, no roofline, no CPU baseline).
+    outputs: a dict that receives the decoded video of the last timed step as "video"."""
     from open_sora_amd import _C, configs, hunyuan_vae
 
     cfg = dict(configs.VAE["hunyuan"])
@@ -248,7 +282,7 @@ def vae_line(dev, T, S, steps, warmup, cpu_budget_s):
     with torch.inference_mode():
         for _ in range(args.warmup):
             out = step()
-        _C.PROFILE_CONV = []
+        _C.PROFILE_CONV = [] if full else None
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
@@ -257,6 +291,24 @@ def vae_line(dev, T, S, steps, warmup, cpu_budget_s):
         elapsed = time.perf_counter() - t0
         prof, _C.PROFILE_CONV = _C.PROFILE_CONV, None
     assert torch.isfinite(out.float()).all() and list(out.shape) == [1, 3, 1 + 4 * ((T - 1) // 4), S, S]
+    if outputs is not None:
+        outputs["video"] = out
+    ms = elapsed / args.steps * 1e3
+    enc_f, dec_f = configs.vae_flops(cfg, T, S, S)
+    res = {
+        "metric": "vae_video_frames_per_sec (encode + decode; ms per encode+decode in ms_per_step)",
+        "value": round(T / (ms * 1e-3), 3), "unit": "video frames/s", "n_gpus": 1, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+        "config": {"workload": f"Hunyuan causal 3-D VAE (128/256/512/512, 16 latent ch) encode + decode of [1,3,{T},{S},{S}], no tiling",
+                   "flops_encode": enc_f, "flops_decode": dec_f},
+        "step_tflops": round((enc_f + dec_f) / (ms * 1e-3) / 1e12, 1),
+        "step_mfma_frac": round((enc_f + dec_f) / (ms * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4),
+    }
+    if not full:
+        del model, out
+        torch.cuda.empty_cache()
+        return res
     # the opt-in GroupNorm fold (hunyuan_vae.FOLD_GN: norm -> SiLU -> conv as one launch reading the un-normalised tensor) under the
     # same clock: a second, separately timed run; never part of `value`
     fold_ms = None
@@ -274,8 +326,6 @@ def vae_line(dev, T, S, steps, warmup, cpu_budget_s):
         finally:
             hunyuan_vae.FOLD_GN = was
         assert torch.isfinite(out_f.float()).all()
-    ms = elapsed / args.steps * 1e3
-    enc_f, dec_f = configs.vae_flops(cfg, T, S, S)
     conv_ms = sum(s.elapsed_time(e) for s, e, _ in prof) / args.steps
     ach = (enc_f + dec_f) / (conv_ms * 1e-3) / 1e12
     # HBM-side bytes of all conv launches of one step: PMC passes of this same command (tools/gpu_pmc_kernels.sh)
@@ -285,15 +335,7 @@ def vae_line(dev, T, S, steps, warmup, cpu_budget_s):
         for rec in json.load(open(rec_path)):
             if rec["kernel"].startswith(("conv256", "convsw")):   # the latest record wins
                 traffic, traffic_src = rec["hbm_bytes_per_step"], rec["source"]
-    res = {
-        "metric": "vae_video_frames_per_sec (encode + decode; ms per encode+decode in ms_per_step)",
-        "value": round(T / (ms * 1e-3), 3), "unit": "video frames/s", "n_gpus": 1, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-        "config": {"workload": f"Hunyuan causal 3-D VAE (128/256/512/512, 16 latent ch) encode + decode of [1,3,{T},{S},{S}], no tiling",
-                   "flops_encode": enc_f, "flops_decode": dec_f},
-        "step_tflops": round((enc_f + dec_f) / (ms * 1e-3) / 1e12, 1),
-        "step_mfma_frac": round((enc_f + dec_f) / (ms * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4),
+    res.update({
         "gn_fold": None if fold_ms is None else {"ms_per_step": round(fold_ms, 3), "what": "same model and input with hunyuan_vae.FOLD_GN = True (opt-in: GroupNorm + SiLU applied "
                     "inside the consuming sliding-window conv; 16 GB less fabric traffic per step)"},
         # all conv launches of one encode + decode: conv3d_256.hip where Cin % 128 == 0 -- the LDS sliding-window kernels
@@ -303,7 +345,7 @@ def vae_line(dev, T, S, steps, warmup, cpu_budget_s):
                      "unit": "TFLOP/s", "frac": round(ach / MFMA_BF16_PEAK_TFLOPS, 4), "traffic": traffic,
                      "traffic_kind": "recorded (PMC passes of this command, see traffic_source)", "traffic_source": traffic_src,
                      "launches": len(prof) // args.steps, "total_conv_ms_per_step": round(conv_ms, 3)},
-    }
+    })
     if not args.no_cpu_baseline:
         fps, ncores, dt = vae_cpu_baseline(args.cpu_budget_s)
         cpu_s = (enc_f + dec_f) / fps
@@ -347,13 +389,21 @@ def main():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl", device_id=dev)
     assert world == args.gpus, f"--gpus {args.gpus} but WORLD_SIZE {world}"
+    outputs = {} if args.dump_outputs else None
     if args.workload == "vae":
         assert world == 1, "the VAE workload is single-GPU (BASELINE configs[2])"
-        print(json.dumps(vae_line(dev, args.vae_frames, args.vae_size, args.steps, args.warmup,
-                                  None if args.no_cpu_baseline else args.cpu_budget_s)), flush=True)
+        line = vae_line(dev, args.vae_frames, args.vae_size, args.steps, args.warmup,
+                        None if args.no_cpu_baseline or not args.full else args.cpu_budget_s, full=args.full, outputs=outputs)
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
+        print(json.dumps(line), flush=True)
         return
 
-    out = dit_line(args, dev, dist, rank, world, args.model, args.steps, args.warmup, with_b1=not args.no_b1)
+    out = dit_line(args, dev, dist, rank, world, args.model, args.steps, args.warmup, with_b1=args.full and not args.no_b1,
+                   outputs=outputs if rank == 0 else None)
+    if outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
+        outputs.clear()
     if rank != 0:
         if dist is not None:
             dist.destroy_process_group()
@@ -363,7 +413,7 @@ def main():
     cfg = dict(configs.MMDIT[args.model])
     T, hw = args.frames, args.latent_hw
     L_img, L_txt = T * (hw // 2) * (hw // 2), 512
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         cb = cpu_baseline(cfg, L_img, L_txt, 3, args.cpu_budget_s)
         td, tsg, cpu_step, ncores = cb["t_double"], cb["t_single"], cb["step_s"], cb["cores"]
         L = L_img + L_txt
@@ -379,7 +429,7 @@ def main():
                       f"(a whole XL step is tens of minutes of CPU; the un-extrapolated whole-forward line is cfg1)",
             "cfg1": cfg1_line(dev, args.cpu_budget_s),
         }
-    if world == 1 and not args.no_extra and args.model == "XL" and not args.fp8:
+    if world == 1 and args.full and not args.no_extra and args.model == "XL" and not args.fp8:
         # the other two single-GPU workloads of SURVEY.md section 8(d), under the same clock as the headline: BASELINE configs[2]
         # (the causal VAE) and the geometry the reference actually ships (11B: hidden 3072, 24 x 128, 19 + 38 blocks); each with
         # its own roofline object.  Never part of `value`.
@@ -423,10 +473,12 @@ def main():
         dist.destroy_process_group()
 
 
-def dit_line(args, dev, dist, rank, world, model_name, steps, warmup, with_b1, geom=None):
+def dit_line(args, dev, dist, rank, world, model_name, steps, warmup, with_b1, geom=None, outputs=None):
     """One denoise-step measurement of the product's sampler: `sampling.I2VDenoiser.denoise` (the reference's Euler loop,
     opensora/utils/sampling.py:159-226) driving MMDiTModel.forward on the CFG triple, `warmup` untimed steps, then EXACTLY
-    `steps` steps between barriers.  Returns the JSON object of the line (rank 0; other ranks: None)."""
+    `steps` steps between barriers.  Returns the JSON object of the line (rank 0; other ranks: None).
+    args.full: also the per-launch events of the rooflines and the side measurements; without it only the timed steps run.
+    outputs: a dict that receives the latents the sampler returned after the last timed step as "latents"."""
     from open_sora_amd import _C, configs, mmdit, sampling
 
     cfg = dict(configs.MMDIT[model_name])
@@ -488,7 +540,7 @@ def dit_line(args, dev, dist, rank, world, model_name, steps, warmup, with_b1, g
             x = sampling.pack(z).contiguous()
             if warmup:
                 x = run_denoise(x, 0, warmup)
-            _C.PROFILE_ATTENTION = [] if rank == 0 else None
+            _C.PROFILE_ATTENTION = [] if rank == 0 and args.full else None
             barrier()
             t0 = time.perf_counter()
             x = run_denoise(x, warmup, steps)
@@ -500,7 +552,7 @@ def dit_line(args, dev, dist, rank, world, model_name, steps, warmup, with_b1, g
             step, st = _plain_step(model, cfg, nb, z, ts, T, hh, hw, L_img, L_txt, dev, g2)
             for i in range(warmup):
                 step(i)
-            _C.PROFILE_ATTENTION = [] if rank == 0 else None
+            _C.PROFILE_ATTENTION = [] if rank == 0 and args.full else None
             barrier()
             t0 = time.perf_counter()
             for i in range(steps):
@@ -512,7 +564,7 @@ def dit_line(args, dev, dist, rank, world, model_name, steps, warmup, with_b1, g
         # sequence parallelism: how long the compute stream STALLED on each kind of exchange (q / k / v / o all-to-alls or the K / V^T
         # all-gathers, the final gather), from event pairs around every wait() in 2 extra steps outside the timed region
         exposed = None
-        if world > 1 and nb == 3:
+        if args.full and world > 1 and nb == 3:
             sp.exposed = []
             barrier()
             run_denoise(x, 0, 2)
@@ -523,14 +575,14 @@ def dit_line(args, dev, dist, rank, world, model_name, steps, warmup, with_b1, g
         # 2 extra steps outside the timed region (the events of 170 launches per step would perturb `value`; they do not perturb
         # a launch's own duration)
         gemm_prof = None
-        if nb == 3 and world == 1:
+        if args.full and nb == 3 and world == 1:
             _C.PROFILE_GEMM = []
             torch.cuda.synchronize()
             run_denoise(x, 0, 2)
             torch.cuda.synchronize()
             gemm_prof, _C.PROFILE_GEMM = _C.PROFILE_GEMM, None
         # the attention body the timed steps ran (before any side measurement touches the QK-norm scales)
-        rep = model.attention_report(world if sp_mode and "all-gather" in sp_mode else 1, L // world if world > 1 else L)
+        rep = model.attention_report(world if sp_mode and "all-gather" in sp_mode else 1, L // world if world > 1 else L) if args.full else None
         # SURVEY.md section 8(d) cfg 2 asks for B = 1 (the pure step) next to the reference's CFG triple: a second, separately
         # timed run at batch 1 (reported under "b1", never part of `value`)
         b1 = None
@@ -596,7 +648,7 @@ def dit_line(args, dev, dist, rank, world, model_name, steps, warmup, with_b1, g
             del x_p, x_e
 
         rel8 = None
-        if args.fp8 and nb == 3 and world == 1:   # one forward of the same weights and inputs in fp8 and in bf16 mode
+        if args.full and args.fp8 and nb == 3 and world == 1:   # one forward of the same weights and inputs in fp8 and in bf16 mode
             t_vec = torch.full((3,), float(ts[0]), dtype=torch.bfloat16, device=dev)
             cond = torch.zeros(3, L_img, 68, device=dev, dtype=torch.bfloat16)
             kw = dict(img=x.repeat(3, 1, 1), img_ids=img_ids, txt=txt, txt_ids=txt_ids, timesteps=t_vec, y_vec=y_vec, cond=cond)
@@ -696,6 +748,8 @@ def dit_line(args, dev, dist, rank, world, model_name, steps, warmup, with_b1, g
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
     assert torch.isfinite(x.float()).all(), "non-finite latents after the timed steps"
+    if outputs is not None:
+        outputs["latents"] = x
     ms_per_step = elapsed / steps * 1e3
     frames_per_s = T / (SAMPLING_STEPS * ms_per_step * 1e-3)
     if rank != 0:
@@ -787,6 +841,9 @@ def dit_line(args, dev, dist, rank, world, model_name, steps, warmup, with_b1, g
         "timing": f"time.perf_counter around EXACTLY {steps} steps between barrier + synchronize, mean (max over ranks); per-kernel figures "
                   "(roofline, roofline_gemm, rank_shapes) from HIP events on the launch stream",
     }
+    if not args.full:   # a plain run records no per-launch events
+        del out["roofline"], out["roofline_gemm"]
+        out["timing"] = out["timing"].split("; per-kernel")[0]
     if b1 is not None:
         out["b1"] = b1
     if side:

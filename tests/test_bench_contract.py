@@ -27,6 +27,29 @@ def test_defaults_and_flags(monkeypatch):
     a = b.parse()
     assert (a.gpus, a.steps, a.warmup) == (8, 5, 2)
     assert b.SAMPLING_STEPS == 30 and b.MFMA_BF16_PEAK_TFLOPS == 2500.0
+    assert a.full is False and a.dump_outputs is None      # a plain run times the headline only
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out_dir"])
+    a = b.parse()
+    assert a.full is True and a.dump_outputs == "out_dir"
+
+
+def test_dump_outputs_writes_float32_npy(tmp_path):
+    import numpy as np
+    import torch
+
+    b = _bench()
+    x = torch.randn(1, 40, 64, generator=torch.Generator().manual_seed(0)).to(torch.bfloat16)
+    b.dump_outputs(str(tmp_path / "d"), {"latents": x})
+    a = np.load(tmp_path / "d" / "latents.npy")
+    assert a.dtype == np.float32 and a.shape == (1, 40, 64) and np.array_equal(a, x.float().numpy())
+    # over the size limit: a fixed sample of each array, the same positions in every run, nothing larger than the limit
+    y = torch.randn(3, 1000, generator=torch.Generator().manual_seed(1))
+    for d in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / d), {"latents": x, "video": y}, limit_bytes=4000)
+    s1 = {n: np.load(tmp_path / "s1" / f"{n}.npy") for n in ("latents", "video")}
+    s2 = {n: np.load(tmp_path / "s2" / f"{n}.npy") for n in ("latents", "video")}
+    assert all(np.array_equal(s1[n], s2[n]) and s1[n].dtype == np.float32 for n in s1)
+    assert sum(v.nbytes for v in s1.values()) <= 4000 and set(s1["video"].tolist()) <= set(y.reshape(-1).tolist())
 
 
 def test_self_spawn_uses_one_rank_per_gpu_on_localhost(monkeypatch):

@@ -203,11 +203,11 @@ def test_blocks_with_a_large_weight_bound_take_the_bound_from_their_operands(cpu
 
 def test_processors_install_on_reference_blocks(cpu_mmdit):
     """The plug-in point of the reference itself: block.set_processor(...) on the reference's own
-    DoubleStreamBlock / SingleStreamBlock (only where /root/reference is mounted)."""
+    DoubleStreamBlock / SingleStreamBlock (only where the reference tree is available, see oracle/ref_loader.py)."""
     from oracle import ref_loader
 
     if not ref_loader.available():
-        pytest.skip("/root/reference not mounted")
+        pytest.skip(f"needs the reference tree (its own module classes are patched): none at {ref_loader.REF_ROOT}")
     cfg, B, T, h, w, L_txt = configs.GOLDEN["hd64_liger_split"]
     M, layers, _ = ref_loader.mmdit()
     ref = M.Flux(device_map="cpu", torch_dtype=torch.float32, **cfg)

@@ -176,7 +176,7 @@ def test_plugin_targets_run_on_the_reference_modules(cpu_vae):
     from oracle import make_golden, ref_loader
 
     if not ref_loader.available():
-        pytest.skip("/root/reference not mounted")
+        pytest.skip(f"needs the reference tree (its own module classes are patched): none at {ref_loader.REF_ROOT}")
     from open_sora_amd import vae_plugin
 
     cfg, B, T, H, W = configs.VAE_GOLDEN["c32_single_frame"] if "c32_single_frame" in configs.VAE_GOLDEN else next(iter(configs.VAE_GOLDEN.values()))
@@ -215,7 +215,7 @@ def test_plugin_refuses_configurations_the_engine_does_not_implement(cpu_vae):
     from oracle import ref_loader
 
     if not ref_loader.available():
-        pytest.skip("/root/reference not mounted")
+        pytest.skip(f"needs the reference tree (its own module classes are patched): none at {ref_loader.REF_ROOT}")
     from open_sora_amd import vae_plugin
 
     _, blocks = ref_loader.hunyuan_vae()

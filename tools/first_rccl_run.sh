@@ -29,7 +29,7 @@ for mode in auto allgather ulysses; do
   for n in 1 2 4 8; do
     [ "$n" -gt "$NGPU" ] && continue
     [ "$n" -eq 1 ] && [ "$mode" != auto ] && continue
-    OSK_SP_MODE=$mode timeout 1200 bash -c "$(declare -f run_n port); run_n $n bench.py --gpus $n --steps $STEPS --warmup $WARM --no-cpu-baseline --no-extra --no-b1" \
+    OSK_SP_MODE=$mode timeout 1200 bash -c "$(declare -f run_n port); run_n $n bench.py --full --gpus $n --steps $STEPS --warmup $WARM --no-cpu-baseline --no-extra --no-b1" \
       > "$OUT/bench_${mode}_n$n.json" 2> "$OUT/bench_${mode}_n$n.err"
     echo "bench mode=$mode n=$n rc=$? $(python - "$OUT/bench_${mode}_n$n.json" <<'PY'
 import json, sys
@@ -44,7 +44,7 @@ PY
 done
 # 3. kernel trace of the widest step (all ranks; rank 0's file is the one to read): RCCL kernels beside the MFMA loops
 N=$NGPU; [ "$N" -gt 8 ] && N=8
-( cd /tmp && timeout 1500 rocprofv3 --kernel-trace --stats -d "$OLDPWD/$OUT/prof_n$N" -- bash -c "cd $OLDPWD && $(declare -f run_n port); run_n $N bench.py --gpus $N --steps 4 --warmup 2 --no-cpu-baseline --no-extra --no-b1" \
+( cd /tmp && timeout 1500 rocprofv3 --kernel-trace --stats -d "$OLDPWD/$OUT/prof_n$N" -- bash -c "cd $OLDPWD && $(declare -f run_n port); run_n $N bench.py --full --gpus $N --steps 4 --warmup 2 --no-cpu-baseline --no-extra --no-b1" \
   > "$OLDPWD/$OUT/prof_n$N.log" 2>&1 ); echo "rocprofv3 n=$N rc=$?" | tee -a "$OUT/summary.txt"
 # 4. tile-parallel VAE: tiled decode of a 33-frame 720p latent, tiles spread over the ranks (bit-identical across world sizes)
 for n in 1 2 4 8; do

@@ -5,7 +5,7 @@ timeout 600 python -m pytest tests/test_gpu_vae.py -q -x -m gpu -k "conv" > $O/t
 if grep -q "failed\|error" $O/tests.log && [ -z "$FORCE" ]; then echo "tests failed: skipping timings"; exit 0; fi
 for rep in 1 2; do for lib in "" ${AB_LIBS:-tools/lib/libosk_conv_nosw2.so tools/lib/libosk_conv_nosw.so}; do OSK_ALT_LIB=$lib timeout 200 python tools/conv_ab.py 2>/dev/null | tee -a $O/conv_ab.jsonl; done; done
 for lib in "" ${AB_LIBS:-tools/lib/libosk_conv_nosw2.so tools/lib/libosk_conv_nosw.so}; do
-  OSK_ALT_LIB=$lib timeout 300 python tools/step_ab.py --workload vae --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | python -c "
+  OSK_ALT_LIB=$lib timeout 300 python tools/step_ab.py --full --workload vae --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); print(json.dumps(dict(lib='$lib' or 'shipped', ms=d['ms_per_step'], conv_ms=d['roofline'].get('total_conv_ms_per_step'), frac=d['roofline']['frac'])))" | tee -a $O/vae_ab.jsonl
 done

@@ -5,11 +5,11 @@ if [ -z "$SKIP_TESTS" ]; then
 echo "== pytest -m gpu"; timeout 1800 python -m pytest tests -q -m gpu --maxfail=10 --tb=short -p no:cacheprovider -rx > $O/pytest_gpu.log 2>&1; tail -6 $O/pytest_gpu.log
 echo "== smoke"; timeout 300 python __graft_entry__.py smoke > $O/smoke.log 2>&1; tail -2 $O/smoke.log
 fi
-echo "== bench (default line)"; timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; cut -c1-300 $O/bench.json; tail -2 $O/bench.err
+echo "== bench (default line)"; timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; cut -c1-300 $O/bench.json; tail -2 $O/bench.err
 for w in dit vae 11b; do
   echo "== rocprofv3 kernel stats: $w"; rm -rf $O/prof_$w
   args="--workload $w"; [ $w = 11b ] && args="--model 11B"; [ $w = dit ] && args=""
-  timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$w -o $w -- python bench.py $args --steps 3 --warmup 1 --no-cpu-baseline --no-b1 --no-extra > $O/prof_$w.json 2> $O/prof_$w.err
+  timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$w -o $w -- python bench.py --full $args --steps 3 --warmup 1 --no-cpu-baseline --no-b1 --no-extra > $O/prof_$w.json 2> $O/prof_$w.err
   f=$(find $O/prof_$w -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $O/${w}_kernel_stats.csv && head -8 "$f" | cut -c1-160; rm -rf $O/prof_$w
 done
 [ -n "$SKIP_PMC" ] && { echo "== done (PMC skipped)"; exit 0; }

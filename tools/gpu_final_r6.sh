@@ -5,18 +5,18 @@ if [ -z "$SKIP_TESTS" ]; then
 echo "== pytest -m gpu"; timeout 1800 python -m pytest tests -q -m gpu --maxfail=10 --tb=short -p no:cacheprovider -rx > $O/pytest_gpu.log 2>&1; tail -6 $O/pytest_gpu.log
 echo "== smoke"; timeout 300 python __graft_entry__.py smoke > $O/smoke.log 2>&1; tail -2 $O/smoke.log
 fi
-echo "== bench (default line)"; timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; cut -c1-300 $O/bench.json; tail -2 $O/bench.err
+echo "== bench (default line)"; timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; cut -c1-300 $O/bench.json; tail -2 $O/bench.err
 for w in dit vae 11b; do
   echo "== rocprofv3 kernel stats: $w"; rm -rf $O/prof_$w
   args="--workload $w"; [ $w = 11b ] && args="--model 11B"; [ $w = dit ] && args=""
-  timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$w -o $w -- python bench.py $args --steps 3 --warmup 1 --no-cpu-baseline --no-b1 --no-extra > $O/prof_$w.json 2> $O/prof_$w.err
+  timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$w -o $w -- python bench.py --full $args --steps 3 --warmup 1 --no-cpu-baseline --no-b1 --no-extra > $O/prof_$w.json 2> $O/prof_$w.err
   f=$(find $O/prof_$w -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $O/${w}_kernel_stats.csv && head -8 "$f" | cut -c1-160; rm -rf $O/prof_$w
 done
 echo "== packed GELU A/B inside the step (shipped vs the scalar-GELU build with the round-5 flags)"
 for i in 1 2; do
   for lib in shipped scalar_gelu; do
     if [ $lib = scalar_gelu ]; then export OSK_ALT_LIB=tools/lib/libosk_gemm_scalar_gelu.so; else unset OSK_ALT_LIB; fi
-    timeout 600 python tools/step_ab.py --steps 10 --warmup 2 --no-cpu-baseline --no-extra --no-b1 2>/dev/null | tail -1 | python -c "
+    timeout 600 python tools/step_ab.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-extra --no-b1 2>/dev/null | tail -1 | python -c "
 import json,sys
 r=json.loads(sys.stdin.read()); print(json.dumps({'lib':'$lib','run':$i,'ms_per_step':r['ms_per_step'],'attn_ms':r['roofline']['avg_launch_ms'],'gemm_ms_per_step':r['roofline_gemm']['block_linear_ms_per_step'],'gemm_frac':r['roofline_gemm']['frac']}))" >> $O/gelu_packed_ab.jsonl
   done

@@ -9,19 +9,19 @@ run() {  # name, counters, command...
 }
 export OSK_BENCH_NO_GN_FOLD=1
 if [ -z "$PMC_ONLY_DIT" ]; then
-run vae_fetch "FETCH_SIZE" python bench.py --workload vae --steps 1 --warmup 0 --no-cpu-baseline
-run vae_write "WRITE_SIZE" python bench.py --workload vae --steps 1 --warmup 0 --no-cpu-baseline
+run vae_fetch "FETCH_SIZE" python bench.py --full --workload vae --steps 1 --warmup 0 --no-cpu-baseline
+run vae_write "WRITE_SIZE" python bench.py --full --workload vae --steps 1 --warmup 0 --no-cpu-baseline
 # the same step with the opt-in GroupNorm fold (hunyuan_vae.FOLD_GN)
-OSK_VAE_FOLD_GN=1 run vaefold_fetch "FETCH_SIZE" python bench.py --workload vae --steps 1 --warmup 0 --no-cpu-baseline
-OSK_VAE_FOLD_GN=1 run vaefold_write "WRITE_SIZE" python bench.py --workload vae --steps 1 --warmup 0 --no-cpu-baseline
+OSK_VAE_FOLD_GN=1 run vaefold_fetch "FETCH_SIZE" python bench.py --full --workload vae --steps 1 --warmup 0 --no-cpu-baseline
+OSK_VAE_FOLD_GN=1 run vaefold_write "WRITE_SIZE" python bench.py --full --workload vae --steps 1 --warmup 0 --no-cpu-baseline
 if [ -n "$PMC_LINEAR_CONV" ]; then   # the round-1 tile mapping of conv256t for comparison
-  run vaelin_fetch "FETCH_SIZE" python bench.py --workload vae --steps 1 --warmup 0 --no-cpu-baseline
-  run vaelin_write "WRITE_SIZE" python bench.py --workload vae --steps 1 --warmup 0 --no-cpu-baseline
+  run vaelin_fetch "FETCH_SIZE" python bench.py --full --workload vae --steps 1 --warmup 0 --no-cpu-baseline
+  run vaelin_write "WRITE_SIZE" python bench.py --full --workload vae --steps 1 --warmup 0 --no-cpu-baseline
 fi
 fi
 if [ -z "$PMC_ONLY_VAE" ]; then
-run dit_fetch "FETCH_SIZE" python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-b1 --no-extra
-run dit_write "WRITE_SIZE" python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-b1 --no-extra
+run dit_fetch "FETCH_SIZE" python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-b1 --no-extra
+run dit_write "WRITE_SIZE" python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-b1 --no-extra
 fi
 python - "$O" <<'PY' | tee $O/summary.txt
 import csv, glob, collections, sys

@@ -3,7 +3,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; export TMPDIR=/tmp; O=gpurun_out; mkdir -p $O
 TAG=${PROF_TAG:-step}
 rm -rf $O/prof_$TAG
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$TAG -o $TAG -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-b1 ${BENCH_ARGS:-} > $O/prof_$TAG.json 2> $O/prof_$TAG.err
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$TAG -o $TAG -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-b1 ${BENCH_ARGS:-} > $O/prof_$TAG.json 2> $O/prof_$TAG.err
 cat $O/prof_$TAG.json | cut -c1-300
 f=$(find $O/prof_$TAG -name "*kernel_stats.csv" | head -1)
 python - "$f" <<'PY'

@@ -2,7 +2,7 @@
 # round 4: counters of the wide attention kernel (separate --pmc passes) and per-kernel stats of the step
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; export TMPDIR=/tmp; O=gpurun_out/r04f; rm -rf $O; mkdir -p $O
 rm -rf $O/prof_dit
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_dit -o dit -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-b1 --no-extra > $O/prof_dit.json 2> $O/prof_dit.err
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_dit -o dit -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-b1 --no-extra > $O/prof_dit.json 2> $O/prof_dit.err
 f=$(find $O/prof_dit -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $O/step_kernel_stats.csv && head -14 "$f" | cut -c1-170; rm -rf $O/prof_dit
 P=$O/pmc_attn; mkdir -p $P; i=0
 for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY" \

@@ -13,7 +13,7 @@ done
 OSK_ALT_LIB=tools/lib/libosk_nopk.so timeout 600 python tools/xproc_probe.py --victim gemv --aggressor none --stream-aggressor gemm256p --iters 4000 2>/dev/null | tail -1 | sed 's/^/{"lib": "nopk", "r": /; s/$/}/' >> $O/r06a_xproc_nopk.jsonl
 timeout 600 python tools/xproc_probe.py --victim gemv --aggressor gemm256p --iters 4000 2>/dev/null | tail -1 | sed 's/^/{"lib": "shipped", "r": /; s/$/}/' >> $O/r06a_xproc_nopk.jsonl
 cat $O/r06a_xproc_nopk.jsonl
-timeout 1500 python bench.py --steps 10 --warmup 2 > $O/r06a_bench.json 2> $O/r06a_bench.err
+timeout 1500 python bench.py --full --steps 10 --warmup 2 > $O/r06a_bench.json 2> $O/r06a_bench.err
 echo "bench rc=$?"; tail -c 3000 $O/r06a_bench.json; tail -5 $O/r06a_bench.err
 timeout 1500 bash tools/first_rccl_run.sh 3 1 > $O/r06a_first_rccl_dry.txt 2>&1
 echo "dry rc=$?"; cat $O/rccl_first/summary.txt

@@ -9,7 +9,7 @@ cut -c1-400 $O/r06k_rank_shapes.jsonl
 P=$O/pmc_step; rm -rf $P; mkdir -p $P
 for i in 1 2; do
   set="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU SQ_WAIT_INST_ANY"; [ $i = 2 ] && set="GRBM_GUI_ACTIVE SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_VMEM SQ_INSTS_SALU"
-  timeout 300 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $P/p$i -o p$i -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-b1 --no-extra > $P/p$i.log 2>&1
+  timeout 300 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $P/p$i -o p$i -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-b1 --no-extra > $P/p$i.log 2>&1
 done
 python - "$P" <<'PY' | tee $O/r06k_pmc_step_mfma.txt
 import csv, glob, collections, sys, re

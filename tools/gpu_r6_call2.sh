@@ -10,7 +10,7 @@ PROF_TAG=r06b_step BENCH_ARGS=--no-extra bash tools/gpu_prof_step.sh 2>&1 | tail
 for i in 1 2; do
   for lib in shipped nopk; do
     if [ $lib = nopk ]; then export OSK_ALT_LIB=tools/lib/libosk_nopk.so; else unset OSK_ALT_LIB; fi
-    timeout 600 python tools/step_ab.py --steps 10 --warmup 2 --no-cpu-baseline --no-extra 2>/dev/null | tail -1 | python -c "
+    timeout 600 python tools/step_ab.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-extra 2>/dev/null | tail -1 | python -c "
 import json,sys
 r=json.loads(sys.stdin.read()); print(json.dumps({'lib':'$lib','run':$i,'ms_per_step':r['ms_per_step'],'attn_ms':r['roofline']['avg_launch_ms'],'gemm_ms_per_step':r['roofline_gemm']['block_linear_ms_per_step'],'b1_ms':r['b1']['ms_per_step']}))" >> $O/r06b_step_ab_nopk.jsonl
   done

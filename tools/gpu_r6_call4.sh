@@ -19,7 +19,7 @@ cat $O/r06d_pkfp32_repro.jsonl
 for i in 1 2; do
   for lib in shipped narrowres; do
     if [ $lib = narrowres ]; then export OSK_ALT_LIB=tools/lib/libosk_conv_narrowres.so; else unset OSK_ALT_LIB; fi
-    timeout 600 python tools/run_with_lib.py bench.py --workload vae --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+    timeout 600 python tools/run_with_lib.py bench.py --full --workload vae --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import json,sys
 r=json.loads(sys.stdin.read()); print(json.dumps({'lib':'$lib','run':$i,'ms_per_step':r['ms_per_step'],'conv_ms':r['roofline']['total_conv_ms_per_step'],'gn_fold_ms':r['gn_fold']['ms_per_step']}))" >> $O/r06d_conv_res_ab.jsonl
   done
