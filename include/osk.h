@@ -402,6 +402,33 @@ int osk_causal_conv3d_gn_ndhwc_bf16(const void* x, int B, int T, int H, int W, i
                                     const void* res, void* out, int To, int Ho, int Wo,
                                     double* gn_sums, int gn_groups, void* stream);
 
+/* =====================================================================================================
+ * Flux 2-D autoencoder (/root/reference/opensora/models/vae/autoencoder_2d.py, the image stage of the t2i2v pipeline).
+ * Activations are NHWC bf16 ([B, H, W, C] contiguous, B = batch x frames as the reference folds T into the batch,
+ * autoencoder_2d.py:269-291); the mid attention, GroupNorm and 1x1 projections reuse the entry points of the causal VAE.
+ * ===================================================================================================== */
+
+/* ---- zero-padded Conv2d (+ optional fused nearest 2x upsample in front, + optional fused residual add behind).
+ * replaces every nn.Conv2d of autoencoder_2d.py: the 3x3 padding=1 convs of ResnetBlock / Upsample / conv_in / conv_out
+ * (:80-83,119,149,204,241), the interpolate(scale_factor=2, "nearest") of Upsample.forward (:121) when up != 0, the
+ * F.pad(x, (0, 1, 0, 1)) + stride-2 conv of Downsample (:107-113: pad = 0, stride = 2), the 1x1 nin_shortcut (:84) with
+ * ksize 1, and the `x + h` of ResnetBlock.forward (:101) when res != NULL.
+ *   x   bf16 [B, H, W, Cin]   source grid BEFORE the virtual upsample; Cin = 8 * 2^j (pad 3 -> 8 channels)
+ *   w   bf16 [Cout, w_row_stride], element [co][(dh*ksize + dw)*Cin + ci] = weight[co][ci][dh][dw];
+ *       rows zero-padded to w_row_stride >= round_up(ksize^2 * Cin, 64)
+ *   bias f32 [Cout] or NULL;  res bf16 [B, Ho, Wo, Cout] or NULL;  out bf16 [B, Ho, Wo, Cout]
+ *   ksize 1 or 3, stride 1 or 2; `pad` zero rows / columns in front (0 <= pad < ksize); every tap beyond the far edge of the
+ *   (upsampled: 2H x 2W) image reads zero as well.  Ho, Wo: the caller's output extent; each output window must start
+ *   inside the padded image ((Ho-1)*stride - pad <= Hu-1), so padding=1 -> Ho = Hu, Downsample -> Ho = Hu/2.
+ * f32 accumulate, one rounding (bias and residual added in f32).  128 x 128 x 64 implicit-GEMM tile on MFMA (csrc/conv2d.hip);
+ * the out-of-image taps are loaded from a zero page.
+ *   gn_sums: reserved for GroupNorm statistics of the output in the epilogue, with the contract of
+ *   osk_causal_conv3d_gn_ndhwc_bf16.  This kernel has no such epilogue: gn_sums != NULL returns OSK_EUNSUPPORTED and launches
+ *   NOTHING (the caller runs the plain conv + osk_groupnorm_stats_ndhwc_bf16). */
+int osk_conv2d_nhwc_bf16(const void* x, int B, int H, int W, int Cin, const void* w, int64_t w_row_stride,
+                         const float* bias, int Cout, int ksize, int stride, int pad, int up, const void* res,
+                         void* out, int Ho, int Wo, double* gn_sums, int gn_groups, void* stream);
+
 /* ---- GroupNorm statistics: sums[b][g] = (sum, sum of squares) in f64 over S voxels x C/G channels.
  * first half of nn.GroupNorm(32, C, eps=1e-6) (unet_causal_3d_blocks.py:216,218; vae.py:115,229; diffusers
  * Attention.group_norm).  x bf16 [B, S, C]; sums f64 [B, G, 2] (zeroed inside, on the stream).  C in

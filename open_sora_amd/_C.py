@@ -67,6 +67,8 @@ SIGNATURES = {
                                         _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp],
     "osk_causal_conv3d_gnin_ndhwc_bf16": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i32, _i32, _i32, _i32,
                                           _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp],
+    "osk_conv2d_nhwc_bf16": [_vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32,
+                             _vp, _i32, _vp],
     "osk_groupnorm_table_f32": [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _f32, _vp],
     "osk_groupnorm_stats_ndhwc_bf16": [_vp, _i32, _i64, _i32, _i32, _vp, _vp],
     "osk_groupnorm_apply_ndhwc_bf16": [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _f32, _i32, _vp],
@@ -755,6 +757,29 @@ def causal_conv3d_gn_in(x: torch.Tensor, table: torch.Tensor, w: torch.Tensor, b
         ev1.record()
         prof.append((ev0, ev1, 2.0 * Cin * Cout * ksize ** 3 * B * To * Ho * Wo))
     return True, fused
+
+
+def conv2d(x: torch.Tensor, w: torch.Tensor, bias, out: torch.Tensor, ksize: int, stride: int = 1, pad: int = 1, up: bool = False,
+           res=None) -> torch.Tensor:
+    """zero-padded 2-D conv, NHWC bf16.  x [B, H, W, Cin] contiguous, Cin = 8 * 2^j; w bf16 [Cout, Kpad] (tap-major,
+    channel-minor, zero padded); bias f32 [Cout] | None; out bf16 [B, Ho, Wo, Cout] contiguous (its extent is the caller's: `pad`
+    zero rows / columns in front, zeros behind as far as the extent reads); res like out | None.  The C entry's fused-statistics
+    argument is not bound: the kernel has no such epilogue (osk.h)."""
+    B, H, W, Cin = x.shape
+    Cout = w.shape[0]
+    Ho, Wo = out.shape[1], out.shape[2]
+    assert x.is_contiguous() and out.is_contiguous() and tuple(out.shape) == (B, Ho, Wo, Cout), (out.shape, (B, Ho, Wo, Cout))
+    assert res is None or (res.is_contiguous() and res.shape == out.shape)
+    prof = PROFILE_CONV
+    if prof is not None:
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+    _check(lib.osk_conv2d_nhwc_bf16(x.data_ptr(), B, H, W, Cin, w.data_ptr(), w.stride(0), _p(bias), Cout, ksize, stride, pad,
+                                    int(up), _p(res), out.data_ptr(), Ho, Wo, None, 0, _stream()), "osk_conv2d_nhwc_bf16")
+    if prof is not None:
+        ev1.record()
+        prof.append((ev0, ev1, 2.0 * Cin * Cout * ksize ** 2 * B * Ho * Wo))
+    return out
 
 
 def groupnorm_table(sums: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, table: torch.Tensor, S: int, G: int,

@@ -263,7 +263,11 @@ def _plan(mod, kind):
         elif kind == "gn":
             p = (leaf.weight.detach().float().contiguous(), leaf.bias.detach().float().contiguous(), leaf.num_groups, leaf.eps)
         elif kind == "lin":
-            p = (leaf.weight.detach().to(BF16).contiguous(), leaf.bias.detach().float().contiguous())
+            # (an nn.Linear, or a 1 x 1 nn.Conv2d: weight [Cout, Cin, 1, 1] -> [Cout, Cin])
+            p = (leaf.weight.detach().reshape(leaf.weight.shape[0], -1).to(BF16).contiguous(), leaf.bias.detach().float().contiguous())
+        elif kind == "conv2d":
+            from .flux_ae import _Conv2dPlan
+            p = _Conv2dPlan(leaf)
         if _drop_plan not in leaf._load_state_dict_post_hooks.values():
             leaf.register_load_state_dict_post_hook(_drop_plan)
         _PLANS[leaf] = (key, p)
@@ -387,15 +391,22 @@ def _mid_attention(att: Attention, x: Tensor) -> Tensor:
     C = 512 (every shipped width): osk_attention_hd512_fwd_bf16 -- scores stay in registers, the mask is a predicate, one
     launch for the whole batch.  Other widths (test geometries): QK^T and P.V as GEMMs around the masked-softmax kernel.
     P V + b_v == P (V + 1 b_v^T) because softmax rows sum to one: the V bias is added after the product either way."""
+    return _one_head_attention(x, att.group_norm, att.to_q, att.to_k, att.to_v, att.to_out[0])
+
+
+def _one_head_attention(x: Tensor, norm: nn.GroupNorm, to_q, to_k, to_v, to_out) -> Tensor:
+    """x + to_out(attention(norm(x))) with one head of dim C, frame-causal over the T frames of x [B, T, H, W, C] (one frame:
+    plain full attention -- the Flux image autoencoder's AttnBlock runs through here with T = 1).  to_*: nn.Linear or 1 x 1
+    nn.Conv2d layers."""
     o = _ops()
     B, T, H, W, C = x.shape
     S, n_hw = T * H * W, H * W
     Sp = (S + 63) // 64 * 64
-    wq, bq = _plan(att.to_q, "lin")
-    wk, bk = _plan(att.to_k, "lin")
-    wv, bv = _plan(att.to_v, "lin")
-    wo, bo = _plan(att.to_out[0], "lin")
-    hn = _gn(att.group_norm, x, False).view(B, S, C)
+    wq, bq = _plan(to_q, "lin")
+    wk, bk = _plan(to_k, "lin")
+    wv, bv = _plan(to_v, "lin")
+    wo, bo = _plan(to_out, "lin")
+    hn = _gn(norm, x, False).view(B, S, C)
     tok = x.view(B, S, C)
     out = torch.empty_like(tok)
     ones = torch.ones(C, dtype=torch.float32, device=x.device)

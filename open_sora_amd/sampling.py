@@ -5,6 +5,8 @@ either side of MMDiTModel.forward:
     get_oscillation_gs :120-133    time_shift / get_res_lin_function / get_schedule :295-332
     get_noise :335-372             pack / unpack :375-393         prepare_ids (from prepare :431-447)
     I2VDenoiser.denoise :159-226   (CFG triple, oscillating guidance, Euler update)
+    DistilledDenoiser :246-279      (guidance-distilled Flux image sampling of the t2i2v pipeline)
+    SamplingMethodDict :282-285    (keyed by the values of opensora/utils/inference.py:16-18, SamplingMethod)
 Schedules are Python floats; tensors stay on the device; the CFG combine + Euler update is one HIP kernel
 (osk_cfg_euler_bf16) instead of six bf16 elementwise launches.
 """
@@ -193,3 +195,59 @@ class I2VDenoiser:
         if neg is None:
             neg = [""] * len(text)
         return text + neg + neg, ret
+
+
+class DistilledDenoiser:
+    """sampling.py:246-279.  `denoise(model, img=..., timesteps=[...], guidance=..., img_ids=..., txt=..., txt_ids=..., y_vec=...)`:
+    no CFG triple -- the guidance value goes into the model's guidance embedding (guidance_embed=True, the flux-dev image model of
+    the t2i2v pipeline) and the Euler update `img + (t_prev - t_curr) * pred` runs in img's dtype with the reference's torch ops,
+    so the state matches the reference's bit for bit for the same model outputs.
+
+    Not in the reference: `hip_graph=True` replays the model forward of steps 1.. from a hipGraph captured after step 0, as in
+    I2VDenoiser (the latent and the timestep vector live in fixed buffers).  Same results bit for bit."""
+
+    def denoise(self, model, **kwargs) -> Tensor:
+        img = kwargs.pop("img")
+        timesteps = kwargs.pop("timesteps")
+        guidance = kwargs.pop("guidance")
+        hip_graph = bool(kwargs.pop("hip_graph", False))
+        guidance_vec = torch.full((img.shape[0],), guidance, device=img.device, dtype=img.dtype)
+        if not hip_graph:
+            for t_curr, t_prev in zip(timesteps[:-1], timesteps[1:]):
+                t_vec = torch.full((img.shape[0],), t_curr, dtype=img.dtype, device=img.device)
+                pred = model(img=img, **kwargs, timesteps=t_vec, guidance=guidance_vec)
+                img = img + (t_prev - t_curr) * pred
+            return img
+        dev = img.device
+        side = _SIDE_STREAMS.get(str(dev))
+        if side is None:
+            side = _SIDE_STREAMS[str(dev)] = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            x = img.clone()                                   # the fixed input buffer of the captured forward
+            t_vec = torch.empty(img.shape[0], dtype=img.dtype, device=dev)
+            graph, pred = None, None
+            for i, (t_curr, t_prev) in enumerate(zip(timesteps[:-1], timesteps[1:])):
+                t_vec.fill_(t_curr)
+                if graph is not None:
+                    graph.replay()
+                else:
+                    pred = model(img=x, **kwargs, timesteps=t_vec, guidance=guidance_vec)
+                    if i == 0 and len(timesteps) > 2:
+                        graph = torch.cuda.CUDAGraph()
+                        with torch.cuda.graph(graph, stream=side):
+                            pred_g = model(img=x, **kwargs, timesteps=t_vec, guidance=guidance_vec)
+                x.copy_(x + (t_prev - t_curr) * pred)
+                if graph is not None:
+                    pred = pred_g
+        torch.cuda.current_stream(dev).wait_stream(side)
+        return x
+
+    def prepare_guidance(self, text: list, optional_models: dict, device, dtype, **kwargs):
+        return text, {}
+
+
+SamplingMethodDict = {
+    "i2v": I2VDenoiser(),
+    "distill": DistilledDenoiser(),
+}
