@@ -495,6 +495,69 @@ int64_t osk_attention_hd512_workspace_bytes(int B, int S);
  * (NCTHW tiles: blend_t -> outer B*C, inner H*W; blend_v -> outer B*C*T, inner W; blend_h -> outer B*C*T*H, inner 1). */
 int osk_blend_bf16(const void* a, void* b, int64_t outer, int Da, int Db, int extent, int64_t inner, void* stream);
 
+/* =====================================================================================================
+ * Video DC-AE decoder (/root/reference/opensora/models/dc_ae, "dc-ae-f32t4c128": the autoencoder of
+ * configs/diffusion/inference/high_compression.py).  Activations are NDHWC bf16 ([B, T, H, W, C] contiguous); the 1x1x1
+ * convolutions without an activation are osk_gemm_bf16 over the B*T*H*W rows.  (Added without changing any existing contract:
+ * the version stays 2.)  csrc/dc_ae.hip.
+ * ===================================================================================================== */
+
+/* ---- zero-padded Conv3d, stride 1, "same" padding in T, H and W (+ nearest upsample in front, + SiLU, + residual add behind).
+ * replaces ConvLayer(is_video=True) of dc_ae/models/nn/ops.py:56-136 -- F.pad(x, (k/2,)*6, "constant") + ChannelChunkConv3d
+ * (:87-96,130-131) and its act (:134-135) -- for every dense conv of the decoder: project_in (dc_ae.py:314-324), the
+ * InterpolateConvUpSampleLayer convs with their chunked_interpolate(scale_factor=[1|2, 2, 2], "nearest") in front (ops.py:285-295:
+ * up_t, up_hw), ResBlock conv1 (+ SiLU) / conv2 (ops.py:615-639), project_out's conv (dc_ae.py:352-362), the 1x1x1
+ * GLUMBConv.inverted_conv (+ SiLU, ops.py:552-560), and the `main + shortcut` of ResidualBlock.forward (ops.py:923) when res != NULL.
+ *   x   bf16 [B, T, H, W, Cin]  source grid BEFORE the virtual upsample; Cin = 8 * 2^j
+ *   w   bf16 [Cout, w_row_stride], element [co][((dt*k + dh)*k + dw)*Cin + ci] = weight[co][ci][dt][dh][dw];
+ *       rows zero-padded to w_row_stride >= round_up(k^3 * Cin, 64)
+ *   bias f32 [Cout] | NULL;  res bf16 like out | NULL;  out bf16 [B, T << up_t, H << up_hw, W << up_hw, Cout]
+ *   out = bf16( act(acc + bias) + res ), act = SiLU when act != 0; f32 accumulate, one rounding.
+ * 128 x 128 x 64 implicit-GEMM tile on MFMA, out-of-volume taps loaded from a zero page; any Cout >= 1 (Cout = 3 runs on the
+ * same tile with 3 live columns).  Cin not 8 * 2^j or a volume beyond 2^31 voxels: OSK_EUNSUPPORTED, nothing launched. */
+int osk_conv3d_zp_ndhwc_bf16(const void* x, int B, int T, int H, int W, int Cin, const void* w, int64_t w_row_stride,
+                             const float* bias, int Cout, int ksize, int up_t, int up_hw, int act, const void* res,
+                             void* out, void* stream);
+
+/* ---- channel-duplicating pixel shuffle: the shortcut of the upsample blocks and of project_in.
+ * replaces ChannelDuplicatingPixelShuffleUpSampleLayer.forward (ops.py:316-337): repeat_interleave(rep, dim=1) + pixel_shuffle_3d
+ * (vo_ops.py:11-35; ft = fhw = 2), + F.pixel_shuffle on H, W only (the T == 1 / no temporal upsample branch, ops.py:333-336;
+ * ft = 1, fhw = 2), + the factor-1 form of project_in (ft = fhw = 1), rep = Cout * ft * fhw^2 / Cin (must divide):
+ *   out[b, t, h, w, co] = x[b, t / ft, h / fhw, w / fhw, (((co*ft + t % ft)*fhw + h % fhw)*fhw + w % fhw) / rep]
+ * x bf16 [B, T, H, W, Cin]; out bf16 [B, T*ft, H*fhw, W*fhw, Cout], Cout % 8 == 0.  A gather, HBM bound. */
+int osk_dup_shuffle_ndhwc_bf16(const void* x, int B, int T, int H, int W, int Cin, void* out, int Cout, int ft, int fhw,
+                               void* stream);
+
+/* ---- depthwise Conv3d, k = 3 or 5, zero "same" padding, + bias, + GLU.
+ * replaces GLUMBConv.depth_conv and the chunk / silu / multiply behind it (ops.py:561-571,584-588; glu != 0: out has C / 2 channels,
+ * out[c] = (y[c] + b[c]) * silu(y[c + C/2] + b[c + C/2])) and LiteMLA.aggreg[0][0] (ops.py:684-691; k = 5, no bias, glu = 0).
+ *   x bf16 [B, T, H, W, C];  w bf16 [k^3, C], element [(dt*k + dh)*k + dw][c] = weight[c][0][dt][dh][dw];  bias f32 [C] | NULL
+ * f32 accumulate, one rounding.  C % 8 (glu: % 16) != 0 or another k: OSK_EUNSUPPORTED. */
+int osk_dwconv3d_ndhwc_bf16(const void* x, int B, int T, int H, int W, int C, const void* w, const float* bias, int ksize,
+                            int glu, void* out, void* stream);
+
+/* ---- block-diagonal 1x1x1 conv, 32 -> 32 channels per group, no bias.
+ * replaces LiteMLA.aggreg[0][1] (ops.py:692: groups = 3 * heads, dim 32).  x, out bf16 [M, C]; w bf16 [C, 32] =
+ * weight[co][ci] (ci within co's group).  MFMA, f32 accumulate.  C % 32 != 0: OSK_EUNSUPPORTED. */
+int osk_gconv32_bf16(const void* x, int64_t M, int C, const void* w, void* out, void* stream);
+
+/* ---- ReLU linear attention, head dim 32.
+ * replaces LiteMLA.relu_linear_att (ops.py:709-765).  qkv bf16 [B, N, G * 96]: G consecutive [q | k | v] groups of 3 x 32
+ * channels.  Per (b, g):  KV = sum_n [v_n ; 1] relu(k_n)^T  (33 x 32),  o_n = KV relu(q_n),  out_n = o_n[:32] / (o_n[32] + eps).
+ * out bf16: row (b, n) at out + (b*N + n) * out_row_stride, columns g*32 .. g*32 + 31 (so two scales write one [.., 2C] tensor).
+ * All sums in f32.  workspace: f32, >= B * G * nsplit * 1056 * 4 bytes; the tokens are cut into nsplit runs whose partial KV are
+ * summed in a fixed order (deterministic).  B * G > 65535 or nsplit > 1024: OSK_EUNSUPPORTED. */
+int osk_relu_linear_attn_bf16(const void* qkv, int B, int N, int G, void* out, int64_t out_row_stride, float* workspace,
+                              int64_t workspace_bytes, int nsplit, float eps, void* stream);
+
+/* ---- RMSNorm over channels with affine weight and bias (+ ReLU, + shortcut add).
+ * replaces RMSNorm3d.forward (dc_ae/models/nn/norm.py:63-68, eps 1e-5), the ReLU behind project_out's norm (dc_ae.py:346-349)
+ * when relu != 0, and the identity-shortcut add of ResidualBlock.forward (ops.py:923) when res != NULL:
+ *   out = act(x * rsqrt(mean_c(x^2) + eps) * weight + bias) + res.   x, res, out bf16 [M, C]; weight, bias f32 [C]; C % 8 == 0.
+ * f32 statistics, one rounding. */
+int osk_rmsnorm_affine_bf16(const void* x, int64_t M, int C, const float* weight, const float* bias, float eps,
+                            const void* res, int relu, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -79,6 +79,12 @@ SIGNATURES = {
     "osk_attention_hd512_workspace_bytes": [_i32, _i32],
     "osk_attention_hd512_fwd_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _i32,
                                      _i32, _f32, _vp],
+    "osk_conv3d_zp_ndhwc_bf16": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
+    "osk_dup_shuffle_ndhwc_bf16": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp],
+    "osk_dwconv3d_ndhwc_bf16": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp],
+    "osk_gconv32_bf16": [_vp, _i64, _i32, _vp, _vp, _vp],
+    "osk_relu_linear_attn_bf16": [_vp, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _f32, _vp],
+    "osk_rmsnorm_affine_bf16": [_vp, _i64, _i32, _vp, _vp, _f32, _vp, _i32, _vp, _vp],
 }
 
 
@@ -866,4 +872,93 @@ def attention_hd512(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, bias_v, 
                                                out.stride(0), out.stride(1), B, S, keys_per_frame, scale, _p(workspace),
                                                0 if workspace is None else workspace.numel() * workspace.element_size(), _stream()),
            "osk_attention_hd512_fwd_ws_bf16")
+    return out
+
+
+# ----------------------------------------------------------------------------------------------
+# Video DC-AE decoder (csrc/dc_ae.hip)
+# ----------------------------------------------------------------------------------------------
+def conv3d_zp(x: torch.Tensor, w: torch.Tensor, bias, out: torch.Tensor, ksize: int, up_t: bool = False, up_hw: bool = False,
+              silu: bool = False, res=None) -> torch.Tensor:
+    """zero-padded stride-1 "same" 3-D conv, NDHWC bf16.  x [B, T, H, W, Cin] contiguous, Cin = 8 * 2^j; w bf16 [Cout, Kpad]
+    (tap-major, channel-minor, zero padded); bias f32 [Cout] | None; out bf16 [B, T << up_t, H << up_hw, W << up_hw, Cout];
+    res like out | None (added after the optional SiLU)."""
+    B, T, H, W, Cin = x.shape
+    Cout = w.shape[0]
+    want = (B, T << int(up_t), H << int(up_hw), W << int(up_hw), Cout)
+    assert x.is_contiguous() and out.is_contiguous() and tuple(out.shape) == want, (out.shape, want)
+    assert x.dtype == w.dtype == out.dtype == torch.bfloat16
+    assert res is None or (res.is_contiguous() and res.shape == out.shape and res.dtype == torch.bfloat16)
+    prof = PROFILE_CONV
+    if prof is not None:
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+    _check(lib.osk_conv3d_zp_ndhwc_bf16(x.data_ptr(), B, T, H, W, Cin, w.data_ptr(), w.stride(0), _p(bias), Cout, ksize, int(up_t),
+                                        int(up_hw), int(silu), _p(res), out.data_ptr(), _stream()), "osk_conv3d_zp_ndhwc_bf16")
+    if prof is not None:
+        ev1.record()
+        prof.append((ev0, ev1, 2.0 * Cin * Cout * ksize ** 3 * out.numel() / Cout))
+    return out
+
+
+def dup_shuffle(x: torch.Tensor, out: torch.Tensor, ft: int, fhw: int) -> torch.Tensor:
+    """channel-duplicating pixel shuffle: x bf16 [B, T, H, W, Cin] -> out bf16 [B, T*ft, H*fhw, W*fhw, Cout]"""
+    B, T, H, W, Cin = x.shape
+    Cout = out.shape[-1]
+    assert x.is_contiguous() and out.is_contiguous() and tuple(out.shape) == (B, T * ft, H * fhw, W * fhw, Cout), out.shape
+    assert x.dtype == out.dtype == torch.bfloat16
+    _check(lib.osk_dup_shuffle_ndhwc_bf16(x.data_ptr(), B, T, H, W, Cin, out.data_ptr(), Cout, ft, fhw, _stream()),
+           "osk_dup_shuffle_ndhwc_bf16")
+    return out
+
+
+def dwconv3d(x: torch.Tensor, w: torch.Tensor, bias, out: torch.Tensor, ksize: int, glu: bool = False) -> torch.Tensor:
+    """depthwise zero-padded conv: x bf16 [B, T, H, W, C]; w bf16 [k^3, C]; bias f32 [C] | None; out bf16 [B, T, H, W, C or C / 2]"""
+    B, T, H, W, C = x.shape
+    assert x.is_contiguous() and out.is_contiguous() and tuple(out.shape) == (B, T, H, W, C // 2 if glu else C), out.shape
+    assert tuple(w.shape) == (ksize ** 3, C) and w.is_contiguous() and x.dtype == w.dtype == out.dtype == torch.bfloat16
+    _check(lib.osk_dwconv3d_ndhwc_bf16(x.data_ptr(), B, T, H, W, C, w.data_ptr(), _p(bias), ksize, int(glu), out.data_ptr(),
+                                       _stream()), "osk_dwconv3d_ndhwc_bf16")
+    return out
+
+
+def gconv32(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """block-diagonal 1x1x1 conv (32 -> 32 per group): x, out bf16 [..., C] contiguous; w bf16 [C, 32]"""
+    C = x.shape[-1]
+    assert x.is_contiguous() and out.is_contiguous() and out.shape == x.shape and tuple(w.shape) == (C, 32) and w.is_contiguous()
+    assert x.dtype == w.dtype == out.dtype == torch.bfloat16
+    _check(lib.osk_gconv32_bf16(x.data_ptr(), x.numel() // C, C, w.data_ptr(), out.data_ptr(), _stream()), "osk_gconv32_bf16")
+    return out
+
+
+def relu_linear_attn_nsplit(N: int) -> int:
+    """runs of tokens the K^T V pass is cut into: one per 512 tokens, at most 64"""
+    return max(1, min(64, (N + 511) // 512))
+
+
+def relu_linear_attn(qkv: torch.Tensor, out: torch.Tensor, eps: float = 1e-15, workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """qkv bf16 [B, N, G * 96] contiguous ([q | k | v] groups of 3 x 32); out bf16 [B, N, >= G * 32] view with contiguous last dim
+    and rows (the first G * 32 columns are written)."""
+    B, N, C3 = qkv.shape
+    G = C3 // 96
+    assert C3 == G * 96 and qkv.is_contiguous() and qkv.dtype == out.dtype == torch.bfloat16
+    assert out.shape[0] == B and out.shape[1] == N and out.stride(2) == 1 and out.stride(0) == N * out.stride(1), out.stride()
+    nsplit = relu_linear_attn_nsplit(N)
+    need = B * G * nsplit * 1056
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.float32, device=qkv.device)
+    _check(lib.osk_relu_linear_attn_bf16(qkv.data_ptr(), B, N, G, out.data_ptr(), out.stride(1), workspace.data_ptr(),
+                                         workspace.numel() * 4, nsplit, eps, _stream()), "osk_relu_linear_attn_bf16")
+    return out
+
+
+def rmsnorm_affine(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, out: torch.Tensor, eps: float = 1e-5, res=None,
+                   relu: bool = False) -> torch.Tensor:
+    """x, out, res bf16 [..., C] contiguous; weight, bias f32 [C].  out = act(rmsnorm(x) * weight + bias) + res"""
+    C = x.shape[-1]
+    assert x.is_contiguous() and out.is_contiguous() and out.shape == x.shape and x.dtype == out.dtype == torch.bfloat16
+    assert weight.dtype == bias.dtype == torch.float32 and weight.numel() == bias.numel() == C
+    assert res is None or (res.is_contiguous() and res.shape == x.shape and res.dtype == torch.bfloat16)
+    _check(lib.osk_rmsnorm_affine_bf16(x.data_ptr(), x.numel() // C, C, weight.data_ptr(), bias.data_ptr(), eps, _p(res), int(relu),
+                                       out.data_ptr(), _stream()), "osk_rmsnorm_affine_bf16")
     return out
