@@ -98,6 +98,34 @@ def conv_same(x, w, b=None, groups: int = 1):
     return F.conv3d(F.pad(x, (p,) * 6) if p else x, w, b, groups=groups)
 
 
+def conv_same_taps(x, w, b=None, groups: int = 1):
+    """conv_same written out as a sum over the k^3 taps, channels last: one matmul per tap (dense), one product per tap
+    (depthwise), one batched matmul (grouped 1x1x1).  The same arithmetic in plain torch, with F.conv3d's number format: the sum
+    runs in fp32 on the operands as stored and is rounded ONCE to x's dtype (so in bf16 it is neither tighter nor looser a
+    comparator than F.conv3d).  For the GPU, where F.conv3d compiles its kernels per shape on first use (minutes for the
+    shipped-width tile; seconds through this).  tests/test_dc_ae_host.py pins it to conv_same and to the reference's golden."""
+    k = w.shape[2]
+    p = k // 2
+    B, C, T, H, W = x.shape
+    xs = (F.pad(x, (p,) * 6) if p else x).permute(0, 2, 3, 4, 1).float()
+    wf = w.float()
+    if groups not in (1, C):
+        assert k == 1 and w.shape[0] == C
+        per = C // groups
+        y = torch.einsum("nthwgi,goi->nthwgo", xs.reshape(B, T, H, W, groups, per), wf.reshape(groups, per, per)).reshape(B, T, H, W, C)
+    else:
+        y = None
+        for dt in range(k):
+            for dh in range(k):
+                for dw in range(k):
+                    win = xs[:, dt:dt + T, dh:dh + H, dw:dw + W, :]
+                    t = win @ wf[:, :, dt, dh, dw].T if groups == 1 else win * wf[:, 0, dt, dh, dw]
+                    y = t if y is None else y.add_(t)
+    if b is not None:
+        y = y + b.float()
+    return y.to(x.dtype).permute(0, 4, 1, 2, 3)
+
+
 def rms_norm(x, w, b):
     y = (x / torch.sqrt(x.float().square().mean(dim=1, keepdim=True) + EPS_NORM)).to(x.dtype)
     return y * w.view(1, -1, 1, 1, 1) + b.view(1, -1, 1, 1, 1)
@@ -138,16 +166,19 @@ def relu_linear_att(qkv):
     return out.reshape(B, -1, T, H, W)
 
 
-def decode(sd: dict, cfg: dict, z):
-    """Decoder.forward on z [B, latent, T, H, W] in z's dtype (sd must hold the same dtype)"""
+def decode(sd: dict, cfg: dict, z, taps: bool = False):
+    """Decoder.forward on z [B, latent, T, H, W] in z's dtype (sd must hold the same dtype).  taps: every conv through
+    conv_same_taps instead of F.conv3d"""
     W, D = cfg["width_list"], cfg["depth_list"]
     n = len(W)
+
+    same = conv_same_taps if taps else conv_same
 
     def P(key):
         return sd.get(key)
 
     def conv(key, x, groups=1):
-        return conv_same(x, sd[key + ".conv.weight"], P(key + ".conv.bias"), groups)
+        return same(x, sd[key + ".conv.weight"], P(key + ".conv.bias"), groups)
 
     x = conv("decoder.project_in.main", z) + dup_shortcut(z, W[-1], 1, False)
     for sid in reversed(range(n)):
@@ -167,8 +198,8 @@ def decode(sd: dict, cfg: dict, z):
                 m = b + ".context_module.main"
                 qkv = conv(m + ".qkv", x)
                 c3 = qkv.shape[1]
-                agg = conv_same(qkv, sd[m + ".aggreg.0.0.weight"], None, groups=c3)
-                agg = conv_same(agg, sd[m + ".aggreg.0.1.weight"], None, groups=c3 // DIM)
+                agg = same(qkv, sd[m + ".aggreg.0.0.weight"], None, groups=c3)
+                agg = same(agg, sd[m + ".aggreg.0.1.weight"], None, groups=c3 // DIM)
                 both = torch.cat([qkv, agg], dim=1)
                 att = relu_linear_att(both).to(both.dtype)
                 h = conv(m + ".proj", att)

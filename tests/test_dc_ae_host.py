@@ -77,6 +77,31 @@ def test_restatement_matches_reference_golden(golden):
     assert rel_l2(by_cols, torch.from_numpy(golden["dec_c_cols"])) <= 1e-5
 
 
+def test_restatement_tap_sum_convs_match_reference_golden(golden):
+    """decode(taps=True), the form the operating-point GPU tests evaluate: in fp32 the same output as through F.conv3d; in
+    bf16 a comparator of the same precision (its error against the golden is not larger than F.conv3d's by more than 25 %)"""
+    sd = R.make_state_dict(R.param_shapes(R.SMALL))
+    sd_b = {k: v.to(BF) for k, v in sd.items()}
+    with torch.no_grad():
+        for tag in ("a", "b"):
+            z, want = torch.from_numpy(golden["z_" + tag]), torch.from_numpy(golden["dec_" + tag])
+            out = R.decode(sd, R.SMALL, z, taps=True)
+            assert rel_l2(out, want) <= 1e-5
+            assert rel_l2(out, R.decode(sd, R.SMALL, z)) <= 1e-5
+            e_taps = rel_l2(R.decode(sd_b, R.SMALL, z.to(BF), taps=True), want)
+            e_conv = rel_l2(finite_retry(lambda: R.decode(sd_b, R.SMALL, z.to(BF))), want)
+            print(f"bf16 restatement ({tag}): relL2 taps {e_taps:.3e} F.conv3d {e_conv:.3e}")
+            assert e_taps <= 1.25 * e_conv
+        g = torch.Generator().manual_seed(4)
+        x, w, b = torch.randn(2, 64, 3, 4, 5, generator=g), torch.randn(6, 64, 3, 3, 3, generator=g), torch.randn(6, generator=g)
+        assert rel_l2(R.conv_same_taps(x, w, b), R.conv_same(x, w, b)) <= 1e-6                                  # dense
+        assert rel_l2(R.conv_same_taps(x, w[:, :, :1, :1, :1]), R.conv_same(x, w[:, :, :1, :1, :1])) <= 1e-6     # 1x1x1
+        wd = torch.randn(64, 1, 5, 5, 5, generator=g)
+        assert rel_l2(R.conv_same_taps(x, wd, None, 64), R.conv_same(x, wd, None, 64)) <= 1e-6                   # depthwise
+        wg = torch.randn(64, 32, 1, 1, 1, generator=g)
+        assert rel_l2(R.conv_same_taps(x, wg, None, 2), R.conv_same(x, wg, None, 2)) <= 1e-6                     # grouped
+
+
 @needs_ref
 def test_restatement_matches_live_reference():
     from tools.make_golden_dc_ae import reference_dcae

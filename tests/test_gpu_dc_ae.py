@@ -15,6 +15,7 @@ import torch
 
 from tests import cpu_ops_dc_ae as E
 from tests import dc_ae_restatement as R
+from tests.dc_ae_audit import _judge, conv_border, dw_border
 from tests.util import assert_parity, finite_retry
 
 BF = torch.bfloat16
@@ -38,23 +39,6 @@ def _gen(name):
 
 def _randn(shape, g, scale=1.0):
     return (scale * torch.randn(shape, generator=g, device=DEV)).to(BF)
-
-
-def _judge(name, out, y, border=None):
-    """|out - y| <= 2^-8 |y| + 1e-4 max|y| everywhere; border and interior reported and asserted separately"""
-    assert torch.isfinite(out.float()).all(), name
-    err = (out.double() - y).abs()
-    bound = 2.0 ** -8 * y.abs() + 1e-4 * float(y.abs().max())
-    if border is None:
-        print(f"{name}: max-abs {float(err.max()):.3e} (max |y| {float(y.abs().max()):.3e})")
-        assert bool((err <= bound).all()), f"{name}: off by up to {float(err.max()):.3e}"
-        return
-    border = border.expand_as(err)
-    e_b = float(err[border].max())
-    e_i = float(err[~border].max()) if (~border).any() else 0.0
-    print(f"{name}: max-abs border {e_b:.3e} interior {e_i:.3e} (max |y| {float(y.abs().max()):.3e})")
-    assert bool((err[border] <= bound[border]).all()), f"{name}: border voxels off by up to {e_b:.3e}"
-    assert bool((err[~border] <= bound[~border]).all()), f"{name}: interior off by up to {e_i:.3e}"
 
 
 # (name, Cin, Cout, T, H, W (source), ksize, up_t, up_hw, res, bias, silu)
@@ -96,10 +80,7 @@ def test_conv3d_zp_kernel_vs_f64(dc_ae, hip_lib, case):
     hip_lib.conv3d_zp(x, plan.w, plan.b, out, k, up_t, up_hw, silu, res)
     torch.cuda.synchronize()
     y = E.conv3d_zp_ref(x, plan.w, plan.b, k, up_t, up_hw, silu, res, dtype=torch.float64)
-    border = torch.zeros(To, Ho, Wo, dtype=torch.bool, device=DEV)
-    border[:1], border[-1:] = True, True
-    border[:, :2], border[:, -2:], border[:, :, :2], border[:, :, -2:] = True, True, True, True
-    _judge(name, out, y, border[None, :, :, :, None])
+    _judge(name, out, y, conv_border(To, Ho, Wo, DEV))
 
 
 @pytest.mark.gpu
@@ -168,10 +149,7 @@ def test_dwconv3d_kernel_vs_f64(dc_ae, hip_lib, case):
     hip_lib.dwconv3d(x, w, b, out, k, glu)
     torch.cuda.synchronize()
     y = E.dwconv3d_ref(x, w, b, k, glu, dtype=torch.float64)
-    border = torch.zeros(T, H, W, dtype=torch.bool, device=DEV)
-    p = k // 2
-    border[:p], border[-p:], border[:, :p], border[:, -p:], border[:, :, :p], border[:, :, -p:] = (True,) * 6
-    _judge(name, out, y, border[None, :, :, :, None])
+    _judge(name, out, y, dw_border(T, H, W, k, DEV))
 
 
 @pytest.mark.gpu
@@ -218,6 +196,191 @@ def test_rmsnorm_affine_kernel_vs_f64(dc_ae, hip_lib, M, C, res, relu):
     hip_lib.rmsnorm_affine(x, w, b, out, 1e-5, r, relu)
     torch.cuda.synchronize()
     _judge(f"rmsnorm {M}x{C}", out, E.rmsnorm_affine_ref(x, w, b, 1e-5, r, relu, dtype=torch.float64))
+
+
+# ------------------------------------------------------------------------ shapes the ABI accepts and the decoder never launches
+# include/osk.h takes all of these; the bound is the one above.  Batch elements hold different data (one generator stream over
+# the whole tensor), so a wrong batch index cannot cancel.
+# (name, B, Cin, Cout, T, H, W (source), ksize, up_t, up_hw, res, bias, silu)
+CONV_CASES_MORE = [
+    # batch > 1 on the 8 x 16 brick path (Hu % 8 == 0, Wu % 16 == 0): frame = q / bh runs over b * Tu + to
+    ("b2_brick_64_64_res", 2, 64, 64, 3, 8, 16, 3, False, False, True, True, False),
+    ("b3_brick_128_64_up_thw_res", 3, 128, 64, 2, 4, 8, 3, True, True, True, True, False),
+    ("b2_brick_32_32_up_hw", 2, 32, 32, 3, 4, 8, 3, False, True, False, True, True),
+    ("b3_brick_64_128_up_t", 3, 64, 128, 1, 8, 16, 3, True, False, False, False, False),
+    # batch > 1 row-major, M % 128 != 0, a 128-voxel tile straddles the batch boundary (105 / 240 / 90 voxels per element)
+    ("b2_rows_64_64_res", 2, 64, 64, 3, 5, 7, 3, False, False, True, True, False),
+    ("b3_rows_128_64_up_thw_res", 3, 128, 64, 2, 3, 5, 3, True, True, True, True, False),
+    ("b3_rows_32_32_up_hw", 3, 32, 32, 2, 3, 5, 3, False, True, False, True, True),
+    ("b2_rows_32_32_up_t", 2, 32, 32, 3, 5, 3, 3, True, False, False, False, False),
+    ("b3_rows_k1_64_96", 3, 64, 96, 3, 5, 3, 1, False, False, False, True, True),
+    # Cin = 8 / 16: 8 / 4 taps share one 64-deep K step; at Cin = 8 the K padding reaches tap indices 27 .. 31
+    ("cin8_k3", 1, 8, 32, 3, 6, 7, 3, False, False, True, True, False),
+    ("cin16_k3", 2, 16, 40, 2, 5, 9, 3, False, True, False, True, True),
+    ("cin8_k1", 2, 8, 32, 2, 5, 7, 1, False, False, False, True, False),
+    ("cin16_k1", 1, 16, 24, 3, 4, 5, 1, False, False, True, False, True),
+    # Cout: the scalar epilogue away from 3, a second N tile with 2 live columns, vector-epilogue tail tiles
+    ("cout6", 1, 32, 6, 2, 9, 11, 3, False, False, True, True, True),
+    ("cout130", 1, 32, 130, 2, 6, 11, 3, False, False, True, True, False),
+    ("cout132", 2, 32, 132, 2, 5, 5, 3, False, True, True, True, False),
+    ("cout200", 1, 64, 200, 2, 8, 12, 3, False, False, False, True, True),
+    # a volume thinner than the kernel
+    ("thin_t1_h1", 1, 64, 64, 1, 1, 9, 3, False, False, True, True, False),
+    ("thin_h1", 2, 32, 32, 3, 1, 6, 3, False, False, False, True, False),
+    ("thin_w1", 1, 32, 32, 2, 7, 1, 3, False, False, False, True, True),
+    ("thin_1x1x1_up_hw", 1, 64, 32, 1, 1, 1, 3, False, True, True, True, False),
+]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", CONV_CASES_MORE, ids=[c[0] for c in CONV_CASES_MORE])
+def test_conv3d_zp_kernel_unlaunched_shapes_vs_f64(dc_ae, hip_lib, case):
+    name, B, Cin, Cout, T, H, W, k, up_t, up_hw, with_res, with_bias, silu = case
+    g = _gen(name)
+    conv = torch.nn.Conv3d(Cin, Cout, k, bias=with_bias).to(DEV)
+    with torch.no_grad():
+        conv.weight.copy_(torch.randn(conv.weight.shape, generator=g, device=DEV) / (Cin * k ** 3) ** 0.5)
+        if with_bias:
+            conv.bias.copy_(0.1 * torch.randn(Cout, generator=g, device=DEV))
+    plan = dc_ae._DensePlan(conv)
+    x = _randn((B, T, H, W, Cin), g)
+    To, Ho, Wo = T << int(up_t), H << int(up_hw), W << int(up_hw)
+    brick = Ho % 8 == 0 and Wo % 16 == 0
+    assert brick == ("brick" in name)
+    if "rows" in name:
+        assert (B * To * Ho * Wo) % 128 and (To * Ho * Wo) % 128
+    res = _randn((B, To, Ho, Wo, Cout), g) if with_res else None
+    guard = torch.full((B * To * Ho * Wo * Cout + 64,), float("nan"), dtype=BF, device=DEV)
+    out = guard[: B * To * Ho * Wo * Cout].view(B, To, Ho, Wo, Cout)
+    hip_lib.conv3d_zp(x, plan.w, plan.b, out, k, up_t, up_hw, silu, res)
+    torch.cuda.synchronize()
+    assert torch.isnan(guard[-64:].float()).all(), "wrote past the end of out"
+    y = E.conv3d_zp_ref(x, plan.w, plan.b, k, up_t, up_hw, silu, res, dtype=torch.float64)
+    _judge(name, out, y, conv_border(To, Ho, Wo, DEV) if k == 3 else None)
+    if B > 1:                                                # and each element against ITS OWN single-batch formula
+        for b in range(B):
+            yb = E.conv3d_zp_ref(x[b: b + 1], plan.w, plan.b, k, up_t, up_hw, silu, None if res is None else res[b: b + 1],
+                                 dtype=torch.float64)
+            _judge(f"{name}[b={b}]", out[b: b + 1], yb, conv_border(To, Ho, Wo, DEV) if k == 3 else None)
+
+
+# (name, B, C, T, H, W, ksize, glu, bias)
+DW_CASES_MORE = [
+    ("b2_glu_k3_256", 2, 256, 3, 5, 6, 3, True, True),
+    ("b2_agg_k5_96", 2, 96, 4, 5, 6, 5, False, False),
+    ("b3_plain_k3_64", 3, 64, 2, 3, 3, 3, False, True),
+    ("thin_k5_w1", 1, 64, 6, 7, 1, 5, False, False),         # extents below the radius (2) of the 5-tap kernel
+    ("thin_k5_t2_h1", 2, 96, 2, 1, 9, 5, False, False),
+    ("thin_glu_k3_h1", 2, 64, 4, 1, 5, 3, True, True),
+    ("thin_glu_k3_1x1x1", 2, 32, 1, 1, 1, 3, True, True),
+]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", DW_CASES_MORE, ids=[c[0] for c in DW_CASES_MORE])
+def test_dwconv3d_kernel_unlaunched_shapes_vs_f64(dc_ae, hip_lib, case):
+    name, B, C, T, H, W, k, glu, with_bias = case
+    g = _gen(name)
+    x = _randn((B, T, H, W, C), g)
+    w = _randn((k ** 3, C), g, k ** -1.5)
+    b = (0.1 * torch.randn(C, generator=g, device=DEV)) if with_bias else None
+    out = torch.full((B, T, H, W, C // 2 if glu else C), float("nan"), dtype=BF, device=DEV)
+    hip_lib.dwconv3d(x, w, b, out, k, glu)
+    torch.cuda.synchronize()
+    _judge(name, out, E.dwconv3d_ref(x, w, b, k, glu, dtype=torch.float64), dw_border(T, H, W, k, DEV))
+    for i in range(B if B > 1 else 0):
+        _judge(f"{name}[b={i}]", out[i: i + 1], E.dwconv3d_ref(x[i: i + 1], w, b, k, glu, dtype=torch.float64),
+               dw_border(T, H, W, k, DEV))
+
+
+def _attn_input(B, N, G, g):
+    qkv = _randn((B, N, G * 96), g)
+    v = qkv.view(B, N, G, 96)
+    v[:, ::3, :, 32:64] = -v[:, ::3, :, 32:64].abs()        # every third token: relu(k) == 0
+    v[:, :, 0, 32:64] = -v[:, :, 0, 32:64].abs()            # group 0: relu(k) == 0 for EVERY token -> 0 / (0 + eps) == 0
+    return qkv
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N", [63, 64, 65, 511, 512, 513, 32769])
+def test_relu_linear_attn_token_counts_at_the_tile_and_split_edges(dc_ae, hip_lib, N):
+    """each side of the 64-token LDS tile and of the 512-token split, and one token past the 64-split cap (64 * 512)"""
+    B, G = 2, 2
+    qkv = _attn_input(B, N, G, _gen(f"la_edges{N}"))
+    last = qkv.view(B, N, G, 96)[:, -1, 1, 32:64]
+    last.copy_(last.abs() + 4.0)                             # the LAST token carries weight in K^T V: dropping it must show
+    out = torch.full((B, N, G * 32), float("nan"), dtype=BF, device=DEV)
+    hip_lib.relu_linear_attn(qkv, out)
+    torch.cuda.synchronize()
+    assert float(out.view(B, N, G, 32)[:, :, 0].float().abs().max()) == 0.0
+    _judge(f"relu_linear_attn B{B} N{N} G{G}", out, E.relu_linear_attn_ref(qkv, dtype=torch.float64))
+
+
+@pytest.mark.gpu
+def test_relu_linear_attn_c_entry_point_nsplit_and_workspace(dc_ae, hip_lib):
+    """osk_relu_linear_attn_bf16 itself: nsplit 1 / 7 / 64 on one input (64 runs of 64 tokens over N = 1000 leave runs 16 .. 63
+    empty) agree with f64 within the bound; a workspace one byte short is refused (OSK_EINVAL = -1) and nothing is written"""
+    B, N, G = 2, 1000, 3
+    qkv = _attn_input(B, N, G, _gen("la_nsplit"))
+    y = E.relu_linear_attn_ref(qkv, dtype=torch.float64)
+    for nsplit in (1, 7, 64):
+        ws = torch.full((B * G * nsplit * 1056,), float("nan"), dtype=torch.float32, device=DEV)
+        out = torch.full((B, N, G * 32), float("nan"), dtype=BF, device=DEV)
+        rc = hip_lib.lib.osk_relu_linear_attn_bf16(qkv.data_ptr(), B, N, G, out.data_ptr(), out.stride(1), ws.data_ptr(),
+                                                   ws.numel() * 4, nsplit, 1e-15, hip_lib._stream())
+        assert rc == 0, (nsplit, rc)
+        torch.cuda.synchronize()
+        assert torch.isfinite(ws).all(), f"nsplit {nsplit}: a partial sum was never written"
+        _judge(f"relu_linear_attn nsplit {nsplit}", out, y)
+        out.fill_(float("nan"))
+        rc = hip_lib.lib.osk_relu_linear_attn_bf16(qkv.data_ptr(), B, N, G, out.data_ptr(), out.stride(1), ws.data_ptr(),
+                                                   ws.numel() * 4 - 1, nsplit, 1e-15, hip_lib._stream())
+        torch.cuda.synchronize()
+        assert rc == -1 and torch.isnan(out.float()).all(), (nsplit, rc)
+
+
+def _edge_rows(M, C, g, scale):
+    """row 0 all zeros (only eps is left under the rsqrt); row 1 with one element 2^15 among O(1) values; the rest normal"""
+    x = _randn((M, C), g, scale)
+    x[0] = 0
+    x[1, C // 3] = 2.0 ** 15
+    return x
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("M,C,res,relu", [(5, 128, False, False), (9, 1024, True, False), (4, 32, False, True)])
+def test_rmsnorm_affine_zero_row_and_outlier_row(dc_ae, hip_lib, M, C, res, relu):
+    g = _gen(f"rms_edge{M}x{C}")
+    x = _edge_rows(M, C, g, 1.0)
+    w = 1.0 + 0.1 * torch.randn(C, generator=g, device=DEV)
+    b = 0.1 * torch.randn(C, generator=g, device=DEV)
+    r = _randn((M, C), g) if res else None
+    out = torch.full((M, C), float("nan"), dtype=BF, device=DEV)
+    hip_lib.rmsnorm_affine(x, w, b, out, 1e-5, r, relu)
+    torch.cuda.synchronize()
+    y = E.rmsnorm_affine_ref(x, w, b, 1e-5, r, relu, dtype=torch.float64)
+    for row in range(3):                                    # each row against its own max |y|: row 1 must not set the floor
+        _judge(f"rmsnorm edge rows {M}x{C} row {row}", out[row], y[row])
+    _judge(f"rmsnorm edge rows {M}x{C}", out, y)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("M,C", [(3, 96), (40, 1536)])
+def test_gconv32_zero_row_and_outlier_row(dc_ae, hip_lib, M, C):
+    g = _gen(f"gconv_edge{M}x{C}")
+    x, w = _edge_rows(M, C, g, 1.0), _randn((C, 32), g, 32 ** -0.5)
+    out = torch.full((M, C), float("nan"), dtype=BF, device=DEV)
+    hip_lib.gconv32(x, w, out)
+    torch.cuda.synchronize()
+    y = E.gconv32_ref(x, w, dtype=torch.float64)
+    assert float(out[0].float().abs().max()) == 0.0
+    grp = (C // 3) // 32
+    for row in range(3):
+        _judge(f"gconv32 edge rows {M}x{C} row {row}", out[row], y[row])
+    others = torch.ones(C, dtype=torch.bool, device=DEV)
+    others[grp * 32: grp * 32 + 32] = False                  # row 1 outside the outlier's group: O(1) values, their own floor
+    _judge(f"gconv32 edge rows {M}x{C} row 1, other groups", out[1][others], y[1][others])
+    _judge(f"gconv32 edge rows {M}x{C}", out, y)
 
 
 # ------------------------------------------------------------------------------------------------------------ the decoder
