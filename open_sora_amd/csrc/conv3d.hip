@@ -7,66 +7,48 @@
 // Conv3d, hunyuan_vae/unet_causal_3d_blocks.py:82-96) and, in the decoder, materialises a nearest-neighbour
 // upsampled copy before the conv (:136-150).  Here neither copy exists: the replicate/causal padding is a CLAMP
 // of the gathered coordinate and the upsample is a SHIFT of it (frame 0 is spatial-only: tu -> tu == 0 ? 0 :
-// 1 + (tu-1)/2), both folded into the per-row source address of the A operand.  K runs tap-major / channel-minor
-// (k = tap * Cin + ci), so with channels-last activations every 16-byte chunk of the A tile is 8 contiguous
-// channels of ONE input voxel: coalesced 16 B global loads straight into LDS (global_load_lds_dwordx4), the same
-// lane-linear, source-swizzled LDS image as the dense GEMM (gemm_bf16.hip).  The weight is pre-laid as
-// [Cout][27 * Cin] (zero-padded to a multiple of 64) = the GEMM's W operand.
-//
-// Tile 128 (voxels) x 128 (Cout) x 64 (K), 4 waves (2 x 2) of 2 x 2 v_mfma_f32_32x32x16_bf16 tiles, operands
-// swapped so an accumulator lane owns one output voxel and 4 consecutive channels: the epilogue (bias, residual
-// add, bf16 pack) is lane-local and stores 8 B pieces of the NDHWC row.
+// 1 + (tu-1)/2), both folded into the per-row source address of the A operand.  That gather is this file's; the tile is
+// tile128.h's (128 voxels x 128 Cout x 64 K, its staging, LDS layout, K loop and epilogue), the voxels in row-major order.  The
+// weight is pre-laid as [Cout][27 * Cin] (zero-padded to a multiple of 64) = the tile's W operand.
 //
 // Roofline: MFMA bf16.  Algorithmic FLOPs = 2 * Cin * Cout * k^3 * B*To*Ho*Wo  (SURVEY.md §8(d)).
 #include "conv_params.h"
+#include "tile128.h"
 #include "../../include/osk.h"
 
 namespace {
 
-constexpr int BM = 128, BN = 128, BK = 64;
-constexpr int TILE_BYTES = 128 * BK * 2;
-constexpr int SMEM_BYTES = 2 * 2 * TILE_BYTES;
-
+using namespace osk_tile128;
 using osk_conv::ConvParams;
-
-OSK_DEV void glds16(const unsigned short* g, unsigned char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 
 OSK_DEV int sel3(int a0, int a1, int a2, int d) { return d == 0 ? a0 : (d == 1 ? a1 : a2); }
 
-// BIGC: Cin % 64 == 0 -> a K tile lies inside one tap (tap is wave-uniform, scalar decode)
+// A operand: the 8-channel chunk of (voxel of staging row i, tap), always inside the volume
+template <bool BIGC>
+struct CausalASrc {
+  const ConvParams& p;
+  int pT[4][3], pH[4][3], pW[4][3];  // per-axis voxel-index terms of the 3 taps (clamp + upsample folded in)
+  __device__ __forceinline__ const unsigned short* operator()(const Lane& g, int i, int kt) const {
+    TapChunk tc = tap_chunk<BIGC>(kt, g.cch[i], p.lg_cpt);
+    if constexpr (!BIGC) tc.tap = tc.tap < p.ntaps ? tc.tap : 0;  // K padding: weights are zero there, any address
+    const Tap3 d = tap3(tc.tap, p.ks);
+    const int pos = sel3(pT[i][0], pT[i][1], pT[i][2], d.dt) + sel3(pH[i][0], pH[i][1], pH[i][2], d.dh) +
+                    sel3(pW[i][0], pW[i][1], pW[i][2], d.dw);
+    return p.x + (((int64_t)pos << p.lg_cpt) + tc.cc) * 8;
+  }
+};
+
 template <bool BIGC>
 __global__ void __launch_bounds__(256, 2) conv3d_kernel(const ConvParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int hi = lane >> 5, l31 = lane & 31;
+  const Lane g = make_lane(p.M, p.Cout, p.w, p.wrs);
+  const int m0 = g.bm * BM;
 
-  const int nbm = (p.M + BM - 1) / BM, nbn = (p.Cout + BN - 1) / BN;
-  const int tile = xcd_remap(blockIdx.x, nbm * nbn);
-  const int bm = tile / nbn, bn = tile - bm * nbn;
-  const int m0 = bm * BM, n0 = bn * BN;
-
-  // ---- staging rows of this lane: 4 row-blocks of 8 rows per wave per operand (as gemm_bf16.hip)
-  const int srow8 = lane >> 3, spos = lane & 7;
-  const unsigned short* gw[4];
-  int lds_off[4], cch[4];
-  int pT[4][3], pH[4][3], pW[4][3];  // per-axis voxel-index terms of the 3 taps (clamp + upsample folded in)
+  CausalASrc<BIGC> a_src = {p};
   const int HW = p.H * p.W;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int rb = i * 4 + wave;
-    const int r = rb * 8 + srow8;
-    cch[i] = spos ^ ((r >> 1) & 7);  // source chunk that must land at LDS position spos
-    lds_off[i] = rb * 1024;
-    int n = n0 + r;
-    n = n < p.Cout ? n : p.Cout - 1;
-    gw[i] = p.w + (int64_t)n * p.wrs + cch[i] * 8;
-    int m = m0 + r;
+    int m = m0 + g.row[i];
     m = m < p.M ? m : p.M - 1;
     const int wo = m % p.Wo;
     int q = m / p.Wo;
@@ -86,135 +68,20 @@ __global__ void __launch_bounds__(256, 2) conv3d_kernel(const ConvParams p) {
       int wu = wo * p.sw + dd - (p.ks >> 1);
       wu = wu < 0 ? 0 : (wu > p.Wu - 1 ? p.Wu - 1 : wu);
       const int ws = p.up_hw ? (wu >> 1) : wu;
-      pT[i][d] = (b * p.T + ts) * HW;
-      pH[i][d] = hs * p.W;
-      pW[i][d] = ws;
+      a_src.pT[i][d] = (b * p.T + ts) * HW;
+      a_src.pH[i][d] = hs * p.W;
+      a_src.pW[i][d] = ws;
     }
   }
 
   f32x16_t acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  mainloop(g, smem, p.nk, a_src, acc);
 
-  const int cpt_mask = (1 << p.lg_cpt) - 1;
-  const int sw = (l31 >> 1) & 7;
-  const int a_row_off = (wm * 64 + l31) * 128;
-  const int w_row_off = (wn * 64 + l31) * 128;
-
-#define STAGE_ISSUE(BUFI, KT)                                                                     \
-  {                                                                                               \
-    unsigned char* ta_ = smem + (BUFI) * 2 * TILE_BYTES;                                          \
-    unsigned char* tw_ = ta_ + TILE_BYTES;                                                        \
-    int tap_u_ = 0, cc_u_ = 0, dt_u_ = 0, dh_u_ = 0, dw_u_ = 0;                                   \
-    if constexpr (BIGC) {                                                                         \
-      const int q_ = (KT) * 8;                                                                    \
-      tap_u_ = q_ >> p.lg_cpt;                                                                    \
-      cc_u_ = q_ & cpt_mask;                                                                      \
-      if (p.ks == 3) {                                                                            \
-        dt_u_ = tap_u_ / 9;                                                                       \
-        const int r_ = tap_u_ - dt_u_ * 9;                                                        \
-        dh_u_ = r_ / 3;                                                                           \
-        dw_u_ = r_ - dh_u_ * 3;                                                                   \
-      }                                                                                           \
-    }                                                                                             \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                               \
-      int dt_, dh_, dw_, cc_;                                                                     \
-      if constexpr (BIGC) {                                                                       \
-        dt_ = dt_u_; dh_ = dh_u_; dw_ = dw_u_; cc_ = cc_u_ + cch[i];                              \
-      } else {                                                                                    \
-        const int q_ = (KT) * 8 + cch[i];                                                         \
-        int tap_ = q_ >> p.lg_cpt;                                                                \
-        cc_ = q_ & cpt_mask;                                                                      \
-        tap_ = tap_ < p.ntaps ? tap_ : 0; /* K padding: weights are zero there, any address */    \
-        dt_ = 0; dh_ = 0; dw_ = 0;                                                                \
-        if (p.ks == 3) {                                                                          \
-          dt_ = tap_ / 9;                                                                         \
-          const int r_ = tap_ - dt_ * 9;                                                          \
-          dh_ = r_ / 3;                                                                           \
-          dw_ = r_ - dh_ * 3;                                                                     \
-        }                                                                                         \
-      }                                                                                           \
-      const int pos_ = sel3(pT[i][0], pT[i][1], pT[i][2], dt_) + sel3(pH[i][0], pH[i][1], pH[i][2], dh_) + \
-                       sel3(pW[i][0], pW[i][1], pW[i][2], dw_);                                   \
-      const unsigned short* ga_ = p.x + (((int64_t)pos_ << p.lg_cpt) + cc_) * 8;                  \
-      glds16(ga_, ta_ + lds_off[i]);                                                              \
-    }                                                                                             \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i) glds16(gw[i] + (KT) * BK, tw_ + lds_off[i]);    \
-  }
-
-  STAGE_ISSUE(0, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  int cur = 0;
-  for (int kt = 0; kt < p.nk; ++kt) {
-    const bool more = kt + 1 < p.nk;
-    if (more) STAGE_ISSUE(cur ^ 1, kt + 1);
-    const unsigned char* ta = smem + cur * 2 * TILE_BYTES;
-    const unsigned char* tw = ta + TILE_BYTES;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const int coff = (((ks << 1) | hi) ^ sw) << 4;
-      bf16x8_t af[2], wf[2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        af[t] = *reinterpret_cast<const bf16x8_t*>(ta + a_row_off + t * 32 * 128 + coff);
-        wf[t] = *reinterpret_cast<const bf16x8_t*>(tw + w_row_off + t * 32 * 128 + coff);
-      }
-#pragma unroll
-      for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-        for (int tm = 0; tm < 2; ++tm)
-          acc[tn][tm] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[tn], af[tm], acc[tn][tm], 0, 0, 0);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    cur ^= 1;
-  }
-#undef STAGE_ISSUE
-
-  // ---- epilogue: lane owns voxel m, channels n = quad*8 + hi*4 + {0..3}
-  const bool vec_ok = (p.Cout & 3) == 0;
 #pragma unroll
   for (int tm = 0; tm < 2; ++tm) {
-    const int m = m0 + wm * 64 + tm * 32 + l31;
+    const int m = m0 + acc_row(g, tm);
     if (m >= p.M) continue;
-    const int64_t roff = (int64_t)m * p.Cout;
-#pragma unroll
-    for (int tn = 0; tn < 2; ++tn) {
-#pragma unroll
-      for (int qd = 0; qd < 4; ++qd) {
-        const int n = n0 + wn * 64 + tn * 32 + qd * 8 + hi * 4;
-        if (n >= p.Cout) continue;
-        float v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = acc[tn][tm][qd * 4 + j];
-        if (vec_ok && n + 3 < p.Cout) {
-          if (p.bias) {
-            const float4 bv = *reinterpret_cast<const float4*>(p.bias + n);
-            v[0] += bv.x; v[1] += bv.y; v[2] += bv.z; v[3] += bv.w;
-          }
-          if (p.res) {
-            const uint2 rv = *reinterpret_cast<const uint2*>(p.res + roff + n);
-            v[0] += bf16_lo(rv.x); v[1] += bf16_hi(rv.x); v[2] += bf16_lo(rv.y); v[3] += bf16_hi(rv.y);
-          }
-          uint2 o;
-          o.x = pack_bf16x2(v[0], v[1]);
-          o.y = pack_bf16x2(v[2], v[3]);
-          *reinterpret_cast<uint2*>(p.out + roff + n) = o;
-        } else {
-          for (int j = 0; j < 4 && n + j < p.Cout; ++j) {
-            float t = v[j] + (p.bias ? p.bias[n + j] : 0.f);
-            if (p.res) t += bf16_bits_to_f32(p.res[roff + n + j]);
-            p.out[roff + n + j] = f32_to_bf16_bits(t);
-          }
-        }
-      }
-    }
+    conv_epilogue_row(g, acc, tm, (int64_t)m * p.Cout, p.Cout, p.bias, false, p.res, p.out);
   }
 }
 
@@ -353,15 +220,9 @@ static int conv_entry(const void* x, int B, int T, int H, int W, int Cin, const 
   const int64_t M = (int64_t)B * To * Ho * Wo;
   if (M >= (int64_t)1 << 31 || (int64_t)B * T * H * W >= (int64_t)1 << 31) return OSK_EUNSUPPORTED;
   p.M = (int)M;
-  int lg = 0;
-  while ((8 << lg) < Cin) ++lg;
-  p.lg_cpt = lg;
   p.ntaps = ksize * ksize * ksize;
-  const int64_t K = (int64_t)p.ntaps * Cin;
-  const int64_t Kp = (K + BK - 1) / BK * BK;
-  if (w_row_stride < Kp || (w_row_stride & 7)) return OSK_EINVAL;  // weight rows zero-padded to a multiple of 64
+  if (conv_k_layout(Cin, p.ntaps, w_row_stride, &p.lg_cpt, &p.nk) != OSK_OK) return OSK_EINVAL;
   p.wrs = w_row_stride;
-  p.nk = (int)(Kp / BK);
   hipStream_t s = (hipStream_t)stream;
   {
     // large-tile kernels with the hand-scheduled K loop (conv3d_256.hip) wherever the shape qualifies

@@ -9,23 +9,18 @@
 //   osk_relu_linear_attn_bf16    LiteMLA.relu_linear_att per (batch, 96-channel [q|k|v] group), f32 accumulation.
 //   osk_rmsnorm_affine_bf16      RMSNorm3d over channels with weight and bias, + ReLU, + identity-shortcut add.
 //
-// The convolution is conv2d.hip's tile with a third spatial axis: K runs tap-major / channel-minor (k = tap * Cin + ci), every
-// 16-byte chunk of the A tile is 8 contiguous channels of ONE input voxel, loaded straight into LDS (global_load_lds_dwordx4) in the
-// lane-linear, source-swizzled image of the dense GEMM; an out-of-volume tap is loaded from a 16-byte page of zeros, the upsample is
-// a shift of the gathered coordinate.  Tile 128 voxels x 128 Cout x 64 K, 4 waves (2 x 2) of 2 x 2 v_mfma_f32_32x32x16_bf16 tiles,
-// operands swapped so an accumulator lane owns one output voxel and 4 consecutive channels.  The 128 voxels of a tile are an
-// 8 x 16 brick of one frame where the output extent allows (H % 8 == 0, W % 16 == 0); other sizes walk the voxels row-major.
-// Cout = 3 (project_out) runs on the same tile with 3 live columns: one code path, at the price of a 128 -> 128 conv.
+// The convolution runs on tile128.h's tile (128 voxels x 128 Cout x 64 K, its staging, LDS layout, K loop, epilogue and 8 x 16 brick
+// order of one frame); what is this file's is the gather: an out-of-volume tap is loaded from a 16-byte page of zeros, the upsample
+// is a shift of the gathered coordinate.  Cout = 3 (project_out) runs on the same tile with 3 live columns: one code path, at the
+// price of a 128 -> 128 conv.
 //
 // Roofline: conv MFMA bf16 (2 * Cin * Cout * k^3 * voxels FLOPs); everything else HBM / L2 bound.
-#include "osk_common.h"
+#include "tile128.h"
 #include "../../include/osk.h"
 
 namespace {
 
-constexpr int BM = 128, BN = 128, BK = 64;
-constexpr int TILE_BYTES = 128 * BK * 2;
-constexpr int SMEM_BYTES = 2 * 2 * TILE_BYTES;
+using namespace osk_tile128;
 
 // the source of every out-of-volume (zero padding) or K-padding A-tile chunk
 __device__ __attribute__((aligned(16))) unsigned short conv3d_zero_page[8];
@@ -46,189 +41,53 @@ struct Conv3dParams {
   int64_t wrs;
 };
 
-OSK_DEV void glds16(const unsigned short* g, unsigned char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
+// A operand: the 8-channel chunk of (voxel of staging row i, tap), from the volume or from the zero page
+template <bool BIGC>
+struct Conv3dASrc {
+  const Conv3dParams& p;
+  int pB[4], pT[4], pH[4], pW[4];   // batch base frame, first tap coordinate in the upsampled volume (may be < 0: zero padding)
+  __device__ __forceinline__ const unsigned short* operator()(const Lane& g, int i, int kt) const {
+    const TapChunk tc = tap_chunk<BIGC>(kt, g.cch[i], p.lg_cpt);
+    const Tap3 d = tap3(tc.tap, p.ks);
+    const int tu = pT[i] + d.dt, hu = pH[i] + d.dh, wu = pW[i] + d.dw;
+    const bool in = tc.tap < p.ntaps && (unsigned)tu < (unsigned)p.Tu && (unsigned)hu < (unsigned)p.Hu && (unsigned)wu < (unsigned)p.Wu;
+    const int pos = ((pB[i] + (tu >> p.ut)) * p.H + (hu >> p.uh)) * p.W + (wu >> p.uh);
+    return in ? p.x + (((int64_t)pos << p.lg_cpt) + tc.cc) * 8 : conv3d_zero_page;
+  }
+};
 
-// output voxel index (row-major b, to, ho, wo) of tile row r of tile bm
-OSK_DEV int tile_voxel(const Conv3dParams& p, int bm, int r) {
-  if (!p.brick) return bm * BM + r;
-  const int bw = p.Wu >> 4, bh = p.Hu >> 3;
-  const int bx = bm % bw;
-  int q = bm / bw;
-  const int by = q % bh;
-  const int frame = q / bh;
-  return (frame * p.Hu + by * 8 + (r >> 4)) * p.Wu + bx * 16 + (r & 15);
-}
-
-// BIGC: Cin % 64 == 0 -> a K tile lies inside one tap (tap is wave-uniform)
 template <bool BIGC>
 __global__ void __launch_bounds__(256, 2) conv3d_zp_kernel(const Conv3dParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int hi = lane >> 5, l31 = lane & 31;
+  const Lane g = make_lane(p.M, p.Cout, p.w, p.wrs);
 
-  const int nbm = (p.M + BM - 1) / BM, nbn = (p.Cout + BN - 1) / BN;
-  const int tile = xcd_remap(blockIdx.x, nbm * nbn);
-  const int bm = tile / nbn, bn = tile - bm * nbn;
-  const int n0 = bn * BN;
-
-  // ---- staging rows of this lane: 4 row-blocks of 8 rows per wave per operand
-  const int srow8 = lane >> 3, spos = lane & 7;
-  const unsigned short* gw[4];
-  int lds_off[4], cch[4];
-  int pB[4], pT[4], pH[4], pW[4];   // batch base frame, first tap coordinate in the upsampled volume (may be < 0: zero padding)
+  Conv3dASrc<BIGC> a_src = {p};
   const int pad = p.ks >> 1;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int rb = i * 4 + wave;
-    const int r = rb * 8 + srow8;
-    cch[i] = spos ^ ((r >> 1) & 7);  // source chunk that must land at LDS position spos
-    lds_off[i] = rb * 1024;
-    int n = n0 + r;
-    n = n < p.Cout ? n : p.Cout - 1;
-    gw[i] = p.w + (int64_t)n * p.wrs + cch[i] * 8;
-    int m = bm * BM + r < p.M ? tile_voxel(p, bm, r) : p.M - 1;   // tail rows re-read the last voxel (never stored)
+    // tail rows re-read the last voxel (never stored)
+    const int m = g.bm * BM + g.row[i] < p.M ? tile_row_index(p.brick, g.bm, g.row[i], p.Hu, p.Wu) : p.M - 1;
     const int wo = m % p.Wu;
     int q = m / p.Wu;
     const int ho = q % p.Hu;
     q /= p.Hu;
     const int to = q % p.Tu;
     const int b = q / p.Tu;
-    pB[i] = b * p.T;
-    pT[i] = to - pad;
-    pH[i] = ho - pad;
-    pW[i] = wo - pad;
+    a_src.pB[i] = b * p.T;
+    a_src.pT[i] = to - pad;
+    a_src.pH[i] = ho - pad;
+    a_src.pW[i] = wo - pad;
   }
 
   f32x16_t acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  mainloop(g, smem, p.nk, a_src, acc);
 
-  const int cpt_mask = (1 << p.lg_cpt) - 1;
-  const int sw = (l31 >> 1) & 7;
-  const int a_row_off = (wm * 64 + l31) * 128;
-  const int w_row_off = (wn * 64 + l31) * 128;
-
-#define STAGE_ISSUE(BUFI, KT)                                                                     \
-  {                                                                                               \
-    unsigned char* ta_ = smem + (BUFI) * 2 * TILE_BYTES;                                          \
-    unsigned char* tw_ = ta_ + TILE_BYTES;                                                        \
-    int tap_u_ = 0, cc_u_ = 0;                                                                    \
-    if constexpr (BIGC) {                                                                         \
-      const int q_ = (KT) * 8;                                                                    \
-      tap_u_ = q_ >> p.lg_cpt;                                                                    \
-      cc_u_ = q_ & cpt_mask;                                                                      \
-    }                                                                                             \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                               \
-      int tap_, cc_;                                                                              \
-      if constexpr (BIGC) {                                                                       \
-        tap_ = tap_u_; cc_ = cc_u_ + cch[i];                                                      \
-      } else {                                                                                    \
-        const int q_ = (KT) * 8 + cch[i];                                                         \
-        tap_ = q_ >> p.lg_cpt;                                                                    \
-        cc_ = q_ & cpt_mask;                                                                      \
-      }                                                                                           \
-      int dt_ = 0, dh_ = 0, dw_ = 0;                                                              \
-      if (p.ks == 3) {                                                                            \
-        dt_ = tap_ / 9;                                                                           \
-        const int r9_ = tap_ - dt_ * 9;                                                           \
-        dh_ = r9_ / 3;                                                                            \
-        dw_ = r9_ - dh_ * 3;                                                                      \
-      }                                                                                           \
-      const int tu_ = pT[i] + dt_, hu_ = pH[i] + dh_, wu_ = pW[i] + dw_;                          \
-      const bool in_ = tap_ < p.ntaps && (unsigned)tu_ < (unsigned)p.Tu &&                        \
-                       (unsigned)hu_ < (unsigned)p.Hu && (unsigned)wu_ < (unsigned)p.Wu;          \
-      const int pos_ = ((pB[i] + (tu_ >> p.ut)) * p.H + (hu_ >> p.uh)) * p.W + (wu_ >> p.uh);     \
-      const unsigned short* ga_ = in_ ? p.x + (((int64_t)pos_ << p.lg_cpt) + cc_) * 8 : conv3d_zero_page; \
-      glds16(ga_, ta_ + lds_off[i]);                                                              \
-    }                                                                                             \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i) glds16(gw[i] + (KT) * BK, tw_ + lds_off[i]);    \
-  }
-
-  STAGE_ISSUE(0, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  int cur = 0;
-  for (int kt = 0; kt < p.nk; ++kt) {
-    const bool more = kt + 1 < p.nk;
-    if (more) STAGE_ISSUE(cur ^ 1, kt + 1);
-    const unsigned char* ta = smem + cur * 2 * TILE_BYTES;
-    const unsigned char* tw = ta + TILE_BYTES;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const int coff = (((ks << 1) | hi) ^ sw) << 4;
-      bf16x8_t af[2], wf[2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        af[t] = *reinterpret_cast<const bf16x8_t*>(ta + a_row_off + t * 32 * 128 + coff);
-        wf[t] = *reinterpret_cast<const bf16x8_t*>(tw + w_row_off + t * 32 * 128 + coff);
-      }
-#pragma unroll
-      for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-        for (int tm = 0; tm < 2; ++tm)
-          acc[tn][tm] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[tn], af[tm], acc[tn][tm], 0, 0, 0);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    cur ^= 1;
-  }
-#undef STAGE_ISSUE
-
-  // ---- epilogue: lane owns voxel m, channels n = quad*8 + hi*4 + {0..3}
-  const bool vec_ok = (p.Cout & 3) == 0;
 #pragma unroll
   for (int tm = 0; tm < 2; ++tm) {
-    const int r = wm * 64 + tm * 32 + l31;
-    if (bm * BM + r >= p.M) continue;
-    const int m = tile_voxel(p, bm, r);
-    const int64_t roff = (int64_t)m * p.Cout;
-#pragma unroll
-    for (int tn = 0; tn < 2; ++tn) {
-#pragma unroll
-      for (int qd = 0; qd < 4; ++qd) {
-        const int n = n0 + wn * 64 + tn * 32 + qd * 8 + hi * 4;
-        if (n >= p.Cout) continue;
-        float v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = acc[tn][tm][qd * 4 + j];
-        if (vec_ok && n + 3 < p.Cout) {
-          if (p.bias) {
-            const float4 bv = *reinterpret_cast<const float4*>(p.bias + n);
-            v[0] += bv.x; v[1] += bv.y; v[2] += bv.z; v[3] += bv.w;
-          }
-          if (p.act) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = silu(v[j]);
-          }
-          if (p.res) {
-            const uint2 rv = *reinterpret_cast<const uint2*>(p.res + roff + n);
-            v[0] += bf16_lo(rv.x); v[1] += bf16_hi(rv.x); v[2] += bf16_lo(rv.y); v[3] += bf16_hi(rv.y);
-          }
-          uint2 o;
-          o.x = pack_bf16x2(v[0], v[1]);
-          o.y = pack_bf16x2(v[2], v[3]);
-          *reinterpret_cast<uint2*>(p.out + roff + n) = o;
-        } else {
-          for (int j = 0; j < 4 && n + j < p.Cout; ++j) {
-            float t = v[j] + (p.bias ? p.bias[n + j] : 0.f);
-            if (p.act) t = silu(t);
-            if (p.res) t += bf16_bits_to_f32(p.res[roff + n + j]);
-            p.out[roff + n + j] = f32_to_bf16_bits(t);
-          }
-        }
-      }
-    }
+    const int r = acc_row(g, tm);
+    if (g.bm * BM + r >= p.M) continue;
+    const int64_t roff = (int64_t)tile_row_index(p.brick, g.bm, r, p.Hu, p.Wu) * p.Cout;
+    conv_epilogue_row(g, acc, tm, roff, p.Cout, p.bias, p.act, p.res, p.out);
   }
 }
 
@@ -526,15 +385,9 @@ extern "C" int osk_conv3d_zp_ndhwc_bf16(const void* x, int B, int T, int H, int 
   p.Tu = (int)Tu; p.Hu = (int)Hu; p.Wu = (int)Wu;
   p.M = (int)M;
   p.brick = (Hu % 8 == 0 && Wu % 16 == 0) ? 1 : 0;
-  int lg = 0;
-  while ((8 << lg) < Cin) ++lg;
-  p.lg_cpt = lg;
   p.ntaps = ksize * ksize * ksize;
-  const int64_t K = (int64_t)p.ntaps * Cin;
-  const int64_t Kp = (K + BK - 1) / BK * BK;
-  if (w_row_stride < Kp || (w_row_stride & 7)) return OSK_EINVAL;  // weight rows zero-padded to a multiple of 64
+  if (conv_k_layout(Cin, p.ntaps, w_row_stride, &p.lg_cpt, &p.nk) != OSK_OK) return OSK_EINVAL;
   p.wrs = w_row_stride;
-  p.nk = (int)(Kp / BK);
   const int64_t nblk = ((M + BM - 1) / BM) * ((Cout + BN - 1) / BN);
   if (nblk >= MAX_BLOCKS) return OSK_EUNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;

@@ -1,126 +1,48 @@
 // bf16 GEMM with fused epilogues for gfx950:  C = epi(A[M,K] @ W[N,K]^T + bias)
 //
-// Tile 128(M) x 128(N) x 64(K), 256 threads = 4 waves (2 x 2), each wave 64 x 64 = 2 x 2 MFMA
-// v_mfma_f32_32x32x16_bf16 tiles.  Operands are SWAPPED in the MFMA (A-operand = W fragment, B-operand
-// = activation fragment) so that a lane of the accumulator owns one output ROW m and 4 consecutive
-// columns n per register quad: the epilogue (bias / GELU / gate*x+residual) is lane-local in m and
-// stores 8 B (4 bf16) contiguous pieces.
-//
-// Staging: HBM -> LDS with global_load_lds_dwordx4 (16 B per lane, LDS image lane-linear), double
-// buffered, one barrier per K tile.  The 128-B LDS rows are XOR-swizzled on the SOURCE side
-// (chunk' = chunk ^ ((row >> 1) & 7)) and un-swizzled on the ds_read_b128 side: conflict-free for the
-// 32-row x 16-B fragment reads of the 32x32x16 MFMA (see DESIGN.md "LDS layouts").
+// The 128(M) x 128(N) x 64(K) tile of tile128.h (staging, LDS layout, K loop) with both operands dense: the A chunks of a lane are
+// one row of A, 64 elements further every K tile.  The epilogue (bias / GELU / gate*x+residual, bf16 or f32 out) is lane-local in
+// the output row m and stores 4 consecutive columns at a time.
 //
 // Roofline: MFMA bf16 (2.5 PFLOP/s dense).  Algorithmic FLOPs = 2*M*N*K.
 #include <atomic>
 #include "gemm_params.h"
+#include "tile128.h"
 #include "../../include/osk.h"
 
 namespace {
 
-constexpr int BM = 128, BN = 128, BK = 64;
-constexpr int TILE_BYTES = 128 * BK * 2;  // 16 KiB per operand tile
-constexpr int SMEM_BYTES = 2 * 2 * TILE_BYTES;
-
+using namespace osk_tile128;
 using osk_gemm::GemmParams;
 
-OSK_DEV void glds16(const unsigned short* g, unsigned char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
+// A operand: row pointers at K tile 0
+struct GemmASrc {
+  const unsigned short* ga[4];
+  __device__ __forceinline__ const unsigned short* operator()(const Lane&, int i, int kt) const { return ga[i] + kt * BK; }
+};
 
 template <bool OUT_F32>
 __global__ void __launch_bounds__(256, 2) gemm_bf16_kernel(const GemmParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int hi = lane >> 5, l31 = lane & 31;
+  const Lane g = make_lane(p.M, p.N, p.W, p.wrs);
+  const int m0 = g.bm * BM;
 
-  const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-  const int tile = xcd_remap(blockIdx.x, nbm * nbn);
-  const int bm = tile / nbn, bn = tile - bm * nbn;
-  const int m0 = bm * BM, n0 = bn * BN;
-
-  // ---- staging addresses: 4 row-blocks of 8 rows per wave per operand
-  const unsigned short* ga[4];
-  const unsigned short* gw[4];
-  int lds_off[4];  // byte offset of this wave's 1-KiB row block inside a tile (wave-uniform)
-  const int srow8 = lane >> 3, spos = lane & 7;
+  GemmASrc a_src;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int rb = i * 4 + wave;
-    const int r = rb * 8 + srow8;
-    const int c = spos ^ ((r >> 1) & 7);  // source chunk that must land at LDS position spos
-    int m = m0 + r;
+    int m = m0 + g.row[i];
     m = m < p.M ? m : p.M - 1;
     const int b = m / p.arpb, l = m - b * p.arpb;
-    ga[i] = p.A + b * p.abs_ + (int64_t)l * p.ars + c * 8;
-    int n = n0 + r;
-    n = n < p.N ? n : p.N - 1;
-    gw[i] = p.W + (int64_t)n * p.wrs + c * 8;
-    lds_off[i] = rb * 1024;
+    a_src.ga[i] = p.A + b * p.abs_ + (int64_t)l * p.ars + g.cch[i] * 8;
   }
 
   f32x16_t acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  const int nk = p.K / BK;
-  const int sw = (l31 >> 1) & 7;
-  // fragment read offsets (bytes) inside a tile for ks = 0; other ks: chunk = (ks*2+hi) ^ sw
-  const int a_row_off = (wm * 64 + l31) * 128;
-  const int w_row_off = (wn * 64 + l31) * 128;
-
-  // (macros rather than lambdas: by-reference captured arrays were placed in scratch by hipcc)
-#define STAGE_ISSUE(BUFI, KT)                                                                  \
-  {                                                                                            \
-    const int k0_ = (KT) * BK;                                                                 \
-    unsigned char* ta_ = smem + (BUFI) * 2 * TILE_BYTES;                                       \
-    unsigned char* tw_ = ta_ + TILE_BYTES;                                                     \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i) glds16(ga[i] + k0_, ta_ + lds_off[i]);       \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i) glds16(gw[i] + k0_, tw_ + lds_off[i]);       \
-  }
-
-  STAGE_ISSUE(0, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  int cur = 0;
-  for (int kt = 0; kt < nk; ++kt) {
-    const bool more = kt + 1 < nk;
-    if (more) STAGE_ISSUE(cur ^ 1, kt + 1);
-    const unsigned char* ta = smem + cur * 2 * TILE_BYTES;
-    const unsigned char* tw = ta + TILE_BYTES;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const int coff = (((ks << 1) | hi) ^ sw) << 4;
-      bf16x8_t af[2], wf[2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        af[t] = *reinterpret_cast<const bf16x8_t*>(ta + a_row_off + t * 32 * 128 + coff);
-        wf[t] = *reinterpret_cast<const bf16x8_t*>(tw + w_row_off + t * 32 * 128 + coff);
-      }
-#pragma unroll
-      for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-        for (int tm = 0; tm < 2; ++tm)
-          acc[tn][tm] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[tn], af[tm], acc[tn][tm], 0, 0, 0);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    cur ^= 1;
-  }
+  mainloop(g, smem, p.K / BK, a_src, acc);
 
   // ---- epilogue: lane owns row m = ... + l31, columns n = quad*8 + hi*4 + {0..3}
 #pragma unroll
   for (int tm = 0; tm < 2; ++tm) {
-    const int m = m0 + wm * 64 + tm * 32 + l31;
+    const int m = m0 + acc_row(g, tm);
     if (m >= p.M) continue;
     const int b = m / p.crpb, l = m - b * p.crpb;
     const int64_t roff = b * p.cbs + (int64_t)l * p.crs;
@@ -129,7 +51,7 @@ __global__ void __launch_bounds__(256, 2) gemm_bf16_kernel(const GemmParams p) {
     for (int tn = 0; tn < 2; ++tn) {
 #pragma unroll
       for (int qd = 0; qd < 4; ++qd) {
-        const int n = n0 + wn * 64 + tn * 32 + qd * 8 + hi * 4;
+        const int n = acc_col(g, tn, qd);
         if (n >= p.N) continue;
         float v[4];
 #pragma unroll
