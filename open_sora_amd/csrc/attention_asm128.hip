@@ -18,11 +18,6 @@ namespace {
 constexpr int HD = 128, NKS = OSK128_NKS, NDT = OSK128_NDT, NU = 2, NW = 4, NSLOT = OSK128N2_NSLOT;
 static_assert(NKS == 9 && NDT == 5 && NSLOT == 4, "generated geometry changed: update the wrapper");
 
-OSK_DEV unsigned rfl(unsigned v) { return __builtin_amdgcn_readfirstlane(v); }
-OSK_DEV uint64_t rfl64(uint64_t v) {
-  return ((uint64_t)rfl((unsigned)(v >> 32)) << 32) | rfl((unsigned)v);
-}
-
 template <bool FAST>   // FAST: a score bound was given (attention_params.h::attn_fast_path); any key count, any segment layout
 __global__ void __launch_bounds__(256, 1) attn_asm128_kernel(const AttnParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];

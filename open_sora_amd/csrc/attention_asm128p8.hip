@@ -27,11 +27,6 @@ constexpr int HD = 128, NKS = OSK128P8_NKS, NDT = OSK128P8_NDT, NU = 2, NW = 4, 
 constexpr int NSLOT_V = OSK128P8N2_NSLOT_V, RP = OSK128P8_RP, NVD = OSK128P8_NVD;
 static_assert(NKS == 9 && NDT == 5 && NSLOT == 4 && NSLOT_V == 3 && RP == 144 && NVD == 9, "generated geometry changed: update the wrapper");
 
-OSK_DEV unsigned rfl(unsigned v) { return __builtin_amdgcn_readfirstlane(v); }
-OSK_DEV uint64_t rfl64(uint64_t v) {
-  return ((uint64_t)rfl((unsigned)(v >> 32)) << 32) | rfl((unsigned)v);
-}
-
 __global__ void __launch_bounds__(256, 1) attn_asm128p8_kernel(const AttnParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;

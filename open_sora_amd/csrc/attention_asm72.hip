@@ -26,11 +26,6 @@ namespace {
 
 constexpr int HDL = 72, NKS = 5, NDT = 3;   // HDL: the head_dim of the LDS images / register layout; the tensors' head_dim is the template parameter HD (72, or 64: see below)
 
-OSK_DEV unsigned rfl(unsigned v) { return __builtin_amdgcn_readfirstlane(v); }
-OSK_DEV uint64_t rfl64(uint64_t v) {
-  return ((uint64_t)rfl((unsigned)(v >> 32)) << 32) | rfl((unsigned)v);
-}
-
 // HD = 64 (round 4: the S-width models; the compiler-scheduled attn_fwd_kernel<64> is gone): the SAME loop on tensors with 64-wide heads --
 // Q's dims 64..71 are zero, K's 8-dim column image is never fetched (its LDS chunk stays zero: the loader slot that fetches it does not
 // exist), V^T has 64 rows (LDS rows 64..71 stay zero), the ones row stays LDS row 72.  80 padded dims for 64 real ones: issued / useful 1.25.

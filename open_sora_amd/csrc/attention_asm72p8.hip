@@ -13,11 +13,6 @@ constexpr int HD = 72, NKS = 5, NDT = 3;
 constexpr int NSLOT_V = OSK72P8N2_NSLOT_V, RP = OSK72P8_RP, NVD = OSK72P8_NVD;
 static_assert(NSLOT_V == 2 && RP == 80 && NVD == 5, "generated geometry changed: update the wrapper");
 
-OSK_DEV unsigned rfl(unsigned v) { return __builtin_amdgcn_readfirstlane(v); }
-OSK_DEV uint64_t rfl64(uint64_t v) {
-  return ((uint64_t)rfl((unsigned)(v >> 32)) << 32) | rfl((unsigned)v);
-}
-
 template <int NU>
 __global__ void __launch_bounds__(NU == 2 ? 256 : 512, NU == 2 ? 1 : 2) attn_asm72p8_kernel(const AttnParams p) {
   constexpr int NW = 8 / NU;                                   // waves per workgroup

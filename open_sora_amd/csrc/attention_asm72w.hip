@@ -18,11 +18,6 @@ namespace {
 
 constexpr int HDL = 72, NKS = 5, NDT = 3;   // HDL: the head_dim of the LDS images / register layout; the tensors' head_dim is the template parameter HD (72, or 64: see below)
 
-OSK_DEV unsigned rfl(unsigned v) { return __builtin_amdgcn_readfirstlane(v); }
-OSK_DEV uint64_t rfl64(uint64_t v) {
-  return ((uint64_t)rfl((unsigned)(v >> 32)) << 32) | rfl((unsigned)v);
-}
-
 template <int HD>   // 72, or 64 (see attention_asm72.hip)
 __global__ void __launch_bounds__(256, 1) attn_asm72w_kernel(const AttnParams p) {
   constexpr bool FAST = true;

@@ -13,15 +13,13 @@
 // Roofline: MFMA bf16.  Algorithmic FLOPs = 2 * Cin * Cout * k^3 * B*To*Ho*Wo.
 #include "acc_quads.h"
 #include "conv_params.h"
+#include "tile256.h"
 #include "gemm256x_regs.inc"
 #include "convsw_regs.inc"
 #include <type_traits>
 
 namespace osk_conv {
 namespace {
-
-OSK_DEV unsigned rfl(unsigned v) { return __builtin_amdgcn_readfirstlane(v); }
-OSK_DEV uint64_t rfl64(uint64_t v) { return ((uint64_t)rfl((unsigned)(v >> 32)) << 32) | rfl((unsigned)v); }
 
 #ifdef OSK_CONV_TILE_TIMING   // tools/make_conv_timing_lib.sh: where a sliding-window tile's time goes (s_memtime sums of wave 0 of every workgroup)
 __device__ unsigned long long osk_conv_tile_ticks[4];   // address set-up, asm statement (prologue + K loop), epilogue, tiles
@@ -325,9 +323,8 @@ __global__ void __launch_bounds__(256, 1) conv256x_kernel(const ConvParams p) {
 
   // ---- LDS-DMA side: exactly conv256w_kernel's (same LDS image)
   const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
-  const int srow8 = lane >> 3, spos = lane & 7;
-  const int r0 = wave * 8 + srow8;
-  const int c = spos ^ ((r0 >> 1) & 7);
+  const int r0 = osk_tile256::dma_row<4>(wave, lane, 0);
+  const int c = osk_tile256::dma_chunk(lane, r0);
   const unsigned chk = (unsigned)(c * 16);
   const unsigned arow0 = lds_base + TABLE + r0 * 4;
   unsigned woff[8];                        // NBJ LDS-DMA pieces per wave cover the BN weight rows (slots beyond NBJ: unused copies)
@@ -602,20 +599,13 @@ __global__ void __launch_bounds__(256, 1) convsw2_kernel(const ConvParams p) {
   }   // tile loop
 }
 
-// one workgroup per CU (a multiple of 8, so that the XCD remap of the tile list keeps a workgroup inside one XCD's range)
-int persistent_grid(int ntiles) {
-  int n_cu = osk_device_cus();
-  n_cu -= n_cu % 8;
-  if (n_cu < 8) n_cu = 8;
-  return ntiles > n_cu ? n_cu : ntiles;
-}
 
 template <int NBJ>
 int launch_x(const ConvParams& p, hipStream_t st) {
   constexpr int BN = 32 * NBJ, SMEM = (NBJ == 8 ? OSKX_SMEM : OSKX128_SMEM) + 27 * 1024;
   OSK_ENSURE_MAX_SMEM(conv256x_kernel<NBJ>, SMEM);
   const int nblk = ((p.M + 255) / 256) * ((p.Cout + BN - 1) / BN);
-  hipLaunchKernelGGL(conv256x_kernel<NBJ>, dim3(persistent_grid(nblk)), dim3(256), SMEM, st, p);
+  hipLaunchKernelGGL(conv256x_kernel<NBJ>, dim3(osk_tile256::persistent_grid(nblk)), dim3(256), SMEM, st, p);
   return (int)hipGetLastError();
 }
 
@@ -627,7 +617,7 @@ int launch_sw(const ConvParams& p0, hipStream_t st) {
   p.brick = 1;
   OSK_ENSURE_MAX_SMEM((convsw_kernel<NBJ, UP, GN>), SMEM);
   const int nblk = (p.M / 256) * ((p.Cout + BN - 1) / BN);
-  hipLaunchKernelGGL((convsw_kernel<NBJ, UP, GN>), dim3(persistent_grid(nblk)), dim3(256), SMEM, st, p);
+  hipLaunchKernelGGL((convsw_kernel<NBJ, UP, GN>), dim3(osk_tile256::persistent_grid(nblk)), dim3(256), SMEM, st, p);
   return (int)hipGetLastError();
 }
 
@@ -637,7 +627,7 @@ int launch_sw2(const ConvParams& p0, hipStream_t st) {
   p.brick = 2;
   OSK_ENSURE_MAX_SMEM(convsw2_kernel<GN>, OSKSWF128_SMEM);
   const int nblk = p.B * ((p.To + 1) / 2) * (p.Ho / 16) * (p.Wo / 16);
-  hipLaunchKernelGGL(convsw2_kernel<GN>, dim3(persistent_grid(nblk)), dim3(256), OSKSWF128_SMEM, st, p);
+  hipLaunchKernelGGL(convsw2_kernel<GN>, dim3(osk_tile256::persistent_grid(nblk)), dim3(256), OSKSWF128_SMEM, st, p);
   return (int)hipGetLastError();
 }
 

@@ -16,7 +16,7 @@
 //
 // Roofline: MFMA bf16 (fp8 instantiation: MFMA fp8).  Algorithmic FLOPs = 2*M*N*K.
 #include "acc_quads.h"
-#include "gemm_params.h"
+#include "tile256.h"
 #include "gemm256_regs_n256.inc"
 #include "gemm256_regs_n128.inc"
 #include "gemm256_fp8_regs_n256.inc"
@@ -24,9 +24,6 @@
 
 namespace osk_gemm {
 namespace {
-
-OSK_DEV unsigned rfl(unsigned v) { return __builtin_amdgcn_readfirstlane(v); }
-OSK_DEV uint64_t rfl64(uint64_t v) { return ((uint64_t)rfl((unsigned)(v >> 32)) << 32) | rfl((unsigned)v); }
 
 // tile T's 16 accumulators = quads 4 T .. 4 T + 3 of aq (acc_quads.h: compiler-visible values, outputs of an empty asm statement
 // behind the K loop): read in place and in program order
@@ -173,31 +170,18 @@ __global__ void __launch_bounds__(512, 2) gemm256_kernel(const GemmParams p) {
   const int hi = lane >> 5, l31 = lane & 31;
 
   const int nbm = (p.M + 255) / 256, nbn = (p.N + BN - 1) / BN;
-  // tile order: every XCD (private 4 MiB L2) owns a contiguous range of the list below; inside it the tiles run in
-  // groups of GRP row bands, N-major within a group: the ~32 tiles resident on an XCD cover GRP bands x a few weight
-  // tiles, so a weight tile is streamed once per GRP bands instead of once per ~2 (OSK_GEMM_GROUP, default 8)
-  const int tile = xcd_remap(blockIdx.x, nbm * nbn);
-  const int grp = p.group > 0 ? p.group : 1;
-  const int per_group = grp * nbn;
-  const int g = tile / per_group, r = tile - g * per_group;
-  const int rows_here = nbm - g * grp < grp ? nbm - g * grp : grp;   // last group may be short
-  const int bn = r / rows_here, bm = g * grp + (r - bn * rows_here);
-  const int m0 = bm * 256, n0 = bn * BN;
+  // the grouped tile order (tile256.h), one tile per workgroup
+  const osk_tile256::TileBlock t = osk_tile256::grouped_tile(xcd_remap(blockIdx.x, nbm * nbn), nbm, nbn, p.group > 0 ? p.group : 1);
+  const int m0 = t.bm * 256, n0 = t.bn * BN;
 
-  // ---- LDS-DMA sources: instruction j = wave + 8 i covers tile rows [8 j, 8 j + 8); byte offsets from the tensor base
-  const int srow8 = lane >> 3, spos = lane & 7;
+  // ---- LDS-DMA sources (tile256.h): 8 waves; byte offsets from the tensor base
   unsigned aoff[4], woff[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int r = (wave + 8 * i) * 8 + srow8;
-    const int c = spos ^ ((r >> 1) & 7);
-    int m = m0 + r;
-    m = m < p.M ? m : p.M - 1;
-    const int b = m / p.arpb, l = m - b * p.arpb;
-    aoff[i] = (unsigned)((b * p.abs_ + (int64_t)l * p.ars) * ES + c * 16);
-    int n = n0 + (r < BN ? r : 0);
-    n = n < p.N ? n : p.N - 1;
-    woff[i] = (unsigned)((int64_t)n * p.wrs * ES + c * 16);
+    const int r = osk_tile256::dma_row<8>(wave, lane, i);
+    const int c = osk_tile256::dma_chunk(lane, r);
+    aoff[i] = (unsigned)(osk_tile256::a_row_offset(p, m0 + r) * ES + c * 16);
+    woff[i] = (unsigned)(osk_tile256::w_row_offset(p, n0 + (r < BN ? r : 0)) * ES + c * 16);
   }
   const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
   const int sw = (l31 >> 1) & 7;

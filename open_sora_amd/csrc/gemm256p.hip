@@ -1,7 +1,7 @@
 // Persistent-workgroup form of the large-tile bf16 GEMM (gemm256.hip):  C = epi(A[M,K] @ W[N,K]^T + bias)
 //
 // One 512-thread workgroup per CU walks a list of 256 x BN output tiles (tile i, i + grid, i + 2 grid, ... of the
-// XCD-aware grouped order of gemm256.hip).  Same tile, LDS image, LDS-DMA loaders, fragment layout and K-step schedule;
+// XCD-aware grouped order of tile256.h).  Same tile, LDS image, LDS-DMA loaders, fragment layout and K-step schedule;
 // what changes is everything AROUND the K loop -- measured in round 1 at ~11 us per round of tiles against 1.7 us per
 // K step, i.e. 27 % of a K = 1152 GEMM (every CU issuing its 64 KiB prologue fetch and its 128 KiB store burst at the
 // same moment, with the matrix pipe idle):
@@ -17,15 +17,13 @@
 //
 // Roofline: MFMA bf16.  Algorithmic FLOPs = 2*M*N*K.
 #include "gemm_epilogue.h"
+#include "tile256.h"
 #include "gemm256_regs_n256.inc"
 #include "gemm256_regs_n128.inc"
 #include "gemm256p_regs_n128.inc"
 
 namespace osk_gemm {
 namespace {
-
-OSK_DEV unsigned rfl(unsigned v) { return __builtin_amdgcn_readfirstlane(v); }
-OSK_DEV uint64_t rfl64(uint64_t v) { return ((uint64_t)rfl((unsigned)(v >> 32)) << 32) | rfl((unsigned)v); }
 
 // tile T's 16 accumulators = quads 4 T .. 4 T + 3 of aq (acc_quads.h): read in place and in program order
 template <int T>
@@ -61,32 +59,21 @@ __global__ void __launch_bounds__(512, 2) gemm256p_kernel(const GemmParams p) {
   const int nbm = (p.M + 255) / 256, nbn = (p.N + BN - 1) / BN;
   const int ntiles = nbm * nbn;
   const int grp = p.group > 0 ? p.group : 1;
-  const int per_group = grp * nbn;
-  // tile order of gemm256.hip: every XCD owns a contiguous range of the list; inside it groups of `grp` row bands,
-  // N-major within a group.  Iteration i of this workgroup is list position blockIdx.x + i * gridDim.x (gridDim.x is a
+  // the grouped tile order (tile256.h).  Iteration i of this workgroup is list position blockIdx.x + i * gridDim.x (gridDim.x is a
   // multiple of 8 whenever a workgroup has more than one tile, so a workgroup stays inside its XCD's range).
   auto tile_of = [&](int it, int& m0, int& n0) {
-    const int tile = xcd_remap(it, ntiles);
-    const int g = tile / per_group, r = tile - g * per_group;
-    const int rows_here = nbm - g * grp < grp ? nbm - g * grp : grp;
-    const int bn = r / rows_here, bm = g * grp + (r - bn * rows_here);
-    m0 = bm * 256;
-    n0 = bn * BN;
+    const osk_tile256::TileBlock t = osk_tile256::grouped_tile(xcd_remap(it, ntiles), nbm, nbn, grp);
+    m0 = t.bm * 256;
+    n0 = t.bn * BN;
   };
-  // LDS-DMA sources: instruction j = wave + 8 i covers tile rows [8 j, 8 j + 8); byte offsets from the tensor bases
-  const int srow8 = lane >> 3, spos = lane & 7;
+  // LDS-DMA sources (tile256.h): 8 waves; byte offsets from the tensor bases
   auto offsets = [&](int m0, int n0, unsigned* aoff, unsigned* woff) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const int r = (wave + 8 * i) * 8 + srow8;
-      const int c = spos ^ ((r >> 1) & 7);
-      int m = m0 + r;
-      m = m < p.M ? m : p.M - 1;
-      const int b = m / p.arpb, l = m - b * p.arpb;
-      aoff[i] = (unsigned)((b * p.abs_ + (int64_t)l * p.ars) * 2 + c * 16);
-      int n = n0 + (r < BN ? r : 0);
-      n = n < p.N ? n : p.N - 1;
-      woff[i] = (unsigned)((int64_t)n * p.wrs * 2 + c * 16);
+      const int r = osk_tile256::dma_row<8>(wave, lane, i);
+      const int c = osk_tile256::dma_chunk(lane, r);
+      aoff[i] = (unsigned)(osk_tile256::a_row_offset(p, m0 + r) * 2 + c * 16);
+      woff[i] = (unsigned)(osk_tile256::w_row_offset(p, n0 + (r < BN ? r : 0)) * 2 + c * 16);
     }
   };
   const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
@@ -142,12 +129,8 @@ int launch_one(const GemmParams& p, hipStream_t st) {
   constexpr int SMEM = BN == 256 ? OSKG256_SMEM : OSKG128_SMEM;
   auto kernel = gemm256p_kernel<BN, OUT_F32, SCHED>;
   OSK_ENSURE_MAX_SMEM(kernel, SMEM);
-  int n_cu = osk_device_cus();
-  n_cu -= n_cu % 8;    // the tile walk keeps a workgroup inside one XCD's range only for a grid that is a multiple of 8
-  if (n_cu < 8) n_cu = 8;
   const int ntiles = ((p.M + 255) / 256) * ((p.N + BN - 1) / BN);
-  const int grid = ntiles < n_cu ? ntiles : n_cu;   // one workgroup per CU (LDS: 96 KiB of 160)
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), SMEM, st, p);
+  hipLaunchKernelGGL(kernel, dim3(osk_tile256::persistent_grid(ntiles)), dim3(512), SMEM, st, p);   // (LDS: 96 KiB of 160)
   return (int)hipGetLastError();
 }
 

@@ -1,7 +1,7 @@
 // The 4-wave persistent bf16 GEMM (round 2's gemm256w.hip, removed in round 3) on v_mfma_f32_16x16x32_bf16:  C = epi(A[M,K] @ W[N,K]^T + bias)
 //
-// Same 256 x 256 x 64 workgroup tile, LDS image, LDS-DMA loaders, tile walk, cross-tile prefetch and bias-initialised
-// accumulators; the wave tile 128 x 128 is 8 x 8 accumulator tiles of 16 x 16 (4 AGPRs each) and a K step is two sub-steps of
+// Same 256 x 256 x 64 workgroup tile, LDS image, LDS-DMA loaders, cross-tile prefetch and bias-initialised accumulators (tile order,
+// grid and loader rows: tile256.h); the wave tile 128 x 128 is 8 x 8 accumulator tiles of 16 x 16 (4 AGPRs each) and a K step is two sub-steps of
 // K = 32.  Why a second MFMA shape (profiles/r02_gemm_experiments.md, "what the K loop's time is made of"): every kernel of
 // this library runs at the board's 1.4 kW cap, so time ~ energy per flop; with that kernel's loop otherwise unchanged, issuing the
 // same flops as 16x16x32 MFMAs (4 accumulator registers written per 16 matrix cycles instead of 16 per 32) measured +5-7 %.
@@ -13,13 +13,11 @@
 // Roofline: MFMA bf16.  Algorithmic FLOPs = 2*M*N*K.
 #include "acc_quads.h"
 #include "gemm_epilogue16.h"
+#include "tile256.h"
 #include "gemm256x_regs.inc"
 
 namespace osk_gemm {
 namespace {
-
-OSK_DEV unsigned rfl(unsigned v) { return __builtin_amdgcn_readfirstlane(v); }
-OSK_DEV uint64_t rfl64(uint64_t v) { return ((uint64_t)rfl((unsigned)(v >> 32)) << 32) | rfl((unsigned)v); }
 
 // The wave's 256 accumulators as 64 quads (tile T = J * NB + I is quad T): made compiler-visible values by an empty asm
 // statement behind the K-loop statement (acc_quads.h) -- the epilogue reads aq[T][i], the compiler emits the v_accvgpr_read.
@@ -48,209 +46,109 @@ __device__ unsigned long long osk_gemm_tile_ticks[4];   // address set-up, asm s
 #define OSK_TT(i, t0)
 #endif
 
-template <bool OUT_F32, int NP>
-__global__ void __launch_bounds__(256, 1) gemm256x_kernel(const GemmPack<NP> pk) {
-  constexpr int WT = OSKX_NB * 16, BN = 256;   // wave tile side
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int q4 = lane >> 4, l15 = lane & 15;
+// ---- what differs between the Linear kernel and the V^T kernel, as seen by the tile walk below: static functions of the pack / of
+// the tile's own GemmParams (nothing is stored: there is nothing for hipcc to place in scratch)
 
-  const int nbn = (pk.p[0].N - pk.p[0].skip_len + BN - 1) / BN;     // N, K, group, skip range are the pack's (equal in every problem)
-  const int nt0 = ((pk.p[0].M + 255) / 256) * nbn;
-  const int ntiles = NP == 1 ? nt0 : nt0 + ((pk.p[NP - 1].M + 255) / 256) * nbn;
-  const int grp = pk.p[0].group > 0 ? pk.p[0].group : 1;
-  const int per_group = grp * nbn;
-  // position in the tile list -> (problem, tile origin): tile order of gemm256.hip / gemm256p.hip inside each problem
-  auto tile_of = [&](int it, int& sel, int& m0, int& n0) {
-    int tile = xcd_remap(it, ntiles);
-    sel = (NP > 1 && tile >= nt0) ? 1 : 0;
-    tile -= sel ? nt0 : 0;
-    const int nbm = (pk.p[sel].M + 255) / 256;
-    const int g = tile / per_group, r = tile - g * per_group;
-    const int rows_here = nbm - g * grp < grp ? nbm - g * grp : grp;
-    const int bn = r / rows_here, bm = g * grp + (r - bn * rows_here);
-    m0 = bm * 256;
-    n0 = bn * BN;
-    n0 += n0 >= pk.p[0].skip_from ? pk.p[0].skip_len : 0;      // PHYSICAL column origin (round 6: a skipped column range, gemm_params.h)
-  };
-  // LDS-DMA sources: instruction j = wave + 4 i (i = 0..7) covers tile rows [8 j, 8 j + 8); byte offsets from the bases
-  const int srow8 = lane >> 3, spos = lane & 7;
-  auto offsets = [&](const GemmParams& p, int m0, int n0, unsigned* aoff, unsigned* woff) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int r = (wave + 4 * i) * 8 + srow8;
-      const int c = spos ^ ((r >> 1) & 7);
-      int m = m0 + r;
-      m = m < p.M ? m : p.M - 1;
-      const int b = m / p.arpb, l = m - b * p.arpb;
-      aoff[i] = (unsigned)((b * p.abs_ + (int64_t)l * p.ars) * 2 + c * 16);
-      int n = n0 + r;
-      n = n < p.N ? n : p.N - 1;
-      woff[i] = (unsigned)((int64_t)n * p.wrs * 2 + c * 16);
-    }
-  };
+// Linear: A = the activations (batched rows), W = the weight (plain rows).  N, K, group and the skip range are the PACK's (equal in
+// every problem: read from problem 0); M and the epilogue class are the problem's.
+template <bool OUT_F32>
+struct LinearWalk {
+  template <int NP>
+  OSK_DEV int col_tiles(const GemmPack<NP>& pk, int) { return (pk.p[0].N - pk.p[0].skip_len + 255) / 256; }
+  // logical column origin -> PHYSICAL column origin (round 6: a skipped column range, gemm_params.h)
+  template <int NP>
+  OSK_DEV int phys_n0(const GemmPack<NP>& pk, int n0) { return n0 + (n0 >= pk.p[0].skip_from ? pk.p[0].skip_len : 0); }
+  OSK_DEV int64_t a_row(const GemmParams& p, int m) { return osk_tile256::a_row_offset(p, m); }
+  OSK_DEV int64_t w_row(const GemmParams& p, int n, bool) { return osk_tile256::w_row_offset(p, n); }
   // a tile whose 256 A rows lie inside M and inside one batch, and whose 256 W rows lie inside N: its per-lane source
   // offsets are an affine function of (m0, n0), so the next tile's are this tile's plus a wave-uniform delta
-  auto affine = [&](const GemmParams& p, int m0, int n0) {
+  OSK_DEV bool affine(const GemmParams& p, int m0, int n0) {
     return m0 + 256 <= p.M && n0 + 256 <= p.N && m0 / p.arpb == (m0 + 255) / p.arpb;
-  };
-  auto a_origin = [&](const GemmParams& p, int m0) -> int64_t {
+  }
+  OSK_DEV int64_t a_origin(const GemmParams& p, int m0) {
     const int b = m0 / p.arpb, l = m0 - b * p.arpb;
     return (b * p.abs_ + (int64_t)l * p.ars) * 2;
-  };
-  const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
-  // fragment row l15 of a 16-row block, 16-byte chunk q4 (k 8 q4 .. + 7 of the sub-step's 32) under the row's swizzle key
-  const unsigned sz0 = (unsigned)((q4 ^ ((l15 >> 1) & 7)) << 4);
-  const unsigned faA0 = lds_base + (wm * WT + l15) * 128 + sz0;
-  const unsigned faW0 = lds_base + OSKX_W_BASE + (wn * WT + l15) * 128 + sz0;
-  const unsigned nk = rfl((unsigned)(pk.p[0].K / 64));
-  const unsigned adst = rfl(lds_base + wave * 1024), wdst = rfl(lds_base + OSKX_W_BASE + wave * 1024);
-
-  unsigned prefetched = 0;
-  for (int it = blockIdx.x; it < ntiles; it += (int)gridDim.x) {
-    const int itn = it + (int)gridDim.x;
-#ifdef OSK_GEMM_TILE_TIMING
-    const unsigned long long tt0 = __builtin_amdgcn_s_memtime();
-#endif
-    int sel, m0, n0, seln = 0, m0n = 0, n0n = 0;
-    tile_of(it, sel, m0, n0);
-    const GemmParams& p = pk.p[NP == 1 ? 0 : sel];                 // wave-uniform: kernel-argument loads at a scalar offset
-    bool has_next = itn < ntiles;
-    unsigned dA = 0, dW = 0;
-    if (has_next) {
-      tile_of(itn, seln, m0n, n0n);
-      // cross-tile prefetch only between two affine tiles of the SAME problem (the deltas are relative to its bases; edge
-      // tiles and the first tile of the second problem start with their own cold fetch)
-      has_next = seln == sel && affine(p, m0, n0) && affine(p, m0n, n0n);
-      dA = (unsigned)(a_origin(p, m0n) - a_origin(p, m0));
-      dW = (unsigned)(((int64_t)n0n - n0) * p.wrs * 2);
-    }
-    const uint64_t abase = rfl64((uint64_t)(uintptr_t)p.A), wbase = rfl64((uint64_t)(uintptr_t)p.W);
-    const uint64_t bbase = rfl64((uint64_t)(uintptr_t)p.bias);
-    unsigned aoff[8], woff[8];
-    offsets(p, m0, n0, aoff, woff);
-    const int m0w = m0 + wm * WT, n0w = n0 + wn * WT;
-    const bool folded = p.bias != nullptr && n0w + WT <= p.N;                 // wave-uniform
-    const unsigned boff = (unsigned)((n0w + q4 * 4) * 4);
-    const unsigned flags = rfl(prefetched | (has_next ? 2u : 0u) | (folded ? 4u : 0u));
-    const unsigned dAs = rfl(dA), dWs = rfl(dW);
-
-    // prefetch lanes: lane l of wave w touches row 64 w + l of the A tile and of the W tile (one dword per 128-byte line)
-    unsigned aoffp, woffp;
-    {
-      int m = m0 + wave * 64 + lane;
-      m = m < p.M ? m : p.M - 1;
-      const int b = m / p.arpb, l = m - b * p.arpb;
-      aoffp = (unsigned)((b * p.abs_ + (int64_t)l * p.ars) * 2);
-      int n = n0 + wave * 64 + lane;
-      n = n < p.N ? n : p.N - 1;
-      woffp = (unsigned)((int64_t)n * p.wrs * 2);
-    }
-#define OSKW_OPERANDS                                                                                               \
-  ::"v"(faA0), "v"(faW0), "v"(aoff[0]), "v"(aoff[1]), "v"(aoff[2]), "v"(aoff[3]), "v"(aoff[4]), "v"(aoff[5]),          \
-      "v"(aoff[6]), "v"(aoff[7]), "v"(woff[0]), "v"(woff[1]), "v"(woff[2]), "v"(woff[3]), "v"(woff[4]), "v"(woff[5]),  \
-      "v"(woff[6]), "v"(woff[7]), "v"(boff), "s"(abase), "s"(wbase), "s"(bbase), "s"(nk), "s"(adst), "s"(wdst),        \
-      "s"(flags), "s"(dAs), "s"(dWs), "v"(aoffp), "v"(woffp)
-    OSK_TT(0, tt0);
-#ifdef OSK_GEMM_TILE_TIMING
-    const unsigned long long tt1 = __builtin_amdgcn_s_memtime();
-#endif
-    asm volatile(
-#include "gemm256x_body.inc"
-        OSKW_OPERANDS : OSKX_CLOBBERS);
-    static_assert(OSKX_ACC_QUADS == 64, "the generated loop's accumulator map: quad T = tile T, a0 .. a255");
-    osk_v4f aq[64];
-    asm volatile("" : OSK_AQ_OUT_0_64(aq));
-    OSK_TT(1, tt1);
-#ifdef OSK_GEMM_TILE_TIMING
-    const unsigned long long tt2 = __builtin_amdgcn_s_memtime();
-#endif
-
+  }
+  OSK_DEV int64_t w_origin(const GemmParams& p, int n0) { return (int64_t)n0 * p.wrs * 2; }
+  OSK_DEV bool folded(const GemmParams& p, int n0w) { return p.bias != nullptr && n0w + OSKX_NB * 16 <= p.N; }   // wave-uniform
+  OSK_DEV void epilogue(const osk_v4f* aq, const GemmParams& p, int m0w, int n0w, int l15, int q4, bool folded) {
+    constexpr int WT = OSKX_NB * 16;
     const int b_first = m0w / p.crpb, b_last = (m0w + WT - 1) / p.crpb;
     const bool interior = m0w + WT <= p.M && n0w + WT <= p.N && b_first == b_last;  // wave-uniform
     epi16::epilogue_all<GeoX, OUT_F32>(aq, p, m0w, n0w, l15, q4, interior, folded);
-    OSK_TT(2, tt2);
-#ifdef OSK_GEMM_TILE_TIMING
-    if (threadIdx.x == 0) atomicAdd(&osk_gemm_tile_ticks[3], 1ull);
-#endif
-    prefetched = has_next ? 1u : 0u;
   }
-}
+};
 
-#undef OSKW_OPERANDS
-
-// ---- the same tile loop for the V^T tasks of osk_gemm_group_bf16 (round 6): one or two problems (img + txt stream of a double
-// block) whose A operand is the V weight and whose W operand are the activations -- V^T = W_v X^T written directly in the attention
-// kernels' key-major operand layout (gemm_params.h: vt, wrpb, wvalid, ccbs, rowbias; epilogue class vt_all).  A separate kernel so
-// that the Linear launches above keep their register allocation (one wave per SIMD, 256 accumulators + ~250 VGPRs: a handful more
-// live values spill to scratch -- measured in this round: +3 k cycles of set-up per tile) and because this one carries ONE epilogue
-// class instead of nine.
-template <int NP>
-__global__ void __launch_bounds__(256, 1) gemm256x_vt_kernel(const GemmPack<NP> pk) {
-  static_assert(NP <= 2, "a run-time index into a wider pack makes hipcc copy the pack to scratch");
-  constexpr int WT = OSKX_NB * 16, BN = 256;   // wave tile side
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int q4 = lane >> 4, l15 = lane & 15;
-
-  // the two problems differ in N (positions on the key axis) and may differ in M
-  const int nbn0 = (pk.p[0].N + BN - 1) / BN, nbn1 = (pk.p[NP - 1].N + BN - 1) / BN;
-  const int nt0 = ((pk.p[0].M + 255) / 256) * nbn0;
-  const int ntiles = NP == 1 ? nt0 : nt0 + ((pk.p[NP - 1].M + 255) / 256) * nbn1;
-  const int grp = pk.p[0].group > 0 ? pk.p[0].group : 1;
-  // position in the tile list -> (problem, tile origin): tile order of gemm256.hip / gemm256p.hip inside each problem
-  auto tile_of = [&](int it, int& sel, int& m0, int& n0) {
-    int tile = xcd_remap(it, ntiles);
-    sel = (NP > 1 && tile >= nt0) ? 1 : 0;
-    tile -= sel ? nt0 : 0;
-    const int nbm = (pk.p[sel].M + 255) / 256;
-    const int per_group = grp * (sel ? nbn1 : nbn0);
-    const int g = tile / per_group, r = tile - g * per_group;
-    const int rows_here = nbm - g * grp < grp ? nbm - g * grp : grp;
-    const int bn = r / rows_here, bm = g * grp + (r - bn * rows_here);
-    m0 = bm * 256;
-    n0 = bn * BN;
-  };
-  // LDS-DMA sources: instruction j = wave + 4 i (i = 0..7) covers tile rows [8 j, 8 j + 8); byte offsets from the bases
-  const int srow8 = lane >> 3, spos = lane & 7;
-  // A = the V weight (one "batch"); W = the activations: column n of the product = (batch n / wrpb, position n % wrpb) of the key axis,
-  // fed from the activation row key = vt_perm64(position) (osk_v_transpose_bf16's order inside every 64-key group); keys behind the
-  // sequence end read the last key (finite values) and are stored as zero by the epilogue
-  auto w_src = [&](const GemmParams& p, int n, bool permute) -> int64_t {
+// V^T task (gemm_params.h: vt, wrpb, wvalid, ccbs, rowbias): A = the V weight (one "batch"); W = the activations: column n of the
+// product = (batch n / wrpb, position n % wrpb) of the key axis, fed from the activation row key = vt_perm64(position)
+// (osk_v_transpose_bf16's order inside every 64-key group); keys behind the sequence end read the last key (finite values) and are
+// stored as zero by the epilogue.  The problems of a pack differ in N (positions on the key axis) and may differ in M.
+struct VtWalk {
+  template <int NP>
+  OSK_DEV int col_tiles(const GemmPack<NP>& pk, int i) { return (pk.p[i].N + 255) / 256; }
+  template <int NP>
+  OSK_DEV int phys_n0(const GemmPack<NP>&, int n0) { return n0; }
+  OSK_DEV int64_t a_row(const GemmParams& p, int m) {
+    m = m < p.M ? m : p.M - 1;
+    return (int64_t)m * p.ars;
+  }
+  // permute = false: the prefetch lanes touch one dword per line of the tile's rows -- the order inside a 64-key group does not matter
+  OSK_DEV int64_t w_row(const GemmParams& p, int n, bool permute) {
     n = n < p.N ? n : p.N - 1;
     const int wb = n / p.wrpb;
     int pos = n - wb * p.wrpb;
     if (permute) pos = vt_perm64(pos, p.vt);
     pos = pos < p.wvalid ? pos : p.wvalid - 1;
     return wb * p.wbs + (int64_t)pos * p.wrs;
-  };
-  auto offsets = [&](const GemmParams& p, int m0, int n0, unsigned* aoff, unsigned* woff) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int r = (wave + 4 * i) * 8 + srow8;
-      const int c = spos ^ ((r >> 1) & 7);
-      int m = m0 + r;
-      m = m < p.M ? m : p.M - 1;
-      aoff[i] = (unsigned)((int64_t)m * p.ars * 2 + c * 16);
-      woff[i] = (unsigned)(w_src(p, n0 + r, true) * 2 + c * 16);
-    }
-  };
+  }
   // a tile whose 256 weight rows lie inside M and whose 256 positions lie inside one batch with every key valid (the key order stays
   // inside 64-key groups): its per-lane source offsets are an affine function of (m0, n0)
-  auto affine = [&](const GemmParams& p, int m0, int n0) {
+  OSK_DEV bool affine(const GemmParams& p, int m0, int n0) {
     const int wb = n0 / p.wrpb, pos0 = n0 - wb * p.wrpb;
     return m0 + 256 <= p.M && n0 + 256 <= p.N && pos0 + 256 <= p.wrpb && pos0 + 256 <= p.wvalid;
-  };
-  auto a_origin = [&](const GemmParams& p, int m0) -> int64_t { return (int64_t)m0 * p.ars * 2; };
-  auto w_origin = [&](const GemmParams& p, int n0) -> int64_t {
+  }
+  OSK_DEV int64_t a_origin(const GemmParams& p, int m0) { return (int64_t)m0 * p.ars * 2; }
+  OSK_DEV int64_t w_origin(const GemmParams& p, int n0) {
     const int wb = n0 / p.wrpb, pos0 = n0 - wb * p.wrpb;
     return (wb * p.wbs + (int64_t)pos0 * p.wrs) * 2;
+  }
+  OSK_DEV bool folded(const GemmParams&, int) { return false; }   // (the per-ROW bias b_v is added by the epilogue)
+  OSK_DEV void epilogue(const osk_v4f* aq, const GemmParams& p, int m0w, int n0w, int l15, int q4, bool) {
+    epi16::vt_all<GeoX>(aq, p, m0w, n0w, l15, q4);
+  }
+};
+
+#define OSKW_OPERANDS                                                                                               \
+  ::"v"(faA0), "v"(faW0), "v"(aoff[0]), "v"(aoff[1]), "v"(aoff[2]), "v"(aoff[3]), "v"(aoff[4]), "v"(aoff[5]),          \
+      "v"(aoff[6]), "v"(aoff[7]), "v"(woff[0]), "v"(woff[1]), "v"(woff[2]), "v"(woff[3]), "v"(woff[4]), "v"(woff[5]),  \
+      "v"(woff[6]), "v"(woff[7]), "v"(boff), "s"(abase), "s"(wbase), "s"(bbase), "s"(nk), "s"(adst), "s"(wdst),        \
+      "s"(flags), "s"(dAs), "s"(dWs), "v"(aoffp), "v"(woffp)
+
+// The persistent loop of both kernels: this workgroup's tiles it = blockIdx.x, + gridDim.x, ... of the pack's tile list (each problem's
+// tiles in the grouped order of tile256.h), each one the generated K loop -- which also fetches the first K steps of the NEXT tile where
+// that tile's source offsets are this tile's plus a wave-uniform delta -- and the walk's epilogue.
+template <class Walk, int NP>
+OSK_DEV void tile_walk(const GemmPack<NP>& pk) {
+  constexpr int WT = OSKX_NB * 16;   // wave tile side
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  const int q4 = lane >> 4, l15 = lane & 15;
+
+  const int nbn0 = Walk::col_tiles(pk, 0), nbn1 = Walk::col_tiles(pk, NP - 1);
+  const int nt0 = ((pk.p[0].M + 255) / 256) * nbn0;
+  const int ntiles = NP == 1 ? nt0 : nt0 + ((pk.p[NP - 1].M + 255) / 256) * nbn1;
+  const int grp = pk.p[0].group > 0 ? pk.p[0].group : 1;
+  // position in the tile list -> (problem, tile origin)
+  auto tile_of = [&](int it, int& sel, int& m0, int& n0) {
+    int tile = xcd_remap(it, ntiles);
+    sel = (NP > 1 && tile >= nt0) ? 1 : 0;
+    tile -= sel ? nt0 : 0;
+    const osk_tile256::TileBlock t = osk_tile256::grouped_tile(tile, (pk.p[sel].M + 255) / 256, sel ? nbn1 : nbn0, grp);
+    m0 = t.bm * 256;
+    n0 = Walk::phys_n0(pk, t.bn * 256);
   };
   const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
   // fragment row l15 of a 16-row block, 16-byte chunk q4 (k 8 q4 .. + 7 of the sub-step's 32) under the row's swizzle key
@@ -275,33 +173,29 @@ __global__ void __launch_bounds__(256, 1) gemm256x_vt_kernel(const GemmPack<NP> 
       tile_of(itn, seln, m0n, n0n);
       // cross-tile prefetch only between two affine tiles of the SAME problem (the deltas are relative to its bases; edge
       // tiles and the first tile of the second problem start with their own cold fetch)
-      has_next = seln == sel && affine(p, m0, n0) && affine(p, m0n, n0n);
-      dA = (unsigned)(a_origin(p, m0n) - a_origin(p, m0));
-      dW = (unsigned)(w_origin(p, n0n) - w_origin(p, n0));
+      has_next = seln == sel && Walk::affine(p, m0, n0) && Walk::affine(p, m0n, n0n);
+      dA = (unsigned)(Walk::a_origin(p, m0n) - Walk::a_origin(p, m0));
+      dW = (unsigned)(Walk::w_origin(p, n0n) - Walk::w_origin(p, n0));
     }
     const uint64_t abase = rfl64((uint64_t)(uintptr_t)p.A), wbase = rfl64((uint64_t)(uintptr_t)p.W);
     const uint64_t bbase = rfl64((uint64_t)(uintptr_t)p.bias);
+    // LDS-DMA sources (tile256.h): 4 waves; byte offsets from the bases
     unsigned aoff[8], woff[8];
-    offsets(p, m0, n0, aoff, woff);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int r = osk_tile256::dma_row<4>(wave, lane, i);
+      const int c = osk_tile256::dma_chunk(lane, r);
+      aoff[i] = (unsigned)(Walk::a_row(p, m0 + r) * 2 + c * 16);
+      woff[i] = (unsigned)(Walk::w_row(p, n0 + r, true) * 2 + c * 16);
+    }
     const int m0w = m0 + wm * WT, n0w = n0 + wn * WT;
-    const bool folded = false;                                                // (the per-ROW bias b_v is added by the epilogue)
+    const bool folded = Walk::folded(p, n0w);
     const unsigned boff = (unsigned)((n0w + q4 * 4) * 4);
     const unsigned flags = rfl(prefetched | (has_next ? 2u : 0u) | (folded ? 4u : 0u));
     const unsigned dAs = rfl(dA), dWs = rfl(dW);
-
     // prefetch lanes: lane l of wave w touches row 64 w + l of the A tile and of the W tile (one dword per 128-byte line)
-    unsigned aoffp, woffp;
-    {
-      int m = m0 + wave * 64 + lane;
-      m = m < p.M ? m : p.M - 1;
-      aoffp = (unsigned)((int64_t)m * p.ars * 2);
-      woffp = (unsigned)(w_src(p, n0 + wave * 64 + lane, false) * 2);   // (one dword per line of the tile's rows: the order inside a group does not matter)
-    }
-#define OSKW_OPERANDS                                                                                               \
-  ::"v"(faA0), "v"(faW0), "v"(aoff[0]), "v"(aoff[1]), "v"(aoff[2]), "v"(aoff[3]), "v"(aoff[4]), "v"(aoff[5]),          \
-      "v"(aoff[6]), "v"(aoff[7]), "v"(woff[0]), "v"(woff[1]), "v"(woff[2]), "v"(woff[3]), "v"(woff[4]), "v"(woff[5]),  \
-      "v"(woff[6]), "v"(woff[7]), "v"(boff), "s"(abase), "s"(wbase), "s"(bbase), "s"(nk), "s"(adst), "s"(wdst),        \
-      "s"(flags), "s"(dAs), "s"(dWs), "v"(aoffp), "v"(woffp)
+    const unsigned aoffp = (unsigned)(Walk::a_row(p, m0 + wave * 64 + lane) * 2);
+    const unsigned woffp = (unsigned)(Walk::w_row(p, n0 + wave * 64 + lane, false) * 2);
     OSK_TT(0, tt0);
 #ifdef OSK_GEMM_TILE_TIMING
     const unsigned long long tt1 = __builtin_amdgcn_s_memtime();
@@ -316,8 +210,7 @@ __global__ void __launch_bounds__(256, 1) gemm256x_vt_kernel(const GemmPack<NP> 
 #ifdef OSK_GEMM_TILE_TIMING
     const unsigned long long tt2 = __builtin_amdgcn_s_memtime();
 #endif
-
-    epi16::vt_all<GeoX>(aq, p, m0w, n0w, l15, q4);
+    Walk::epilogue(aq, p, m0w, n0w, l15, q4, folded);
     OSK_TT(2, tt2);
 #ifdef OSK_GEMM_TILE_TIMING
     if (threadIdx.x == 0) atomicAdd(&osk_gemm_tile_ticks[3], 1ull);
@@ -328,12 +221,24 @@ __global__ void __launch_bounds__(256, 1) gemm256x_vt_kernel(const GemmPack<NP> 
 
 #undef OSKW_OPERANDS
 
-int grid_for(int ntiles) {
-  int n_cu = osk_device_cus();
-  n_cu -= n_cu % 8;    // the tile walk keeps a workgroup inside one XCD's range only for a grid that is a multiple of 8
-  if (n_cu < 8) n_cu = 8;
-  return ntiles < n_cu ? ntiles : n_cu;   // one workgroup per CU (LDS: 128 KiB of 160)
+template <bool OUT_F32, int NP>
+__global__ void __launch_bounds__(256, 1) gemm256x_kernel(const GemmPack<NP> pk) {
+  tile_walk<LinearWalk<OUT_F32>>(pk);
 }
+
+// ---- the same tile walk for the V^T tasks of osk_gemm_group_bf16 (round 6): one or two problems (img + txt stream of a double block)
+// whose product is written directly in the attention kernels' key-major operand layout (epilogue class vt_all).  A separate kernel so
+// that the Linear launches above keep their register allocation (one wave per SIMD, 256 accumulators + ~250 VGPRs: a handful more
+// live values spill to scratch -- measured in this round: +3 k cycles of set-up per tile) and because this one carries ONE epilogue
+// class instead of nine.
+template <int NP>
+__global__ void __launch_bounds__(256, 1) gemm256x_vt_kernel(const GemmPack<NP> pk) {
+  static_assert(NP <= 2, "a run-time index into a wider pack makes hipcc copy the pack to scratch");
+  tile_walk<VtWalk>(pk);
+}
+
+// tiles of one problem (an empty slot of a pack, M = 0: none)
+int tiles_of(const GemmParams& p) { return ((p.M + 255) / 256) * ((p.N - p.skip_len + 255) / 256); }
 
 template <bool OUT_F32>
 int launch_one(const GemmParams& p, hipStream_t st) {
@@ -341,8 +246,7 @@ int launch_one(const GemmParams& p, hipStream_t st) {
   OSK_ENSURE_MAX_SMEM(kernel, OSKX_SMEM);
   GemmPack<1> pk;
   pk.p[0] = p;
-  const int ntiles = ((p.M + 255) / 256) * ((p.N - p.skip_len + 255) / 256);
-  hipLaunchKernelGGL(kernel, dim3(grid_for(ntiles)), dim3(256), OSKX_SMEM, st, pk);
+  hipLaunchKernelGGL(kernel, dim3(osk_tile256::persistent_grid(tiles_of(p))), dim3(256), OSKX_SMEM, st, pk);   // (LDS: 128 KiB of 160)
   return (int)hipGetLastError();
 }
 
@@ -361,8 +265,6 @@ int launch_gemm256x(const GemmParams& p, int out_f32, hipStream_t st) {
   return out_f32 ? launch_one<true>(p, st) : launch_one<false>(p, st);
 }
 
-static int tiles_of(const GemmParams& p) { return ((p.M + 255) / 256) * ((p.N - p.skip_len + 255) / 256); }
-
 // two problems with equal K in one launch (bf16 output)
 int launch_gemm256x_pair(const GemmParams& p0, const GemmParams& p1, hipStream_t st) {
   auto kernel = gemm256x_kernel<false, 2>;
@@ -370,7 +272,7 @@ int launch_gemm256x_pair(const GemmParams& p0, const GemmParams& p1, hipStream_t
   GemmPack<2> pk;
   pk.p[0] = p0;
   pk.p[1] = p1;
-  hipLaunchKernelGGL(kernel, dim3(grid_for(tiles_of(p0) + tiles_of(p1))), dim3(256), OSKX_SMEM, st, pk);
+  hipLaunchKernelGGL(kernel, dim3(osk_tile256::persistent_grid(tiles_of(p0) + tiles_of(p1))), dim3(256), OSKX_SMEM, st, pk);
   return (int)hipGetLastError();
 }
 
@@ -386,7 +288,7 @@ int launch_gemm256x_vt(const GemmParams* ps, int n, hipStream_t st) {
     if (i >= n) pk.p[i].M = 0;          // (an empty second slot: no tiles)
     ntiles += tiles_of(pk.p[i]);
   }
-  hipLaunchKernelGGL(kernel, dim3(grid_for(ntiles)), dim3(256), OSKX_SMEM, st, pk);
+  hipLaunchKernelGGL(kernel, dim3(osk_tile256::persistent_grid(ntiles)), dim3(256), OSKX_SMEM, st, pk);
   return (int)hipGetLastError();
 }
 

@@ -1,5 +1,6 @@
-// Fused epilogue of the large-tile GEMM kernels (gemm256.hip [fp8], gemm256p.hip; the 16 x 16 accumulator layout of gemm256x.hip has its own: gemm_epilogue16.h): bias / GELU-tanh / gate * x + residual /
-// bf16 or f32 store, on the accumulator layout of v_mfma_f32_32x32x16_bf16 with swapped operands (a lane owns ONE output
+// Fused epilogue of gemm256p.hip (the 16 x 16 accumulator layout of gemm256x.hip has its own, gemm_epilogue16.h; the fp8 kernel
+// gemm256.hip keeps a private copy of this layout's epilogue with its per-row / per-column scales in front): bias / GELU-tanh /
+// gate * x + residual / bf16 or f32 store, on the accumulator layout of v_mfma_f32_32x32x16_bf16 with swapped operands (a lane owns ONE output
 // row and 4 consecutive columns per 8-column block).  Geo supplies the wave tile: TM x TN MFMA tiles and
 // read<T>(aq, float[16]) = the 16 accumulator registers of tile T = tn * TM + tm out of aq = the wave's accumulator quads as
 // compiler-visible values (acc_quads.h: outputs of an empty asm statement behind the K loop; tile T = quads 4 T .. 4 T + 3).

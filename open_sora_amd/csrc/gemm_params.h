@@ -1,4 +1,5 @@
-// Launch parameters shared by the bf16 GEMM kernels (gemm_bf16.hip, gemm256.hip).
+// Launch parameters of every GEMM kernel: gemm_bf16.hip (128 x 128 tiles, and the dispatcher), gemm256x.hip, gemm256p.hip (bf16, 256-row
+// tiles), gemm256.hip (fp8).  What the 256-row kernels do alike around their K loops is csrc/tile256.h.
 #pragma once
 #include "osk_common.h"
 #include <utility>

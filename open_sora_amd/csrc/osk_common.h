@@ -88,6 +88,10 @@ OSK_DEV void quad_transpose(unsigned& x0, unsigned& x1, unsigned& x2, unsigned& 
   x3 = hi ? y3 : t1;
 }
 
+// a wave-uniform value as the compiler knows it: in SGPRs (the "s" operands of the generated asm loops)
+OSK_DEV unsigned rfl(unsigned v) { return __builtin_amdgcn_readfirstlane(v); }
+OSK_DEV uint64_t rfl64(uint64_t v) { return ((uint64_t)rfl((unsigned)(v >> 32)) << 32) | rfl((unsigned)v); }
+
 // Bijective XCD-aware remap of a 1-D block id (block b is observed on XCD b % 8): give every XCD a
 // contiguous range of logical tiles so neighbouring tiles share that XCD's private 4 MiB L2.
 OSK_DEV int xcd_remap(int bid, int nblk) {

@@ -897,6 +897,60 @@ def test_gemm_group_vt_task_equals_gemm_plus_v_transpose(hip_lib, hd, H, B, L, K
     assert (got[..., ~valid.to(DEV)] == 0).all(), "positions behind the sequence end must be zero"
 
 
+def _vt_walk_case(single):
+    """V^T groups whose workgroups walk SEVERAL tiles (K = 128 keeps them cheap).  Returns the streams (rows of the joint sequence,
+    first key position), the joint length and the tile counts per problem.  single: hd 64, H 16 (4 row tiles), B 2, L 8400 -- 33
+    column tiles per batch, the last one with a ragged key end: affine and non-affine successors.  Otherwise the img / txt layout of a
+    double block, B 1: the img problem alone has more tiles than the part has CUs, so the problem boundary falls mid-walk."""
+    hd, H, K = 64, 16, 128
+    B, streams = (2, [(0, 8400)]) if single else (1, [(128, 16500), (0, 128)])       # (first row = first key position, rows)
+    L = sum(n for _, n in streams)
+    tiles = [(H * hd + 255) // 256 * ((B * ((n + 63) // 64 * 64) + 255) // 256) for _, n in streams]
+    return hd, H, K, B, L, streams, tiles
+
+
+@pytest.mark.parametrize("single", [True, False], ids=["one_task_264_tiles", "img_txt_pack"])
+def test_gemm_group_vt_workgroups_walk_several_tiles(hip_lib, single):
+    """gemm256x_vt_kernel's cross-tile prefetch, affine test and w_origin delta: they run only where a workgroup has more than one tile,
+    i.e. with more tiles than CUs.  References and tolerances of test_gemm_group_vt_task_equals_gemm_plus_v_transpose: the two-kernel
+    path and fp64; zero pad, nothing in front of the first position, three launches bit-identical."""
+    hd, H, K, B, L, streams, tiles = _vt_walk_case(single)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    assert tiles[0] > cus, f"{tiles} tiles on {cus} CUs: no workgroup would walk a second tile of the first problem"
+    N = H * hd
+    x = rnd("x", (B, L, K), seed=231)
+    ws = [rnd(f"w{i}", (N, K), std=K ** -0.5, seed=232 + i) for i in range(len(streams))]
+    bs = [rnd(f"b{i}", (N,), std=0.3, dtype=torch.float32, seed=236 + i) for i in range(len(streams))]
+    Lp = (L + 63) // 64 * 64
+
+    def run():
+        vt = torch.full((B, H, hd, Lp + 64), 7.0, dtype=BF, device=DEV)      # a wider key axis: the tasks start at position 64
+        assert hip_lib.gemm_group([dict(x=x[:, r0: r0 + n], w=w, bias=b, vt=vt, vt_pos=64 + r0, hd=hd)
+                                   for (r0, n), w, b in zip(streams, ws, bs)])
+        return vt
+
+    vt = run()
+    # the two-kernel path: osk_gemm_bf16 per stream into the joint [B, L, H*hd] + osk_v_transpose_bf16
+    v = torch.empty(B, L, N, dtype=BF, device=DEV)
+    for (r0, n), w, b in zip(streams, ws, bs):
+        hip_lib.gemm(x[:, r0: r0 + n], w, b, v[:, r0: r0 + n])
+    ref = torch.zeros(B, H, hd, Lp, dtype=BF, device=DEV)
+    hip_lib.v_transpose(v, ref, H, hd)
+    assert (vt[..., :64] == 7.0).all(), "wrote in front of its first position"
+    got = vt[..., 64:]
+    bf16_ulp_close(got.float().cpu(), ref.float().cpu(), rel=2 ** -7, abs_=2e-3)
+    from tests import cpu_ops
+    key = cpu_ops.pos2key(hd, Lp)
+    pad = torch.zeros(B, Lp, N, dtype=torch.float64)
+    for (r0, n), w, b in zip(streams, ws, bs):
+        pad[:, r0: r0 + n] = x[:, r0: r0 + n].double().cpu() @ w.double().cpu().T + b.double().cpu()
+    ref64 = pad[:, key].reshape(B, Lp, H, hd).permute(0, 2, 3, 1)
+    bf16_ulp_close(got.float().cpu(), ref64.float().bfloat16().float(), rel=2 ** -7, abs_=2e-3)
+    assert (got[..., ~(key < L).to(DEV)] == 0).all(), "positions behind the sequence end must be zero"
+    for _ in range(2):
+        assert torch.equal(run(), vt), "V^T group: run-to-run difference"
+
+
 def test_gemm_group_skip_range_and_block_packs(hip_lib):
     """a single-stream block's linear1 without its V columns (row layout [q | k | . | gelu(mlp)]) + the V^T task in one launch, and a
     double block's four problems (img / txt q|k + img / txt V^T behind each other on the key axis) -- against the single calls."""

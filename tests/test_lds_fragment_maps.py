@@ -64,7 +64,7 @@ def test_lds_dma_piece_writes_whole_swizzled_rows():
         seen = set()
         for l in range(64):
             r = 8 * j + (l >> 3)
-            c = (l & 7) ^ ((r >> 1) & 7)      # source chunk of this lane (csrc/gemm256*.hip: `spos ^ ((r >> 1) & 7)`)
+            c = (l & 7) ^ ((r >> 1) & 7)      # source chunk of this lane (csrc/tile256.h: dma_row / dma_chunk)
             assert image_addr(r, c) == r * 128 + ((l & 7) << 4)   # lands at the lane's linear LDS position
             seen.add((r, c))
         assert len(seen) == 64
