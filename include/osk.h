@@ -496,7 +496,7 @@ int64_t osk_attention_hd512_workspace_bytes(int B, int S);
 int osk_blend_bf16(const void* a, void* b, int64_t outer, int Da, int Db, int extent, int64_t inner, void* stream);
 
 /* =====================================================================================================
- * Video DC-AE decoder (/root/reference/opensora/models/dc_ae, "dc-ae-f32t4c128": the autoencoder of
+ * Video DC-AE decoder and encoder (/root/reference/opensora/models/dc_ae, "dc-ae-f32t4c128": the autoencoder of
  * configs/diffusion/inference/high_compression.py).  Activations are NDHWC bf16 ([B, T, H, W, C] contiguous); the 1x1x1
  * convolutions without an activation are osk_gemm_bf16 over the B*T*H*W rows.  (Added without changing any existing contract:
  * the version stays 2.)  csrc/dc_ae.hip.
@@ -518,6 +518,32 @@ int osk_blend_bf16(const void* a, void* b, int64_t outer, int Da, int Db, int ex
 int osk_conv3d_zp_ndhwc_bf16(const void* x, int B, int T, int H, int W, int Cin, const void* w, int64_t w_row_stride,
                              const float* bias, int Cout, int ksize, int up_t, int up_hw, int act, const void* res,
                              void* out, void* stream);
+
+/* ---- zero-padded strided Conv3d of the encoder's downsample blocks (+ residual add behind).
+ * replaces ConvLayer(is_video=True, kernel_size=3, stride=(1|2, 2, 2), use_bias=True, norm=None, act_func=None) as
+ * build_downsample_block builds it (dc_ae.py:166-195) -- F.pad(x, (1,)*6, "constant") + ChannelChunkConv3d(stride) (ops.py:87-106,
+ * 130-131) -- and the `main + shortcut` of ResidualBlock.forward (ops.py:923) when res != NULL.
+ *   x   bf16 [B, T, H, W, Cin], Cin = 8 * 2^j;  w, w_row_stride, bias as for osk_conv3d_zp_ndhwc_bf16 with k = 3
+ *   stride_t 1 | 2, stride_hw == 2 (anything else: OSK_EINVAL)
+ *   out bf16 [B, (T-1)/stride_t + 1, (H-1)/2 + 1, (W-1)/2 + 1, Cout] (PyTorch's floor((n + 2 - 3)/s) + 1);  res like out | NULL
+ *   out[b, to, ho, wo] = bf16( sum_taps w . x[b, to*stride_t - 1 + dt, ho*2 - 1 + dh, wo*2 - 1 + dw] + bias + res ), taps outside
+ *   the volume of batch b are zeros; f32 accumulate, one rounding, no activation.  Odd T, H, W are legal (there the far padding
+ *   is read); stride_t = 2 with T = 1 yields one frame from the taps (pad, frame, pad).
+ * The tile, alignment rules, limits and error codes of osk_conv3d_zp_ndhwc_bf16. */
+int osk_conv3d_zp_strided_ndhwc_bf16(const void* x, int B, int T, int H, int W, int Cin, const void* w, int64_t w_row_stride,
+                                     const float* bias, int Cout, int stride_t, int stride_hw, const void* res, void* out,
+                                     void* stream);
+
+/* ---- pixel-unshuffle channel averaging: the shortcut of the encoder's downsample blocks and of its project_out.
+ * replaces PixelUnshuffleChannelAveragingDownSampleLayer.forward (ops.py:189-228): pixel_unshuffle_3d (vo_ops.py:38-56; ft = fhw = 2),
+ * or F.pixel_unshuffle on H, W only (no temporal downsample or T == 1, ops.py:217-222; ft = 1, fhw = 2), or the factor-1 form of
+ * project_out (ft = fhw = 1), then view(B, Cout, gs, ...).mean(2).  per = ft * fhw^2, gs = Cin * per / Cout (must divide):
+ *   out[b, t, h, w, co] = bf16( (1/gs) * sum_{g < gs} x[b, t*ft + dt, h*fhw + dh, w*fhw + dw, c] ),
+ *   u = co*gs + g, c = u / per, s = u % per, dt = s / fhw^2, dh = (s / fhw) % fhw, dw = s % fhw.
+ * x bf16 [B, T, H, W, Cin]; out bf16 [B, T/ft, H/fhw, W/fhw, Cout].  f32 sum, one rounding.  A gather, HBM bound.
+ * T % ft, H % fhw, W % fhw or Cin * per % Cout != 0: OSK_EINVAL;  Cout % 8 != 0: OSK_EUNSUPPORTED; nothing launched. */
+int osk_unshuffle_avg_ndhwc_bf16(const void* x, int B, int T, int H, int W, int Cin, void* out, int Cout, int ft, int fhw,
+                                 void* stream);
 
 /* ---- channel-duplicating pixel shuffle: the shortcut of the upsample blocks and of project_in.
  * replaces ChannelDuplicatingPixelShuffleUpSampleLayer.forward (ops.py:316-337): repeat_interleave(rep, dim=1) + pixel_shuffle_3d

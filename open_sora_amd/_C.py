@@ -80,7 +80,9 @@ SIGNATURES = {
     "osk_attention_hd512_fwd_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _i32,
                                      _i32, _f32, _vp],
     "osk_conv3d_zp_ndhwc_bf16": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
+    "osk_conv3d_zp_strided_ndhwc_bf16": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
     "osk_dup_shuffle_ndhwc_bf16": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp],
+    "osk_unshuffle_avg_ndhwc_bf16": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp],
     "osk_dwconv3d_ndhwc_bf16": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp],
     "osk_gconv32_bf16": [_vp, _i64, _i32, _vp, _vp, _vp],
     "osk_relu_linear_attn_bf16": [_vp, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _f32, _vp],
@@ -876,7 +878,7 @@ def attention_hd512(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, bias_v, 
 
 
 # ----------------------------------------------------------------------------------------------
-# Video DC-AE decoder (csrc/dc_ae.hip)
+# Video DC-AE decoder and encoder (csrc/dc_ae.hip)
 # ----------------------------------------------------------------------------------------------
 def conv3d_zp(x: torch.Tensor, w: torch.Tensor, bias, out: torch.Tensor, ksize: int, up_t: bool = False, up_hw: bool = False,
               silu: bool = False, res=None) -> torch.Tensor:
@@ -898,6 +900,40 @@ def conv3d_zp(x: torch.Tensor, w: torch.Tensor, bias, out: torch.Tensor, ksize: 
     if prof is not None:
         ev1.record()
         prof.append((ev0, ev1, 2.0 * Cin * Cout * ksize ** 3 * out.numel() / Cout))
+    return out
+
+
+def conv3d_zp_strided(x: torch.Tensor, w: torch.Tensor, bias, out: torch.Tensor, stride_t: int, res=None) -> torch.Tensor:
+    """zero-padded k = 3 conv with stride (stride_t, 2, 2), NDHWC bf16.  x [B, T, H, W, Cin] contiguous, Cin = 8 * 2^j; w, bias as
+    for conv3d_zp; out bf16 [B, (T-1)//stride_t + 1, (H-1)//2 + 1, (W-1)//2 + 1, Cout]; res like out | None."""
+    B, T, H, W, Cin = x.shape
+    Cout = w.shape[0]
+    want = (B, (T - 1) // stride_t + 1, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cout)
+    assert x.is_contiguous() and out.is_contiguous() and tuple(out.shape) == want, (out.shape, want)
+    assert x.dtype == w.dtype == out.dtype == torch.bfloat16
+    assert res is None or (res.is_contiguous() and res.shape == out.shape and res.dtype == torch.bfloat16)
+    prof = PROFILE_CONV
+    if prof is not None:
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+    _check(lib.osk_conv3d_zp_strided_ndhwc_bf16(x.data_ptr(), B, T, H, W, Cin, w.data_ptr(), w.stride(0), _p(bias), Cout,
+                                                int(stride_t), 2, _p(res), out.data_ptr(), _stream()),
+           "osk_conv3d_zp_strided_ndhwc_bf16")
+    if prof is not None:
+        ev1.record()
+        prof.append((ev0, ev1, 2.0 * Cin * Cout * 27 * out.numel() / Cout))
+    return out
+
+
+def unshuffle_avg(x: torch.Tensor, out: torch.Tensor, ft: int, fhw: int) -> torch.Tensor:
+    """pixel-unshuffle channel averaging: x bf16 [B, T, H, W, Cin] -> out bf16 [B, T/ft, H/fhw, W/fhw, Cout]"""
+    B, T, H, W, Cin = x.shape
+    Cout = out.shape[-1]
+    assert T % ft == 0 and H % fhw == 0 and W % fhw == 0, (x.shape, ft, fhw)
+    assert x.is_contiguous() and out.is_contiguous() and tuple(out.shape) == (B, T // ft, H // fhw, W // fhw, Cout), out.shape
+    assert x.dtype == out.dtype == torch.bfloat16
+    _check(lib.osk_unshuffle_avg_ndhwc_bf16(x.data_ptr(), B, T, H, W, Cin, out.data_ptr(), Cout, ft, fhw, _stream()),
+           "osk_unshuffle_avg_ndhwc_bf16")
     return out
 
 

@@ -1,9 +1,12 @@
-// Kernels of the Video DC-AE decoder (dc-ae-f32t4c128) for gfx950: every operator of
-// opensora/models/dc_ae/models/nn/ops.py the decoder runs, on channels-last NDHWC bf16 activations.
+// Kernels of the Video DC-AE autoencoder (dc-ae-f32t4c128) for gfx950: every operator of
+// opensora/models/dc_ae/models/nn/ops.py the decoder and the encoder run, on channels-last NDHWC bf16 activations.
 //
 //   osk_conv3d_zp_ndhwc_bf16     ConvLayer(is_video) k = 1 / 3: zero "same" padding on all six faces, + nearest upsample in front
 //                                (T and H,W independently), + bias, + SiLU, + residual add behind.  MFMA implicit GEMM.
+//   osk_conv3d_zp_strided_ndhwc_bf16  the encoder's downsample ConvLayer: k = 3, stride (1|2, 2, 2), zero padding 1, + bias,
+//                                + residual add.  The same tile; the gathered coordinate is out * stride - 1 + tap.
 //   osk_dup_shuffle_ndhwc_bf16   ChannelDuplicatingPixelShuffleUpSampleLayer: a pure gather (repeat_interleave + pixel shuffle).
+//   osk_unshuffle_avg_ndhwc_bf16 PixelUnshuffleChannelAveragingDownSampleLayer: pixel unshuffle + mean over channel groups.
 //   osk_dwconv3d_ndhwc_bf16      depthwise Conv3d k = 3 / 5, zero padded, + bias, + the GLU x * silu(gate) of GLUMBConv.
 //   osk_gconv32_bf16             block-diagonal 1x1x1 conv, 32 -> 32 channels per group (LiteMLA.aggreg[0][1]).  MFMA.
 //   osk_relu_linear_attn_bf16    LiteMLA.relu_linear_att per (batch, 96-channel [q|k|v] group), f32 accumulation.
@@ -31,10 +34,11 @@ struct Conv3dParams {
   const float* bias;
   const unsigned short* res;
   unsigned short* out;
-  int T, H, W;       // source (pre-upsample) dims
-  int Tu, Hu, Wu;    // dims the conv sees == output dims
+  int T, H, W;       // source (pre-upsample / pre-stride) dims
+  int Tu, Hu, Wu;    // output dims (stride 1: also the dims the conv sees)
   int Cout;
   int ks, ut, uh, act;
+  int st, sh;        // strided conv only: temporal and spatial stride
   int lg_cpt, ntaps, nk;
   int M;
   int brick;         // 1 = a tile is an 8 x 16 brick of one frame
@@ -46,6 +50,13 @@ template <bool BIGC>
 struct Conv3dASrc {
   const Conv3dParams& p;
   int pB[4], pT[4], pH[4], pW[4];   // batch base frame, first tap coordinate in the upsampled volume (may be < 0: zero padding)
+  __device__ __forceinline__ void set(int i, int b, int to, int ho, int wo) {
+    const int pad = p.ks >> 1;
+    pB[i] = b * p.T;
+    pT[i] = to - pad;
+    pH[i] = ho - pad;
+    pW[i] = wo - pad;
+  }
   __device__ __forceinline__ const unsigned short* operator()(const Lane& g, int i, int kt) const {
     const TapChunk tc = tap_chunk<BIGC>(kt, g.cch[i], p.lg_cpt);
     const Tap3 d = tap3(tc.tap, p.ks);
@@ -56,13 +67,34 @@ struct Conv3dASrc {
   }
 };
 
+// A operand of the strided conv (k = 3, padding 1): the first tap of output (to, ho, wo) sits at source (to * st - 1, ho * sh - 1,
+// wo * sh - 1).  The batch base stays apart from the temporal coordinate, so a padded tap of batch b is a zero, never batch b +- 1
 template <bool BIGC>
+struct Conv3dStridedASrc {
+  const Conv3dParams& p;
+  int pB[4], pT[4], pH[4], pW[4];   // batch base frame, first tap coordinate in the source volume (-1: zero padding)
+  __device__ __forceinline__ void set(int i, int b, int to, int ho, int wo) {
+    pB[i] = b * p.T;
+    pT[i] = to * p.st - 1;
+    pH[i] = ho * p.sh - 1;
+    pW[i] = wo * p.sh - 1;
+  }
+  __device__ __forceinline__ const unsigned short* operator()(const Lane& g, int i, int kt) const {
+    const TapChunk tc = tap_chunk<BIGC>(kt, g.cch[i], p.lg_cpt);
+    const Tap3 d = tap3(tc.tap, 3);
+    const int t = pT[i] + d.dt, h = pH[i] + d.dh, w = pW[i] + d.dw;
+    const bool in = tc.tap < p.ntaps && (unsigned)t < (unsigned)p.T && (unsigned)h < (unsigned)p.H && (unsigned)w < (unsigned)p.W;
+    const int pos = ((pB[i] + t) * p.H + h) * p.W + w;
+    return in ? p.x + (((int64_t)pos << p.lg_cpt) + tc.cc) * 8 : conv3d_zero_page;
+  }
+};
+
+template <class ASrc>
 __global__ void __launch_bounds__(256, 2) conv3d_zp_kernel(const Conv3dParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const Lane g = make_lane(p.M, p.Cout, p.w, p.wrs);
 
-  Conv3dASrc<BIGC> a_src = {p};
-  const int pad = p.ks >> 1;
+  ASrc a_src = {p};
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     // tail rows re-read the last voxel (never stored)
@@ -73,10 +105,7 @@ __global__ void __launch_bounds__(256, 2) conv3d_zp_kernel(const Conv3dParams p)
     q /= p.Hu;
     const int to = q % p.Tu;
     const int b = q / p.Tu;
-    a_src.pB[i] = b * p.T;
-    a_src.pT[i] = to - pad;
-    a_src.pH[i] = ho - pad;
-    a_src.pW[i] = wo - pad;
+    a_src.set(i, b, to, ho, wo);
   }
 
   f32x16_t acc[2][2];
@@ -119,6 +148,40 @@ __global__ void __launch_bounds__(256) dup_shuffle_kernel(const unsigned short* 
   o.z = r[4] | ((unsigned)r[5] << 16);
   o.w = r[6] | ((unsigned)r[7] << 16);
   *reinterpret_cast<uint4*>(out + idx * 8) = o;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// out[b, t, h, w, co] = mean over g < gs of x[b, t*ft + dt, h*fh + dh, w*fh + dw, c],  u = co*gs + g, c = u / per, s = u % per,
+// (dt, dh, dw) = (s / fh^2, (s / fh) % fh, s % fh), per = ft * fh^2.  One thread = 8 output channels of one output voxel: the
+// 8 * gs consecutive u it sums walk the sub-voxels fastest and the source channels slowest
+__global__ void __launch_bounds__(256) unshuffle_avg_kernel(const unsigned short* __restrict__ x, unsigned short* __restrict__ out,
+                                                            int To, int Ho, int Wo, int Cin, int Cout, int ft, int fh, int gs,
+                                                            float inv_gs, int64_t total) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int cchunks = Cout >> 3;
+  const int c0 = (int)(idx % cchunks) * 8;
+  int64_t v = idx / cchunks;
+  const int wo = (int)(v % Wo); v /= Wo;
+  const int ho = (int)(v % Ho); v /= Ho;
+  const int to = (int)(v % To);
+  const int b = (int)(v / To);
+  const int H = Ho * fh, W = Wo * fh;
+  const int fh2 = fh * fh, per = ft * fh2;
+  const int64_t src = ((((int64_t)b * To + to) * ft * H + (int64_t)ho * fh) * W + (int64_t)wo * fh) * Cin;
+  float a[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float t = 0.f;
+    for (int k = 0; k < gs; ++k) {
+      const int u = (c0 + j) * gs + k;
+      const int c = u / per, s = u - c * per;
+      const int dt = s / fh2, dh = (s / fh) % fh, dw = s % fh;
+      t += bf16_bits_to_f32(x[src + ((int64_t)(dt * H + dh) * W + dw) * Cin + c]);
+    }
+    a[j] = t * inv_gs;
+  }
+  *reinterpret_cast<uint4*>(out + idx * 8) = pack8(a);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -392,8 +455,56 @@ extern "C" int osk_conv3d_zp_ndhwc_bf16(const void* x, int B, int T, int H, int 
   if (nblk >= MAX_BLOCKS) return OSK_EUNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((unsigned)nblk), block(256);
-  if (Cin % 64 == 0) hipLaunchKernelGGL((conv3d_zp_kernel<true>), grid, block, SMEM_BYTES, s, p);
-  else hipLaunchKernelGGL((conv3d_zp_kernel<false>), grid, block, SMEM_BYTES, s, p);
+  if (Cin % 64 == 0) hipLaunchKernelGGL((conv3d_zp_kernel<Conv3dASrc<true>>), grid, block, SMEM_BYTES, s, p);
+  else hipLaunchKernelGGL((conv3d_zp_kernel<Conv3dASrc<false>>), grid, block, SMEM_BYTES, s, p);
+  return (int)hipGetLastError();
+}
+
+extern "C" int osk_conv3d_zp_strided_ndhwc_bf16(const void* x, int B, int T, int H, int W, int Cin, const void* w,
+                                                int64_t w_row_stride, const float* bias, int Cout, int stride_t, int stride_hw,
+                                                const void* res, void* out, void* stream) {
+  if (!x || !w || !out || B <= 0 || T <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return OSK_EINVAL;
+  if ((stride_t != 1 && stride_t != 2) || stride_hw != 2) return OSK_EINVAL;
+  if ((Cin & 7) || (Cin & (Cin - 1))) return OSK_EUNSUPPORTED;  // Cin = 8 * 2^j
+  if (!al16(x) || !al16(w) || !al16(bias) || ((uintptr_t)out & 7) || ((uintptr_t)res & 7)) return OSK_EINVAL;
+  Conv3dParams p;
+  p.x = (const unsigned short*)x; p.w = (const unsigned short*)w; p.bias = bias;
+  p.res = (const unsigned short*)res; p.out = (unsigned short*)out;
+  p.T = T; p.H = H; p.W = W; p.Cout = Cout;
+  p.ut = 0; p.uh = 0; p.act = 0; p.ks = 3;
+  p.st = stride_t; p.sh = stride_hw;
+  const int64_t To = (T - 1) / stride_t + 1, Ho = (H - 1) / stride_hw + 1, Wo = (W - 1) / stride_hw + 1;
+  const int64_t M = (int64_t)B * To * Ho * Wo;
+  if ((int64_t)B * T * H * W >= (int64_t)1 << 31 || (int64_t)B * T * H * W * Cin >= (int64_t)1 << 34) return OSK_EUNSUPPORTED;
+  p.Tu = (int)To; p.Hu = (int)Ho; p.Wu = (int)Wo;
+  p.M = (int)M;
+  p.brick = (Ho % 8 == 0 && Wo % 16 == 0) ? 1 : 0;
+  p.ntaps = 27;
+  if (conv_k_layout(Cin, p.ntaps, w_row_stride, &p.lg_cpt, &p.nk) != OSK_OK) return OSK_EINVAL;
+  p.wrs = w_row_stride;
+  const int64_t nblk = ((M + BM - 1) / BM) * ((Cout + BN - 1) / BN);
+  if (nblk >= MAX_BLOCKS) return OSK_EUNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid((unsigned)nblk), block(256);
+  if (Cin % 64 == 0) hipLaunchKernelGGL((conv3d_zp_kernel<Conv3dStridedASrc<true>>), grid, block, SMEM_BYTES, s, p);
+  else hipLaunchKernelGGL((conv3d_zp_kernel<Conv3dStridedASrc<false>>), grid, block, SMEM_BYTES, s, p);
+  return (int)hipGetLastError();
+}
+
+extern "C" int osk_unshuffle_avg_ndhwc_bf16(const void* x, int B, int T, int H, int W, int Cin, void* out, int Cout, int ft, int fhw,
+                                            void* stream) {
+  if (!x || !out || B <= 0 || T <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return OSK_EINVAL;
+  if ((ft != 1 && ft != 2) || (fhw != 1 && fhw != 2)) return OSK_EINVAL;
+  if (T % ft || H % fhw || W % fhw || !al16(out)) return OSK_EINVAL;
+  if (Cout & 7) return OSK_EUNSUPPORTED;
+  const int64_t per = (int64_t)ft * fhw * fhw;
+  if ((Cin * per) % Cout) return OSK_EINVAL;
+  const int64_t gs = Cin * per / Cout;
+  const int64_t total = (int64_t)B * (T / ft) * (H / fhw) * (W / fhw) * (Cout >> 3);
+  const int64_t nblk = (total + 255) / 256;
+  if (nblk >= MAX_BLOCKS || Cin * per >= (int64_t)1 << 31) return OSK_EUNSUPPORTED;
+  hipLaunchKernelGGL(unshuffle_avg_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x,
+                     (unsigned short*)out, T / ft, H / fhw, W / fhw, Cin, Cout, ft, fhw, (int)gs, 1.0f / (float)gs, total);
   return (int)hipGetLastError();
 }
 
