@@ -330,6 +330,21 @@ int osk_attention_short_bf16(const void* q, int64_t q_batch_stride, int64_t q_ro
                              int64_t o_batch_stride, int64_t o_row_stride, const float* alibi_slopes, int B, int H, int Lq, int Lk,
                              int hd, float scale, void* stream);
 
+/* ---- self-attention with a learned relative-position bias: the attention of the T5 text encoder.
+ * replaces T5Attention.forward inside the Hugging Face T5EncoderModel that HFEmbedder runs (opensora/models/text/conditioner.py:48-53:
+ * T5-v1.1-XXL, 512 tokens, attention_mask=None -- pad tokens are attended).  T5 self-attention is non-causal, does not scale its
+ * scores (the caller passes scale = 1.0) and adds a per-head bias that depends on the relative distance j - i alone:
+ *   out[b, i, h] = sum_j softmax_j(scale * q_i . k_j + bias[h * bias_row_stride + (j - i) + (L - 1)]) v_j ,   Lq = Lk = L
+ * q, k, v, out bf16 [B, L, H * hd] views (batch / row strides in elements, last dim contiguous: q, k, v may be the three column
+ * groups of one fused [B, L, 3 * H * hd] projection output); V is taken as is (no osk_v_transpose_bf16).  bias f32
+ * [H, >= 2 L - 1] indexed by distance (open_sora_amd/t5.py expands T5's 32-bucket embedding into it once per L), or NULL (no
+ * bias).  Scores, bias add and online softmax in f32; no L x L matrix in memory.  hd == 64 and 1 <= L <= 4096, any L (key tails
+ * are masked, query rows >= L never stored); another hd or a longer L: OSK_EUNSUPPORTED. */
+int osk_attention_relbias_bf16(const void* q, int64_t q_batch_stride, int64_t q_row_stride, const void* k, int64_t k_batch_stride,
+                               int64_t k_row_stride, const void* v, int64_t v_batch_stride, int64_t v_row_stride, void* out,
+                               int64_t o_batch_stride, int64_t o_row_stride, const float* bias, int64_t bias_row_stride, int B,
+                               int H, int L, int hd, float scale, void* stream);
+
 /* name of the device kernel osk_attention_fwd_bf16 dispatches to for (hd, seg_len) (reporting only: bench.py labels its
  * roofline line and the rocprof stats with it). */
 const char* osk_attention_kernel_name(int hd, int seg_len);

@@ -23,6 +23,8 @@ SIGNATURES = {
     "osk_gemm_geglu_bf16": [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _vp],
     "osk_attention_short_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _i32,
                                  _f32, _vp],
+    "osk_attention_relbias_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i32, _i32, _i32, _i32,
+                                   _f32, _vp],
     "osk_attention_kernel_name": [_i32, _i32],
     "osk_attention_body_name": [_i32, _i32, _i32, _f32],
     "osk_ln_modulate_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _vp],
@@ -553,6 +555,28 @@ def attention_short(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torc
     _check(lib.osk_attention_short_bf16(q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1), v.data_ptr(),
                                         v.stride(0), v.stride(1), out.data_ptr(), out.stride(0), out.stride(1), _p(alibi_slopes),
                                         B, H, Lq, Lk, hd, scale, _stream()), "osk_attention_short_bf16")
+    return out
+
+
+def attention_relbias(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, H: int, hd: int, scale: float,
+                      bias: torch.Tensor | None = None) -> torch.Tensor:
+    """softmax(scale q k^T + bias[h, (j - i) + L - 1]) v, the T5 self-attention (osk_attention_relbias_bf16); q, k, v, out bf16
+    [B, L, H*hd] views with contiguous last dim (q, k, v may be column groups of one fused projection output); bias f32
+    [H, >= 2L - 1] with contiguous rows (any row stride) or None."""
+    B, L, C = q.shape
+    assert C == H * hd and k.shape == q.shape and v.shape == q.shape and out.shape == q.shape, (q.shape, k.shape, v.shape, out.shape)
+    assert q.dtype == k.dtype == v.dtype == out.dtype == torch.bfloat16, (q.dtype, k.dtype, v.dtype, out.dtype)
+    for t in (q, k, v):
+        assert t.stride(2) == 1 and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0 and t.data_ptr() % 16 == 0, (t.stride(), t.data_ptr() % 16)
+    assert out.stride(2) == 1 and out.stride(0) % 4 == 0 and out.stride(1) % 4 == 0 and out.data_ptr() % 8 == 0, out.stride()
+    brs = 0
+    if bias is not None:
+        assert bias.dtype == torch.float32 and bias.dim() == 2 and bias.shape[0] == H and bias.shape[1] >= 2 * L - 1, (bias.dtype, bias.shape)
+        assert bias.stride(1) == 1 and bias.stride(0) >= 2 * L - 1, bias.stride()
+        brs = bias.stride(0)
+    _check(lib.osk_attention_relbias_bf16(q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1), v.data_ptr(),
+                                          v.stride(0), v.stride(1), out.data_ptr(), out.stride(0), out.stride(1), _p(bias), brs,
+                                          B, H, L, hd, scale, _stream()), "osk_attention_relbias_bf16")
     return out
 
 
