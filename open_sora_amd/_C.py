@@ -181,26 +181,36 @@ def ln_modulate(x: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor, out: 
     return out
 
 
-# bench.py sets this to a list to collect (start, end, FLOPs) around every GEMM launch of a side measurement (never the timed region)
+# bench.py sets these to lists for a side measurement (never the timed region): (start, end, FLOPs) around every GEMM launch,
+# (start, end) around every flash-attention launch
 PROFILE_GEMM = None
+PROFILE_ATTENTION = None
 
 
-class _gemm_prof:
-    """context: two HIP events around the launches inside, appended to PROFILE_GEMM with their algorithmic FLOPs"""
+class _prof:
+    """context: two HIP events around the launches inside, appended to `sink` (one of the lists above; None: off) with `extra`"""
 
-    def __init__(self, flops: float):
-        self.flops, self.on = flops, PROFILE_GEMM is not None
+    def __init__(self, sink, *extra):
+        self.sink, self.extra = sink, extra
 
     def __enter__(self):
-        if self.on:
+        if self.sink is not None:
             self.e0, self.e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             self.e0.record()
 
     def __exit__(self, *exc):
-        if self.on:
+        if self.sink is not None:
             self.e1.record()
-            PROFILE_GEMM.append((self.e0, self.e1, self.flops))
+            self.sink.append((self.e0, self.e1, *self.extra))
         return False
+
+
+def _gemm_prof(flops: float) -> _prof:
+    return _prof(PROFILE_GEMM, flops)
+
+
+def _attn_prof() -> _prof:
+    return _prof(PROFILE_ATTENTION)
 
 
 def gemm(a: torch.Tensor, w: torch.Tensor, bias, out: torch.Tensor, *, res=None, gate=None,
@@ -256,9 +266,11 @@ class OskGemmOperands(C.Structure):
                 ("res", _vp), ("gate", _vp), ("gate_batch_stride", _i64), ("M", _i32)]
 
 
-def _gemm_operands(a, w, bias, out, res, gate, gate_batch_stride) -> OskGemmOperands:
+def _gemm_operands(a, w, bias, out, res, gate, gate_batch_stride, *, wide_out: bool = False) -> OskGemmOperands:
+    """wide_out: the output tensor may be WIDER than the task's N (a skip range / a column slice of gemm_group: the row layout
+    [q | k | . | mlp] is addressed through its row stride)"""
     B, L, K = a.shape
-    assert out.shape[0] == B and out.shape[1] == L and out.shape[2] == w.shape[0] and w.shape[1] == K
+    assert out.shape[0] == B and out.shape[1] == L and (out.shape[2] >= 1 if wide_out else out.shape[2] == w.shape[0]) and w.shape[1] == K
     assert a.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and out.dtype == torch.bfloat16
     if res is not None:
         assert res.stride() == out.stride() and res.dtype == torch.bfloat16
@@ -307,7 +319,7 @@ def gemm_group(tasks: list) -> bool:
         else:
             a, w, out = d["a"], d["w"], d["out"]
             k_ = a.shape[2]
-            t.op = _gemm_operands_n(a, w, d.get("bias"), out, d.get("res"), d.get("gate"), d.get("gate_batch_stride", 0))
+            t.op = _gemm_operands(a, w, d.get("bias"), out, d.get("res"), d.get("gate"), d.get("gate_batch_stride", 0), wide_out=True)
             sf, sl = d.get("skip", (0, 0))
             t.N, t.gelu_from, t.skip_from, t.skip_len, t.vt_head_dim = w.shape[0], d.get("gelu_from", w.shape[0]) if d.get("gelu_from") is not None else w.shape[0], sf, sl, 0
             flops += 2.0 * a.shape[0] * a.shape[1] * (w.shape[0] - sl) * k_
@@ -319,18 +331,6 @@ def gemm_group(tasks: list) -> bool:
         return False
     _check(rc, "osk_gemm_group_bf16")
     return True
-
-
-def _gemm_operands_n(a, w, bias, out, res, gate, gate_batch_stride) -> OskGemmOperands:
-    """_gemm_operands for a task whose output tensor may be WIDER than the task's N (a skip range / a column slice: the row layout
-    [q | k | . | mlp] is addressed through its row stride)"""
-    B, L, K = a.shape
-    assert out.shape[0] == B and out.shape[1] == L and out.shape[2] >= 1 and w.shape[1] == K
-    assert a.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and out.dtype == torch.bfloat16
-    if res is not None:
-        assert res.stride() == out.stride() and res.dtype == torch.bfloat16
-    return OskGemmOperands(a.data_ptr(), a.stride(0), a.stride(1), L, w.data_ptr(), w.stride(0), _p(bias), out.data_ptr(),
-                           out.stride(0), out.stride(1), L, _p(res), _p(gate), gate_batch_stride, B * L)
 
 
 def ln_modulate_fp8(x: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor, mod_batch_stride: int, eps: float = 1e-6):
@@ -460,10 +460,6 @@ def v_transpose(v: torch.Tensor, vt: torch.Tensor, H: int, hd: int):
            "osk_v_transpose_bf16")
 
 
-# bench.py sets this to a list to collect (start, end) HIP events around every attention launch
-PROFILE_ATTENTION = None
-
-
 _ATTN_WS: dict = {}
 
 
@@ -479,6 +475,19 @@ def attention_workspace(device) -> torch.Tensor:
     return ws
 
 
+def _attn_call(name: str, q, k, vt, out, H, hd, scale, lse, n_seg, seg_len, k_seg_stride, vt_seg_stride, q_prescaled, kv_batches,
+               workspace, own=(), after_vt=()):
+    """the C call of the three flash-attention wrappers below (their arguments, in their order).  own: the entry point's arguments
+    between kv_batches and the workspace; after_vt: those between the V^T stride and out."""
+    B, Lq, _ = q.shape
+    with _attn_prof():
+        _check(getattr(lib, name)(q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k_seg_stride, k.stride(0), k.stride(1),
+                                  vt.data_ptr(), vt_seg_stride, *after_vt, out.data_ptr(), out.stride(0), out.stride(1), _p(lse),
+                                  B, H, Lq, n_seg, k.shape[1] if seg_len is None else seg_len, hd, scale, int(q_prescaled),
+                                  kv_batches, *own, _p(workspace), 0 if workspace is None else workspace.numel(), _stream()), name)
+    return out
+
+
 def attention_fwd(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Tensor, H: int, hd: int,
                   scale: float, *, lse=None, n_seg: int = 1, seg_len: int | None = None,
                   k_seg_stride: int = 0, vt_seg_stride: int = 0, q_prescaled: bool = False, kv_batches: int = 0,
@@ -488,25 +497,11 @@ def attention_fwd(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch
     attention_workspace()): lets the library split the workgroups of the grid's last partial round along the keys.
     score_bound > 0: |q . k| (as the kernel sees the scores, log2 units) never exceeds it -- enables the fast body
     (include/osk.h, osk_attention_fwd_bounded_bf16)."""
-    B, Lq, _ = q.shape
-    if seg_len is None:
-        seg_len = k.shape[1]
     if CHECK_SCORE_BOUND and score_bound > 0 and not torch.cuda.is_current_stream_capturing():   # (the check syncs: illegal in a capture)
-        _assert_score_bound(q, k, H, hd, scale, n_seg, seg_len, k_seg_stride, q_prescaled, kv_batches, score_bound)
-    prof = PROFILE_ATTENTION
-    if prof is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    _check(lib.osk_attention_fwd_bounded_bf16(q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k_seg_stride,
-                                              k.stride(0), k.stride(1), vt.data_ptr(), vt_seg_stride, out.data_ptr(),
-                                              out.stride(0), out.stride(1), _p(lse), B, H, Lq, n_seg, seg_len, hd,
-                                              scale, int(q_prescaled), kv_batches, float(score_bound), _p(workspace),
-                                              0 if workspace is None else workspace.numel(), _stream()),
-           "osk_attention_fwd_bounded_bf16")
-    if prof is not None:
-        ev1.record()
-        prof.append((ev0, ev1))
-    return out
+        _assert_score_bound(q, k, H, hd, scale, n_seg, k.shape[1] if seg_len is None else seg_len, k_seg_stride, q_prescaled, kv_batches,
+                            score_bound)
+    return _attn_call("osk_attention_fwd_bounded_bf16", q, k, vt, out, H, hd, scale, lse, n_seg, seg_len, k_seg_stride, vt_seg_stride,
+                      q_prescaled, kv_batches, workspace, own=(float(score_bound),))
 
 
 def rownorm2_max(x: torch.Tensor, out: torch.Tensor, H: int, hd: int, accumulate: bool = False) -> torch.Tensor:
@@ -524,24 +519,10 @@ def attention_fwd_auto(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: 
                        workspace: torch.Tensor | None = None):
     """attention_fwd with the score bound taken from the operands on the device (osk_attention_fwd_auto_bf16): qn2 / kn2 from
     rownorm2_max() of the q / k of THIS call (f32 [B, H] / [kv_batches or B, H]).  Units whose bound allows it run the FAST body."""
-    B, Lq, _ = q.shape
-    if seg_len is None:
-        seg_len = k.shape[1]
+    B = q.shape[0]
     assert qn2.dtype == kn2.dtype == torch.float32 and qn2.numel() == B * H and kn2.numel() == (kv_batches or B) * H
-    prof = PROFILE_ATTENTION
-    if prof is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    _check(lib.osk_attention_fwd_auto_bf16(q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k_seg_stride,
-                                           k.stride(0), k.stride(1), vt.data_ptr(), vt_seg_stride, out.data_ptr(),
-                                           out.stride(0), out.stride(1), _p(lse), B, H, Lq, n_seg, seg_len, hd,
-                                           scale, int(q_prescaled), kv_batches, qn2.data_ptr(), kn2.data_ptr(), _p(workspace),
-                                           0 if workspace is None else workspace.numel(), _stream()),
-           "osk_attention_fwd_auto_bf16")
-    if prof is not None:
-        ev1.record()
-        prof.append((ev0, ev1))
-    return out
+    return _attn_call("osk_attention_fwd_auto_bf16", q, k, vt, out, H, hd, scale, lse, n_seg, seg_len, k_seg_stride, vt_seg_stride,
+                      q_prescaled, kv_batches, workspace, own=(qn2.data_ptr(), kn2.data_ptr()))
 
 
 def attention_short(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, H: int, hd: int, scale: float,
@@ -645,23 +626,8 @@ def attention_fwd_pv8(q: torch.Tensor, k: torch.Tensor, vt8: torch.Tensor, v_sca
                       k_seg_stride: int = 0, vt_seg_stride: int = 0, q_prescaled: bool = False, kv_batches: int = 0,
                       workspace: torch.Tensor | None = None):
     """attention_fwd with the P.V product on the fp8 MFMA: vt8 / v_scale from v_transpose_fp8 (vt_seg_stride in bytes)."""
-    B, Lq, _ = q.shape
-    if seg_len is None:
-        seg_len = k.shape[1]
-    prof = PROFILE_ATTENTION
-    if prof is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    _check(lib.osk_attention_fwd_pv8_bf16(q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k_seg_stride,
-                                          k.stride(0), k.stride(1), vt8.data_ptr(), vt_seg_stride, v_scale.data_ptr(),
-                                          out.data_ptr(), out.stride(0), out.stride(1), _p(lse), B, H, Lq, n_seg,
-                                          seg_len, hd, scale, int(q_prescaled), kv_batches, _p(workspace),
-                                          0 if workspace is None else workspace.numel(), _stream()),
-           "osk_attention_fwd_pv8_bf16")
-    if prof is not None:
-        ev1.record()
-        prof.append((ev0, ev1))
-    return out
+    return _attn_call("osk_attention_fwd_pv8_bf16", q, k, vt8, out, H, hd, scale, lse, n_seg, seg_len, k_seg_stride, vt_seg_stride,
+                      q_prescaled, kv_batches, workspace, after_vt=(v_scale.data_ptr(),))
 
 
 def copy_rows_ok(src: torch.Tensor, dst: torch.Tensor) -> bool:

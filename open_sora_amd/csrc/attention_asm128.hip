@@ -203,9 +203,7 @@ template <bool FAST>
 int launch_one(const AttnParams& p, hipStream_t st) {
   auto kernel = attn_asm128_kernel<FAST>;
   OSK_ENSURE_MAX_SMEM(kernel, OSK128_SMEM);
-  const int units = ((p.Lq + 255) / 256) * p.B * p.H;
-  const int tail_units = p.tail_split > 1 ? units - p.tail_first : 0;
-  dim3 grid(units + tail_units * (p.tail_split - 1)), block(64 * NW);
+  dim3 grid(attn_grid(p)), block(64 * NW);
   hipLaunchKernelGGL(kernel, grid, block, OSK128_SMEM, st, p);
   return (int)hipGetLastError();
 }

@@ -193,9 +193,7 @@ __global__ void __launch_bounds__(256, 1) attn_asm128p8_kernel(const AttnParams 
 int launch_one(const AttnParams& p, hipStream_t st) {
   auto kernel = attn_asm128p8_kernel;
   OSK_ENSURE_MAX_SMEM(kernel, OSK128P8_SMEM);
-  const int units = ((p.Lq + 255) / 256) * p.B * p.H;
-  const int tail_units = p.tail_split > 1 ? units - p.tail_first : 0;
-  dim3 grid(units + tail_units * (p.tail_split - 1)), block(64 * NW);
+  dim3 grid(attn_grid(p)), block(64 * NW);
   hipLaunchKernelGGL(kernel, grid, block, OSK128P8_SMEM, st, p);
   return (int)hipGetLastError();
 }

@@ -250,9 +250,7 @@ template <bool FAST, int HD>
 int launch_one(const AttnParams& p, hipStream_t st) {
   auto kernel = attn_asm72_kernel<FAST, HD>;
   OSK_ENSURE_MAX_SMEM(kernel, OSK72_SMEM);
-  const int units = ((p.Lq + 255) / 256) * p.B * p.H;
-  const int tail_units = p.tail_split > 1 ? units - p.tail_first : 0;
-  dim3 grid(units + tail_units * (p.tail_split - 1)), block(256);
+  dim3 grid(attn_grid(p)), block(256);
   hipLaunchKernelGGL(kernel, grid, block, OSK72_SMEM, st, p);
   return (int)hipGetLastError();
 }

@@ -204,9 +204,7 @@ __global__ void __launch_bounds__(NU == 2 ? 256 : 512, NU == 2 ? 1 : 2) attn_asm
 int launch_one(const AttnParams& p, hipStream_t st) {
   auto kernel = attn_asm72p8_kernel<2>;
   OSK_ENSURE_MAX_SMEM(kernel, OSK72P8_SMEM);
-  const int units = ((p.Lq + 255) / 256) * p.B * p.H;
-  const int tail_units = p.tail_split > 1 ? units - p.tail_first : 0;
-  dim3 grid(units + tail_units * (p.tail_split - 1)), block(64 * 4);
+  dim3 grid(attn_grid(p)), block(64 * 4);
   hipLaunchKernelGGL(kernel, grid, block, OSK72P8_SMEM, st, p);
   return (int)hipGetLastError();
 }

@@ -5,24 +5,13 @@
 // (attn_fwd_kernel<64>, 400 lines: 8 waves x 32 rows, register-staged tiles) -- head_dim 64 now runs the head_dim-72 loop.
 //
 // Roofline: MFMA bf16.  Algorithmic FLOPs = 4 * B * H * Lq * Lk * hd (QK^T + PV, not halved).
+#include <algorithm>
 #include <atomic>
+#include <initializer_list>
 #include "attention_params.h"
 #include "../../include/osk.h"
 
-namespace {
 using osk_attn::AttnParams;
-
-// ONE kernel family per head_dim (tail units split along the keys + merge when the caller handed over a workspace)
-template <int HD>
-int launch(const AttnParams& p, hipStream_t st) {
-  int rc;
-  if constexpr (HD == 72) rc = p.rows == 512 ? osk_attn::launch_asm72w(p, st) : osk_attn::launch_asm72(p, st);
-  else if constexpr (HD == 64) rc = p.rows == 512 ? osk_attn::launch_asm64w(p, st) : osk_attn::launch_asm64(p, st);
-  else rc = osk_attn::launch_asm128(p, st);
-  return rc != 0 || p.tail_split == 1 ? rc : osk_attn::launch_merge(p, HD, st);
-}
-
-}  // namespace
 
 namespace osk_attn {
 namespace {
@@ -93,8 +82,7 @@ void split_tail(AttnParams& p, int units, int hd, void* workspace, int64_t works
 }
 
 int launch_merge(const AttnParams& p, int hd, hipStream_t st) {
-  const int units = ((p.Lq + p.rows - 1) / p.rows) * p.B * p.H;
-  dim3 grid(units - p.tail_first, p.rows / 64), block(256);
+  dim3 grid(attn_units(p) - p.tail_first, p.rows / 64), block(256);
   if (hd == 72) hipLaunchKernelGGL(attn_merge_kernel<72>, grid, block, 0, st, p);
   else if (hd == 64) hipLaunchKernelGGL(attn_merge_kernel<64>, grid, block, 0, st, p);
   else if (hd == 128) hipLaunchKernelGGL(attn_merge_kernel<128>, grid, block, 0, st, p);
@@ -107,13 +95,18 @@ int launch_merge(const AttnParams& p, int hd, hipStream_t st) {
 // reporting: (key parts, rows per work unit) the launch of a call with these arguments uses -- the SAME selection code as
 // osk_attention_fwd_bounded_bf16 below (round 4 modelled 256-row units whatever the call: ADVICE r4)
 static std::atomic<int> g_rows_override{0};   // tools only (osk_attention_rows_override): 0 = by estimate, 256 / 512 = forced where legal
-static void launch_shape(osk_attn::AttnParams& p, int hd, void* workspace, int64_t workspace_bytes) {
+static void launch_shape(AttnParams& p, int hd, void* workspace, int64_t workspace_bytes) {
   p.rows = 256;
   const int forced = g_rows_override.load(std::memory_order_relaxed);
   const bool wide_legal = (hd == 72 || hd == 64) && osk_attn::attn_fast_path(p) && p.Lq >= 1024;
   if (forced ? (forced == 512 && wide_legal) : osk_attn::attn_wide_path(p, hd, osk_device_cus(), workspace != nullptr)) p.rows = 512;
-  if (hd == 64 || hd == 72 || hd == 128)
-    osk_attn::split_tail(p, ((p.Lq + p.rows - 1) / p.rows) * p.B * p.H, hd, workspace, workspace_bytes);
+  if (hd == 64 || hd == 72 || hd == 128) osk_attn::split_tail(p, osk_attn::attn_units(p), hd, workspace, workspace_bytes);
+}
+
+static void set_segments(AttnParams& p, int n_seg, int seg_len) {
+  p.n_seg = n_seg; p.seg_len = seg_len;
+  p.seg_lp = (seg_len + 63) / 64 * 64;
+  p.tps = p.seg_lp / 64;
 }
 
 static float bound_to_bf16_up(float score_bound) {
@@ -126,10 +119,9 @@ extern "C" int osk_attention_launch_shape(int B, int H, int Lq, int n_seg, int s
                                           int64_t workspace_bytes, int* rows_per_unit) {
   if (rows_per_unit) *rows_per_unit = 256;
   if (B <= 0 || H <= 0 || Lq <= 0 || n_seg <= 0 || seg_len <= 0 || (hd != 64 && hd != 72 && hd != 128) || !(score_bound >= 0.f)) return 1;
-  osk_attn::AttnParams p{};
-  p.B = B; p.H = H; p.Lq = Lq; p.n_seg = n_seg; p.seg_len = seg_len;
-  p.seg_lp = (seg_len + 63) / 64 * 64;
-  p.tps = p.seg_lp / 64;
+  AttnParams p{};
+  p.B = B; p.H = H; p.Lq = Lq;
+  set_segments(p, n_seg, seg_len);
   p.bound = bound_to_bf16_up(score_bound);
   static char dummy[16] __attribute__((aligned(16)));
   launch_shape(p, hd, workspace_bytes > 0 ? dummy : nullptr, workspace_bytes);
@@ -164,6 +156,52 @@ extern "C" int osk_attention_fwd_bf16(const void* q, int64_t q_batch_stride, int
                                    scale, q_prescaled, kv_batches, nullptr, 0, stream);
 }
 
+// The argument checks and the AttnParams fill the three entry points share.  What differs between them is an argument: vt_stride_mask (7:
+// bf16 V^T, strides in elements; 15: the e4m3 layout of the pv8 variant, its stride in bytes) and hds, the head dims the entry point has
+// kernels for.  Status precedence: OSK_EINVAL before OSK_EUNSUPPORTED -- an entry point makes its own OSK_EINVAL checks before it calls this
+// function and its own OSK_EUNSUPPORTED checks after it, so a malformed call is reported as malformed whatever head dim it asks for.
+static int attn_params(AttnParams& p, const void* q, int64_t q_batch_stride, int64_t q_row_stride, const void* k, int64_t k_seg_stride,
+                       int64_t k_batch_stride, int64_t k_row_stride, const void* vt, int64_t vt_seg_stride, int64_t vt_stride_mask,
+                       void* out, int64_t o_batch_stride, int64_t o_row_stride, float* lse, int B, int H, int Lq, int n_seg, int seg_len,
+                       int hd, std::initializer_list<int> hds, float scale, int q_prescaled, int kv_batches, const void* workspace,
+                       int64_t workspace_bytes) {
+  if (!q || !k || !vt || !out || B <= 0 || H <= 0 || Lq <= 0 || n_seg <= 0 || seg_len <= 0) return OSK_EINVAL;
+  if ((q_batch_stride & 7) || (q_row_stride & 7) || (k_seg_stride & 7) || (k_batch_stride & 7) || (k_row_stride & 7) ||
+      (vt_seg_stride & vt_stride_mask) || (o_batch_stride & 3) || (o_row_stride & 3))
+    return OSK_EINVAL;
+  if (((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)vt & 15) || ((uintptr_t)out & 7)) return OSK_EINVAL;
+  if (kv_batches < 0 || kv_batches > B) return OSK_EINVAL;
+  if (workspace && (((uintptr_t)workspace & 15) || workspace_bytes < 0)) return OSK_EINVAL;
+  if (std::find(hds.begin(), hds.end(), hd) == hds.end()) return OSK_EUNSUPPORTED;
+  p.q = (const unsigned short*)q; p.qbs = q_batch_stride; p.qrs = q_row_stride;
+  p.k = (const unsigned short*)k; p.kss = k_seg_stride; p.kbs = k_batch_stride; p.krs = k_row_stride;
+  p.vt = (const unsigned short*)vt; p.vtss = vt_seg_stride;
+  p.out = (unsigned short*)out; p.obs = o_batch_stride; p.ors = o_row_stride;
+  p.lse = lse; p.B = B; p.H = H; p.Lq = Lq;
+  set_segments(p, n_seg, seg_len);
+  p.sc = q_prescaled ? 1.0f : scale * 1.4426950408889634f;  // log2 units; 1: q already carries it
+  p.q_prescaled = q_prescaled;
+  p.Bkv = kv_batches > 0 ? kv_batches : B;
+  p.map = 1;   // XCD-contiguous work order (each XCD walks one head's K / V^T stream)
+  return OSK_OK;
+}
+
+// ONE kernel per (head_dim, query rows per work unit); the FAST / general body is the launch function's choice (attn_fast_path)
+static int run(const AttnParams& p, int hd, hipStream_t st) {
+  const bool wide = p.rows == 512;
+  switch (hd) {
+    case 64: return wide ? osk_attn::launch_asm64w(p, st) : osk_attn::launch_asm64(p, st);
+    case 72: return wide ? osk_attn::launch_asm72w(p, st) : osk_attn::launch_asm72(p, st);
+    case 128: return osk_attn::launch_asm128(p, st);
+    default: return OSK_EUNSUPPORTED;
+  }
+}
+
+// after a launch that returned rc: combine the key parts of its split tail units (launch_shape / split_tail decided whether there are any)
+static int then_merge(int rc, const AttnParams& p, int hd, hipStream_t st) {
+  return rc != 0 || p.tail_split == 1 ? rc : osk_attn::launch_merge(p, hd, st);
+}
+
 extern "C" int osk_attention_fwd_bounded_bf16(const void* q, int64_t q_batch_stride, int64_t q_row_stride,
                                          const void* k, int64_t k_seg_stride, int64_t k_batch_stride,
                                          int64_t k_row_stride, const void* vt, int64_t vt_seg_stride,
@@ -171,35 +209,16 @@ extern "C" int osk_attention_fwd_bounded_bf16(const void* q, int64_t q_batch_str
                                          float* lse, int B, int H, int Lq, int n_seg, int seg_len, int hd,
                                          float scale, int q_prescaled, int kv_batches, float score_bound,
                                          void* workspace, int64_t workspace_bytes, void* stream) {
-  if (!q || !k || !vt || !out || B <= 0 || H <= 0 || Lq <= 0 || n_seg <= 0 || seg_len <= 0) return OSK_EINVAL;
-  if ((q_batch_stride & 7) || (q_row_stride & 7) || (k_seg_stride & 7) || (k_batch_stride & 7) ||
-      (k_row_stride & 7) || (vt_seg_stride & 7) || (o_batch_stride & 3) || (o_row_stride & 3))
-    return OSK_EINVAL;
-  if (((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)vt & 15) || ((uintptr_t)out & 7)) return OSK_EINVAL;
-  AttnParams p;
-  p.q = (const unsigned short*)q; p.qbs = q_batch_stride; p.qrs = q_row_stride;
-  p.k = (const unsigned short*)k; p.kss = k_seg_stride; p.kbs = k_batch_stride; p.krs = k_row_stride;
-  p.vt = (const unsigned short*)vt; p.vtss = vt_seg_stride;
-  p.out = (unsigned short*)out; p.obs = o_batch_stride; p.ors = o_row_stride;
-  p.lse = lse; p.B = B; p.H = H; p.Lq = Lq; p.n_seg = n_seg; p.seg_len = seg_len;
-  p.seg_lp = (seg_len + 63) / 64 * 64;
-  p.tps = p.seg_lp / 64;
-  p.sc = q_prescaled ? 1.0f : scale * 1.4426950408889634f;  // log2 units; 1: q already carries it
-  p.q_prescaled = q_prescaled;
   if (!(score_bound >= 0.f)) return OSK_EINVAL;   // (also rejects NaN)
+  AttnParams p;
+  const int rc = attn_params(p, q, q_batch_stride, q_row_stride, k, k_seg_stride, k_batch_stride, k_row_stride, vt, vt_seg_stride, 7,
+                             out, o_batch_stride, o_row_stride, lse, B, H, Lq, n_seg, seg_len, hd, {64, 72, 128}, scale, q_prescaled,
+                             kv_batches, workspace, workspace_bytes);
+  if (rc != OSK_OK) return rc;
   p.bound = bound_to_bf16_up(score_bound);
-  if (kv_batches < 0 || kv_batches > B) return OSK_EINVAL;
-  p.Bkv = kv_batches > 0 ? kv_batches : B;
-  p.map = 1;   // XCD-contiguous work order (each XCD walks one head's K / V^T stream)
-  if (workspace && (((uintptr_t)workspace & 15) || workspace_bytes < 0)) return OSK_EINVAL;
   launch_shape(p, hd, workspace, workspace_bytes);
   hipStream_t st = (hipStream_t)stream;
-  switch (hd) {
-    case 64: return launch<64>(p, st);
-    case 72: return launch<72>(p, st);
-    case 128: return launch<128>(p, st);
-    default: return OSK_EUNSUPPORTED;
-  }
+  return then_merge(run(p, hd, st), p, hd, st);
 }
 
 // ---- auto-dispatched pair (round 6): the bound comes from the operands themselves, per (batch, head), on the device
@@ -210,55 +229,31 @@ extern "C" int osk_attention_fwd_auto_bf16(const void* q, int64_t q_batch_stride
                                            float* lse, int B, int H, int Lq, int n_seg, int seg_len, int hd,
                                            float scale, int q_prescaled, int kv_batches, const float* q_norm2_max,
                                            const float* k_norm2_max, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (!q || !k || !vt || !out || !q_norm2_max || !k_norm2_max || B <= 0 || H <= 0 || Lq <= 0 || n_seg <= 0 || seg_len <= 0) return OSK_EINVAL;
-  if ((q_batch_stride & 7) || (q_row_stride & 7) || (k_seg_stride & 7) || (k_batch_stride & 7) ||
-      (k_row_stride & 7) || (vt_seg_stride & 7) || (o_batch_stride & 3) || (o_row_stride & 3))
-    return OSK_EINVAL;
-  if (((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)vt & 15) || ((uintptr_t)out & 7) ||
-      ((uintptr_t)q_norm2_max & 3) || ((uintptr_t)k_norm2_max & 3)) return OSK_EINVAL;
-  if (hd != 64 && hd != 72 && hd != 128) return OSK_EUNSUPPORTED;
-  if (!q_prescaled && scale * 1.4426950408889634f != 1.0f) return OSK_EUNSUPPORTED;   // the norms must be those of the operands the MFMA sees
+  if (!q_norm2_max || !k_norm2_max || ((uintptr_t)q_norm2_max & 3) || ((uintptr_t)k_norm2_max & 3)) return OSK_EINVAL;
   AttnParams p;
-  p.q = (const unsigned short*)q; p.qbs = q_batch_stride; p.qrs = q_row_stride;
-  p.k = (const unsigned short*)k; p.kss = k_seg_stride; p.kbs = k_batch_stride; p.krs = k_row_stride;
-  p.vt = (const unsigned short*)vt; p.vtss = vt_seg_stride;
-  p.out = (unsigned short*)out; p.obs = o_batch_stride; p.ors = o_row_stride;
-  p.lse = lse; p.B = B; p.H = H; p.Lq = Lq; p.n_seg = n_seg; p.seg_len = seg_len;
-  p.seg_lp = (seg_len + 63) / 64 * 64;
-  p.tps = p.seg_lp / 64;
+  int rc = attn_params(p, q, q_batch_stride, q_row_stride, k, k_seg_stride, k_batch_stride, k_row_stride, vt, vt_seg_stride, 7,
+                       out, o_batch_stride, o_row_stride, lse, B, H, Lq, n_seg, seg_len, hd, {64, 72, 128}, scale, q_prescaled,
+                       kv_batches, workspace, workspace_bytes);
+  if (rc != OSK_OK) return rc;
+  if (!q_prescaled && scale * 1.4426950408889634f != 1.0f) return OSK_EUNSUPPORTED;   // the norms must be those of the operands the MFMA sees
   p.sc = 1.0f;
   p.q_prescaled = 1;
-  if (kv_batches < 0 || kv_batches > B) return OSK_EINVAL;
-  p.Bkv = kv_batches > 0 ? kv_batches : B;
-  p.map = 1;
-  if (workspace && (((uintptr_t)workspace & 15) || workspace_bytes < 0)) return OSK_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   p.bound = 1.0f;                                  // "a bound exists": the FAST body's layout rules (attn_fast_path)
-  const bool fast_possible = osk_attn::attn_fast_path(p);
-  auto run = [&](const AttnParams& a) {
-    switch (hd) {
-      case 64: return a.rows == 512 ? osk_attn::launch_asm64w(a, st) : osk_attn::launch_asm64(a, st);
-      case 72: return a.rows == 512 ? osk_attn::launch_asm72w(a, st) : osk_attn::launch_asm72(a, st);
-      default: return osk_attn::launch_asm128(a, st);
-    }
-  };
-  if (!fast_possible) {                            // several key segments of fewer than 3 tiles: only the general body takes them
+  if (!osk_attn::attn_fast_path(p)) {              // several key segments of fewer than 3 tiles: only the general body takes them
     p.bound = 0.f;
     launch_shape(p, hd, workspace, workspace_bytes);
-    const int rc = run(p);
-    return rc != 0 || p.tail_split == 1 ? rc : osk_attn::launch_merge(p, hd, st);
+    return then_merge(run(p, hd, st), p, hd, st);
   }
   // the FAST twin: launch shape as a bounded call's (wide layout, tail split), every workgroup checks its own (batch, head)
   p.qn2 = q_norm2_max; p.kn2 = k_norm2_max;
   launch_shape(p, hd, workspace, workspace_bytes);
-  int rc = run(p);
+  rc = run(p, hd, st);
   if (rc != 0) return rc;
   // the general twin: 256-row units, no tail split (its units write their final rows; the merge kernel skips them)
   AttnParams g = p;
   g.bound = 0.f; g.rows = 256; g.tail_split = 1; g.tail_first = 0x7fffffff; g.ws_o = nullptr; g.ws_lse = nullptr;
-  rc = run(g);
-  if (rc != 0) return rc;
-  return p.tail_split == 1 ? OSK_OK : osk_attn::launch_merge(p, hd, st);
+  return then_merge(run(g, hd, st), p, hd, st);
 }
 
 // squared row norms of a bf16 [B, L, H * hd] view, maximum per (batch, head): out[b * H + h] = max_l sum_d x[b, l, h, d]^2  (f32).
@@ -342,13 +337,8 @@ extern "C" const char* osk_attention_kernel_name(int hd, int seg_len) {
 extern "C" const char* osk_attention_body_name(int hd, int n_seg, int seg_len, float score_bound) {
   if (hd != 64 && hd != 72 && hd != 128) return "unsupported";
   AttnParams p{};
-  p.n_seg = n_seg; p.seg_len = seg_len;
-  p.seg_lp = (seg_len + 63) / 64 * 64;
-  p.tps = p.seg_lp / 64;
-  if (score_bound > 0.f) {   // rounded up to bf16 as osk_attention_fwd_bounded_bf16 does
-    const unsigned bits = __builtin_bit_cast(unsigned, score_bound);
-    p.bound = __builtin_bit_cast(float, (bits + 0xFFFFu) & 0xFFFF0000u);
-  }
+  set_segments(p, n_seg, seg_len);
+  if (score_bound > 0.f) p.bound = bound_to_bf16_up(score_bound);   // (negative / NaN: no bound, the general body)
   const bool fast = osk_attn::attn_fast_path(p);
   if (hd == 72 || hd == 64) return fast ? "attn_asm72_kernel<FAST>" : "attn_asm72_kernel<general>";   // (Lq >= 1024: the FAST body's wide layout, attn_asm72w_kernel)
   return fast ? "attn_asm128_kernel<FAST>" : "attn_asm128_kernel<general>";
@@ -467,11 +457,6 @@ __global__ void __launch_bounds__(256) v_absmax_kernel(const unsigned short* __r
     if (smax[i]) atomicMax(&amax_bits[b * H + i], smax[i]);
 }
 
-__global__ void v_scale_zero_kernel(unsigned* __restrict__ p, int n) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) p[i] = 0u;
-}
-
 __global__ void v_scale_finalize_kernel(unsigned* __restrict__ amax_bits, int n) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
@@ -486,7 +471,7 @@ extern "C" int osk_v_scale_fp8(const void* v, int64_t bs, int64_t rs, float* sca
   if (!v || !scales || B <= 0 || L <= 0 || H <= 0 || H > 256 || (hd & 7) || (bs & 7) || (rs & 7) || ((uintptr_t)v & 15))
     return OSK_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(v_scale_zero_kernel, dim3((B * H + 255) / 256), dim3(256), 0, st, reinterpret_cast<unsigned*>(scales), B * H);   // (a kernel, not hipMemsetAsync: see osk_rownorm2_max_bf16)
+  hipLaunchKernelGGL(zero_u32_kernel, dim3((B * H + 255) / 256), dim3(256), 0, st, reinterpret_cast<unsigned*>(scales), B * H);   // (a kernel, not hipMemsetAsync: see osk_rownorm2_max_bf16)
   int rows = (L + 127) / 128;            // about 128 blocks per batch item
   if (rows < 16) rows = 16;
   dim3 grid((L + rows - 1) / rows, B), block(256);
@@ -519,28 +504,15 @@ extern "C" int osk_attention_fwd_pv8_bf16(const void* q, int64_t q_batch_stride,
                                           float* lse, int B, int H, int Lq, int n_seg, int seg_len, int hd,
                                           float scale, int q_prescaled, int kv_batches, void* workspace,
                                           int64_t workspace_bytes, void* stream) {
-  if (!q || !k || !vt8 || !v_scale || !out || B <= 0 || H <= 0 || Lq <= 0 || n_seg <= 0 || seg_len <= 0) return OSK_EINVAL;
-  if ((q_batch_stride & 7) || (q_row_stride & 7) || (k_seg_stride & 7) || (k_batch_stride & 7) ||
-      (k_row_stride & 7) || (vt8_seg_stride & 15) || (o_batch_stride & 3) || (o_row_stride & 3))
-    return OSK_EINVAL;
-  if (((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)vt8 & 15) || ((uintptr_t)out & 7)) return OSK_EINVAL;
-  if (hd != 128 && hd != 72) return OSK_EUNSUPPORTED;
-  osk_attn::AttnParams p;
-  p.q = (const unsigned short*)q; p.qbs = q_batch_stride; p.qrs = q_row_stride;
-  p.k = (const unsigned short*)k; p.kss = k_seg_stride; p.kbs = k_batch_stride; p.krs = k_row_stride;
-  p.vt = nullptr; p.vt8 = (const unsigned char*)vt8; p.vtss = vt8_seg_stride; p.v_scale = v_scale;
-  p.out = (unsigned short*)out; p.obs = o_batch_stride; p.ors = o_row_stride;
-  p.lse = lse; p.B = B; p.H = H; p.Lq = Lq; p.n_seg = n_seg; p.seg_len = seg_len;
-  p.seg_lp = (seg_len + 63) / 64 * 64;
-  p.tps = p.seg_lp / 64;
-  p.sc = q_prescaled ? 1.0f : scale * 1.4426950408889634f;
-  p.q_prescaled = q_prescaled;
-  if (kv_batches < 0 || kv_batches > B) return OSK_EINVAL;
-  p.Bkv = kv_batches > 0 ? kv_batches : B;
-  p.map = 1;   // XCD-contiguous work order (each XCD walks one head's K / V^T stream)
-  if (workspace && (((uintptr_t)workspace & 15) || workspace_bytes < 0)) return OSK_EINVAL;
-  osk_attn::split_tail(p, ((Lq + 255) / 256) * B * H, hd, workspace, workspace_bytes);
+  if (!v_scale) return OSK_EINVAL;
+  AttnParams p;
+  int rc = attn_params(p, q, q_batch_stride, q_row_stride, k, k_seg_stride, k_batch_stride, k_row_stride, vt8, vt8_seg_stride, 15,
+                       out, o_batch_stride, o_row_stride, lse, B, H, Lq, n_seg, seg_len, hd, {72, 128}, scale, q_prescaled,
+                       kv_batches, workspace, workspace_bytes);
+  if (rc != OSK_OK) return rc;
+  p.vt = nullptr; p.vt8 = (const unsigned char*)vt8; p.v_scale = v_scale;
+  osk_attn::split_tail(p, osk_attn::attn_units(p), hd, workspace, workspace_bytes);
   hipStream_t st = (hipStream_t)stream;
-  const int rc = hd == 128 ? osk_attn::launch_asm128p8(p, st) : osk_attn::launch_asm72p8(p, st);
-  return rc != 0 || p.tail_split == 1 ? rc : osk_attn::launch_merge(p, hd, st);
+  rc = hd == 128 ? osk_attn::launch_asm128p8(p, st) : osk_attn::launch_asm72p8(p, st);
+  return then_merge(rc, p, hd, st);
 }

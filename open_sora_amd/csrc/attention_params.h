@@ -134,6 +134,14 @@ OSK_DEV KeyPart key_part(const AttnParams& p, bool tail, int part, bool ragged) 
   return r;
 }
 
+// host: work units (workgroups before the tail split) of a launch, and its grid: every split tail unit takes tail_split workgroups.
+// p.rows is the geometry of the kernel that is launched: the entry points pick the kernel from it (attention_fwd.hip)
+static inline int attn_units(const AttnParams& p) { return ((p.Lq + p.rows - 1) / p.rows) * p.B * p.H; }
+static inline int attn_grid(const AttnParams& p) {
+  const int units = attn_units(p);
+  return p.tail_split > 1 ? units + (units - p.tail_first) * (p.tail_split - 1) : units;
+}
+
 // host: decide the tail split of a launch of `units` work units given the workspace (attention_fwd.hip)
 void split_tail(AttnParams& p, int units, int hd, void* workspace, int64_t workspace_bytes);
 int launch_merge(const AttnParams& p, int hd, hipStream_t st);
