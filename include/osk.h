@@ -599,6 +599,42 @@ int osk_relu_linear_attn_bf16(const void* qkv, int B, int N, int G, void* out, i
 int osk_rmsnorm_affine_bf16(const void* x, int64_t M, int C, const float* weight, const float* bias, float eps,
                             const void* res, int relu, void* out, void* stream);
 
+/* ==== CLIP-L text encoder: the three entries below replace the arithmetic inside the Hugging Face CLIPTextModel that HFEmbedder
+ * runs for `y_vec` (opensora/models/text/conditioner.py:17-20 builds it, 48-53 calls it: 77 tokens, attention_mask=None,
+ * `pooler_output`).  open_sora_amd/clip.py is their caller. */
+
+/* ---- LayerNorm over channels with affine weight and bias (nn.LayerNorm: CLIPEncoderLayer.layer_norm1 / layer_norm2 and
+ * final_layer_norm).
+ * replaces the nn.LayerNorm calls of the CLIP branch (conditioner.py:17-20, 48-53):
+ *   out[m, :] = bf16((x[m, :] - mean) * rsqrt(var + eps) * weight + bias),   var = mean((x - mean)^2)   (biased)
+ * x, out bf16 [M, C], rows x_row_stride / out_row_stride elements apart (% 8 == 0, >= C), 16-byte aligned; weight, bias f32 [C].
+ * f32 statistics over the register-resident row, the mean first and then the variance of the centred values (never
+ * E[x^2] - mean^2: a constant row comes out as bf16(bias), not NaN); one rounding.  C % 8 == 0 and C <= 4096; another C:
+ * OSK_EUNSUPPORTED, nothing launched. */
+int osk_layernorm_affine_bf16(const void* x, int64_t x_row_stride, void* out, int64_t out_row_stride, const float* weight,
+                              const float* bias, int64_t M, int C, float eps, void* stream);
+
+/* ---- causal softmax self-attention, head dim 64: the attention of the CLIP text tower.
+ * replaces CLIPAttention.forward under the causal mask of CLIPTextTransformer (conditioner.py:17-20, 48-53):
+ *   out[b, i, h] = sum_{j <= i} softmax_j(scale * q_i . k_j) v_j ,   Lq = Lk = L
+ * Operands as osk_attention_relbias_bf16 (q, k, v, out bf16 [B, L, H * hd] views with batch / row strides in elements; q | k | v may
+ * be read in place from one fused projection output; V as stored), no bias argument.  The CAUSAL instantiation of that kernel:
+ * query block qb walks key tiles 0 .. qb only (tiles above the diagonal are skipped, not masked), the diagonal tile masks j > i
+ * with -inf before the running maximum.  hd == 64 and 1 <= L <= 4096; another hd or a longer L: OSK_EUNSUPPORTED, nothing written. */
+int osk_attention_causal_bf16(const void* q, int64_t q_batch_stride, int64_t q_row_stride, const void* k, int64_t k_batch_stride,
+                              int64_t k_row_stride, const void* v, int64_t v_batch_stride, int64_t v_row_stride, void* out,
+                              int64_t o_batch_stride, int64_t o_row_stride, int B, int H, int L, int hd, float scale, void* stream);
+
+/* ---- Linear + quick-GELU: CLIPMLP.fc1 and its activation.
+ * replaces fc1 + QuickGELUActivation of the CLIP branch (conditioner.py:17-20, 48-53):
+ *   C = bf16(quick_gelu(A W^T + bias)),   quick_gelu(v) = v * sigmoid(1.702 v) = v / (1 + exp2(-1.702 log2(e) v))  in f32
+ * The arguments of osk_gemm_bf16 without res / gate / gelu_from / out_f32 (C is bf16), the same constraints (K % 64 == 0, strides,
+ * alignment).  ALWAYS the 128 x 128 tile kernel, whatever M: at large M it runs at about half the rate of the 256-row tiles
+ * osk_gemm_bf16 would pick.  CLIP never has large M (3 x 77 rows); the large-tile epilogues know no quick-GELU. */
+int osk_gemm_quickgelu_bf16(const void* A, int64_t a_batch_stride, int64_t a_row_stride, int a_rows_per_batch, const void* W,
+                            int64_t w_row_stride, const float* bias, void* C, int64_t c_batch_stride, int64_t c_row_stride,
+                            int c_rows_per_batch, int M, int N, int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

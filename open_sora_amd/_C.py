@@ -89,6 +89,9 @@ SIGNATURES = {
     "osk_gconv32_bf16": [_vp, _i64, _i32, _vp, _vp, _vp],
     "osk_relu_linear_attn_bf16": [_vp, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _f32, _vp],
     "osk_rmsnorm_affine_bf16": [_vp, _i64, _i32, _vp, _vp, _f32, _vp, _i32, _vp, _vp],
+    "osk_layernorm_affine_bf16": [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _f32, _vp],
+    "osk_attention_causal_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _f32, _vp],
+    "osk_gemm_quickgelu_bf16": [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp],
 }
 
 
@@ -987,4 +990,56 @@ def rmsnorm_affine(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, ou
     assert res is None or (res.is_contiguous() and res.shape == x.shape and res.dtype == torch.bfloat16)
     _check(lib.osk_rmsnorm_affine_bf16(x.data_ptr(), x.numel() // C, C, weight.data_ptr(), bias.data_ptr(), eps, _p(res), int(relu),
                                        out.data_ptr(), _stream()), "osk_rmsnorm_affine_bf16")
+    return out
+
+
+# ----------------------------------------------------------------------------------------------
+# CLIP text encoder kernels
+# ----------------------------------------------------------------------------------------------
+def _rows_of(t: torch.Tensor):
+    """(rows, row stride) of a [..., C] view whose leading axes collapse into equally spaced rows"""
+    assert t.dim() >= 2 and t.stride(-1) == 1, (t.shape, t.stride())
+    rs = t.stride(-2)
+    for d in range(t.dim() - 2):
+        assert t.shape[d] == 1 or t.stride(d) == t.stride(d + 1) * t.shape[d + 1], f"rows are not equally spaced: {t.shape} {t.stride()}"
+    return t.numel() // t.shape[-1], rs
+
+
+def layernorm_affine(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, out: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
+    """out = bf16((x - mean) * rsqrt(var + eps) * weight + bias) over the last axis (osk_layernorm_affine_bf16); x, out bf16 [..., C]
+    views with contiguous last dim and equally spaced rows (a row stride >= C on either side); weight, bias f32 [C]."""
+    C = x.shape[-1]
+    assert out.shape == x.shape and x.dtype == out.dtype == torch.bfloat16, (x.shape, out.shape, x.dtype, out.dtype)
+    assert weight.dtype == bias.dtype == torch.float32 and weight.numel() == bias.numel() == C and weight.is_contiguous() and bias.is_contiguous()
+    (M, xrs), (_, ors) = _rows_of(x), _rows_of(out)
+    _check(lib.osk_layernorm_affine_bf16(x.data_ptr(), xrs, out.data_ptr(), ors, weight.data_ptr(), bias.data_ptr(), M, C, eps, _stream()),
+           "osk_layernorm_affine_bf16")
+    return out
+
+
+def attention_causal(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, H: int, hd: int, scale: float) -> torch.Tensor:
+    """softmax over j <= i of scale q k^T, times v: the CLIP text self-attention (osk_attention_causal_bf16); q, k, v, out bf16
+    [B, L, H*hd] views with contiguous last dim (q, k, v may be column groups of one fused projection output)."""
+    B, L, C = q.shape
+    assert C == H * hd and k.shape == q.shape and v.shape == q.shape and out.shape == q.shape, (q.shape, k.shape, v.shape, out.shape)
+    assert q.dtype == k.dtype == v.dtype == out.dtype == torch.bfloat16, (q.dtype, k.dtype, v.dtype, out.dtype)
+    for t in (q, k, v):
+        assert t.stride(2) == 1 and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0 and t.data_ptr() % 16 == 0, (t.stride(), t.data_ptr() % 16)
+    assert out.stride(2) == 1 and out.stride(0) % 4 == 0 and out.stride(1) % 4 == 0 and out.data_ptr() % 8 == 0, out.stride()
+    _check(lib.osk_attention_causal_bf16(q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1), v.data_ptr(),
+                                         v.stride(0), v.stride(1), out.data_ptr(), out.stride(0), out.stride(1), B, H, L, hd, scale,
+                                         _stream()), "osk_attention_causal_bf16")
+    return out
+
+
+def gemm_quickgelu(a: torch.Tensor, w: torch.Tensor, bias, out: torch.Tensor) -> torch.Tensor:
+    """out = bf16(quick_gelu(a w^T + bias)), quick_gelu(v) = v * sigmoid(1.702 v) (osk_gemm_quickgelu_bf16); a bf16 [B, L, K] view,
+    w bf16 [N, K], bias f32 [N] | None, out bf16 [B, L, N] view -- gemm()'s operands without an epilogue choice."""
+    B, L, K = a.shape
+    N = w.shape[0]
+    assert out.shape[0] == B and out.shape[1] == L and out.shape[2] == N and w.shape[1] == K
+    assert a.dtype == w.dtype == out.dtype == torch.bfloat16, (a.dtype, w.dtype, out.dtype)
+    with _gemm_prof(2.0 * B * L * N * K):
+        _check(lib.osk_gemm_quickgelu_bf16(a.data_ptr(), a.stride(0), a.stride(1), L, w.data_ptr(), w.stride(0), _p(bias), out.data_ptr(),
+                                           out.stride(0), out.stride(1), L, B * L, N, K, _stream()), "osk_gemm_quickgelu_bf16")
     return out

@@ -20,6 +20,11 @@
 //   * Online softmax in f32; the bias is added before the running maximum (it is learned and unbounded: no bounded body).  Keys
 //     >= L are masked with -inf before the maximum, their V rows are zero in LDS; query rows >= L are computed on a clamped row
 //     and never stored.
+//
+// CAUSAL instantiation (osk_attention_causal_bf16: CLIP's text tower, conditioner.py:17-20, 48-53): no bias, out[b, i, h] sums over
+// j <= i.  Query block qb walks the key tiles 0 .. qb only -- the tiles wholly above the diagonal are skipped, not masked -- and
+// the diagonal tile (k0 == q0) masks j > i with -inf before the running maximum; key k0 <= i is visible to every row of every tile
+// walked, so the maximum stays finite.  Staging, LDS layout and the MFMA layout are the ones above.
 #include "../../include/osk.h"
 #include "osk_common.h"
 
@@ -40,6 +45,7 @@ constexpr int RB_T = 64;            // query rows per workgroup == keys per tile
 constexpr int LDS_STRIDE = 72;      // bf16 elements per LDS row (64 + 8)
 constexpr float LOG2E = 1.4426950408889634f;
 
+template <bool CAUSAL>
 __global__ void __launch_bounds__(256) attn_relbias_kernel(const RelBiasParams p) {
   __shared__ __attribute__((aligned(16))) unsigned short ks[RB_T * LDS_STRIDE];    // K tile: row = key, 64 dims
   __shared__ __attribute__((aligned(16))) unsigned short vt[RB_HD * LDS_STRIDE];   // V^T tile: row = dim, 64 keys
@@ -78,8 +84,10 @@ __global__ void __launch_bounds__(256) attn_relbias_kernel(const RelBiasParams p
       kr[r] = kk < L ? *reinterpret_cast<const uint4*>(kg + (int64_t)kk * p.krs + kc * 8) : make_uint4(0, 0, 0, 0);
       vr[r] = vk < L ? *reinterpret_cast<const uint4*>(vg + (int64_t)vk * p.vrs + (vc0 + 4 * r) * 8) : make_uint4(0, 0, 0, 0);
     }
-    const int idx = k0 - q0 - (RB_T - 1) + (L - 1) + tid;               // distance index of sb[tid]
-    br = (bg && tid < 2 * RB_T - 1 && idx >= 0 && idx <= 2 * L - 2) ? bg[idx] * LOG2E : 0.f;
+    if constexpr (!CAUSAL) {
+      const int idx = k0 - q0 - (RB_T - 1) + (L - 1) + tid;             // distance index of sb[tid]
+      br = (bg && tid < 2 * RB_T - 1 && idx >= 0 && idx <= 2 * L - 2) ? bg[idx] * LOG2E : 0.f;
+    }
   };
   auto stage = [&]() {
 #pragma unroll
@@ -92,7 +100,8 @@ __global__ void __launch_bounds__(256) attn_relbias_kernel(const RelBiasParams p
       col[4 * LDS_STRIDE] = (unsigned short)(u.z & 0xFFFF); col[5 * LDS_STRIDE] = (unsigned short)(u.z >> 16);
       col[6 * LDS_STRIDE] = (unsigned short)(u.w & 0xFFFF); col[7 * LDS_STRIDE] = (unsigned short)(u.w >> 16);
     }
-    if (tid < 128) sb[tid] = br;
+    if constexpr (!CAUSAL)
+      if (tid < 128) sb[tid] = br;
   };
 
   f32x4_t o[4];                     // O^T: dims 16 db + 4 g .. + 3 of query il
@@ -100,7 +109,7 @@ __global__ void __launch_bounds__(256) attn_relbias_kernel(const RelBiasParams p
   for (int db = 0; db < 4; ++db) o[db] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   float m = -INFINITY, lsum = 0.f;  // running maximum (log2 units, whole row) and this lane's share of the denominator
 
-  const int nkt = (L + RB_T - 1) / RB_T;
+  const int nkt = CAUSAL ? qb + 1 : (L + RB_T - 1) / RB_T;   // causal: the tiles above the diagonal are not walked
   fetch(0);
   for (int t = 0; t < nkt; ++t) {
     const int k0 = t * RB_T;
@@ -122,15 +131,21 @@ __global__ void __launch_bounds__(256) attn_relbias_kernel(const RelBiasParams p
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int jl = kb * 16 + 4 * g + i;
-        float x = __builtin_fmaf(s[kb][i], p.sc, sb[jl - il + (RB_T - 1)]);
-        x = k0 + jl < L ? x : -INFINITY;
+        float x;
+        if constexpr (CAUSAL) {
+          x = s[kb][i] * p.sc;
+          x = (k0 + jl < L && k0 + jl <= q0 + il) ? x : -INFINITY;     // only the diagonal tile has j > i
+        } else {
+          x = __builtin_fmaf(s[kb][i], p.sc, sb[jl - il + (RB_T - 1)]);
+          x = k0 + jl < L ? x : -INFINITY;
+        }
         s[kb][i] = x;
         mt = fmaxf(mt, x);
       }
     }
     mt = fmaxf(mt, __shfl_xor(mt, 16, 64));
     mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-    const float mn = fmaxf(m, mt);                         // finite: key k0 < L is in every tile
+    const float mn = fmaxf(m, mt);                         // finite: key k0 < L (causal: k0 <= q0 too) is in every tile
     const float alpha = __builtin_amdgcn_exp2f(m - mn);    // first tile: 2^(-inf) = 0
     m = mn;
     float psum = 0.f;
@@ -178,11 +193,12 @@ __global__ void __launch_bounds__(256) attn_relbias_kernel(const RelBiasParams p
 
 }  // namespace
 
-extern "C" int osk_attention_relbias_bf16(const void* q, int64_t q_batch_stride, int64_t q_row_stride, const void* k,
-                                          int64_t k_batch_stride, int64_t k_row_stride, const void* v, int64_t v_batch_stride,
-                                          int64_t v_row_stride, void* out, int64_t o_batch_stride, int64_t o_row_stride,
-                                          const float* bias, int64_t bias_row_stride, int B, int H, int L, int hd, float scale,
-                                          void* stream) {
+// argument checks shared by the two entry points + the launch of one instantiation
+template <bool CAUSAL>
+static int launch_relbias(const void* q, int64_t q_batch_stride, int64_t q_row_stride, const void* k, int64_t k_batch_stride,
+                          int64_t k_row_stride, const void* v, int64_t v_batch_stride, int64_t v_row_stride, void* out,
+                          int64_t o_batch_stride, int64_t o_row_stride, const float* bias, int64_t bias_row_stride, int B, int H, int L,
+                          int hd, float scale, void* stream) {
   if (!q || !k || !v || !out || B <= 0 || H <= 0 || L <= 0) return OSK_EINVAL;
   if (hd != RB_HD || L > 4096) return OSK_EUNSUPPORTED;
   if ((q_batch_stride & 7) || (q_row_stride & 7) || (k_batch_stride & 7) || (k_row_stride & 7) || (v_batch_stride & 7) ||
@@ -196,6 +212,23 @@ extern "C" int osk_attention_relbias_bf16(const void* q, int64_t q_batch_stride,
   RelBiasParams p{(const unsigned short*)q, q_batch_stride, q_row_stride, (const unsigned short*)k, k_batch_stride, k_row_stride,
                   (const unsigned short*)v, v_batch_stride, v_row_stride, (unsigned short*)out, o_batch_stride, o_row_stride,
                   bias, bias_row_stride, B, H, L, nqb, scale * LOG2E};
-  hipLaunchKernelGGL(attn_relbias_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(attn_relbias_kernel<CAUSAL>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
   return (int)hipGetLastError();
+}
+
+extern "C" int osk_attention_relbias_bf16(const void* q, int64_t q_batch_stride, int64_t q_row_stride, const void* k,
+                                          int64_t k_batch_stride, int64_t k_row_stride, const void* v, int64_t v_batch_stride,
+                                          int64_t v_row_stride, void* out, int64_t o_batch_stride, int64_t o_row_stride,
+                                          const float* bias, int64_t bias_row_stride, int B, int H, int L, int hd, float scale,
+                                          void* stream) {
+  return launch_relbias<false>(q, q_batch_stride, q_row_stride, k, k_batch_stride, k_row_stride, v, v_batch_stride, v_row_stride, out,
+                               o_batch_stride, o_row_stride, bias, bias_row_stride, B, H, L, hd, scale, stream);
+}
+
+extern "C" int osk_attention_causal_bf16(const void* q, int64_t q_batch_stride, int64_t q_row_stride, const void* k,
+                                         int64_t k_batch_stride, int64_t k_row_stride, const void* v, int64_t v_batch_stride,
+                                         int64_t v_row_stride, void* out, int64_t o_batch_stride, int64_t o_row_stride, int B, int H,
+                                         int L, int hd, float scale, void* stream) {
+  return launch_relbias<true>(q, q_batch_stride, q_row_stride, k, k_batch_stride, k_row_stride, v, v_batch_stride, v_row_stride, out,
+                              o_batch_stride, o_row_stride, nullptr, 0, B, H, L, hd, scale, stream);
 }

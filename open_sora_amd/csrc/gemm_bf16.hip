@@ -21,7 +21,11 @@ struct GemmASrc {
   __device__ __forceinline__ const unsigned short* operator()(const Lane&, int i, int kt) const { return ga[i] + kt * BK; }
 };
 
-template <bool OUT_F32>
+// ACT: the activation of the epilogue.  ACT_GELU_FROM: tanh-GELU on the columns >= gelu_from (every osk_gemm_bf16 launch);
+// ACT_QUICK_GELU: x * sigmoid(1.702 x) on every column (osk_gemm_quickgelu_bf16: CLIP's fc1)
+constexpr int ACT_GELU_FROM = 0, ACT_QUICK_GELU = 1;
+
+template <bool OUT_F32, int ACT = ACT_GELU_FROM>
 __global__ void __launch_bounds__(256, 2) gemm_bf16_kernel(const GemmParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const Lane g = make_lane(p.M, p.N, p.W, p.wrs);
@@ -62,8 +66,10 @@ __global__ void __launch_bounds__(256, 2) gemm_bf16_kernel(const GemmParams p) {
             v[0] += bv.x; v[1] += bv.y; v[2] += bv.z; v[3] += bv.w;
           }
 #pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (n + j >= p.gelu_from) v[j] = gelu_tanh(v[j]);
+          for (int j = 0; j < 4; ++j) {
+            if constexpr (ACT == ACT_QUICK_GELU) v[j] = quick_gelu(v[j]);
+            else if (n + j >= p.gelu_from) v[j] = gelu_tanh(v[j]);
+          }
           if (grow) {
             const float4 gv = *reinterpret_cast<const float4*>(grow + n);
             const uint2 rv = *reinterpret_cast<const uint2*>(p.res + roff + n);
@@ -83,7 +89,8 @@ __global__ void __launch_bounds__(256, 2) gemm_bf16_kernel(const GemmParams p) {
         } else {
           for (int j = 0; j < 4 && n + j < p.N; ++j) {
             float t = v[j] + (p.bias ? p.bias[n + j] : 0.f);
-            if (n + j >= p.gelu_from) t = gelu_tanh(t);
+            if constexpr (ACT == ACT_QUICK_GELU) t = quick_gelu(t);
+            else if (n + j >= p.gelu_from) t = gelu_tanh(t);
             if (grow) t = bf16_bits_to_f32(p.res[roff + n + j]) + grow[n + j] * t;
             if constexpr (OUT_F32) reinterpret_cast<float*>(p.C)[roff + n + j] = t;
             else reinterpret_cast<unsigned short*>(p.C)[roff + n + j] = f32_to_bf16_bits(t);
@@ -263,6 +270,21 @@ extern "C" int osk_gemm_bf16(const void* A, int64_t a_batch_stride, int64_t a_ro
   dim3 grid(nblk), block(256);
   if (out_f32) hipLaunchKernelGGL((gemm_bf16_kernel<true>), grid, block, SMEM_BYTES, st, p);
   else hipLaunchKernelGGL((gemm_bf16_kernel<false>), grid, block, SMEM_BYTES, st, p);
+  return (int)hipGetLastError();
+}
+
+// ---- Linear + quick-GELU (CLIP's fc1).  Always the 128 x 128 tile kernel above: the text tower's M is a few hundred rows at most,
+// where the large tiles would not fill the chip either, and their epilogues stay as they are.
+extern "C" int osk_gemm_quickgelu_bf16(const void* A, int64_t a_batch_stride, int64_t a_row_stride, int a_rows_per_batch, const void* W,
+                                       int64_t w_row_stride, const float* bias, void* C, int64_t c_batch_stride, int64_t c_row_stride,
+                                       int c_rows_per_batch, int M, int N, int K, void* stream) {
+  GemmParams p;
+  const int rc = fill_params(p, A, a_batch_stride, a_row_stride, a_rows_per_batch, W, w_row_stride, bias, C, c_batch_stride,
+                             c_row_stride, c_rows_per_batch, nullptr, nullptr, 0, M, N, K, N, 0);
+  if (rc != OSK_OK) return rc;
+  const int64_t nblk = (int64_t)((M + BM - 1) / BM) * ((N + BN - 1) / BN);
+  if (nblk > 0x7FFFFFFF) return OSK_EUNSUPPORTED;
+  hipLaunchKernelGGL((gemm_bf16_kernel<false, ACT_QUICK_GELU>), dim3((unsigned)nblk), dim3(256), SMEM_BYTES, (hipStream_t)stream, p);
   return (int)hipGetLastError();
 }
 

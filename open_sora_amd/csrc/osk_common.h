@@ -70,6 +70,8 @@ OSK_DEV float gelu_tanh(float x) {
   const float e = __builtin_amdgcn_exp2f(x * __builtin_fmaf(0.044715f * K0, x * x, K0));
   return x * __builtin_amdgcn_rcpf(1.0f + e);
 }
+// quick-GELU (CLIP): x * sigmoid(1.702 x) == x / (1 + 2^(-1.702 log2(e) x)); the limits are gelu_tanh's
+OSK_DEV float quick_gelu(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * (-1.702f * 1.4426950408889634f))); }
 OSK_DEV float silu(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f)); }
 
 // 4 x 4 transpose of (register, lane-of-a-quad): X[r] of lane j -> X[j] of lane r, within every quad of lanes; two DPP butterfly
