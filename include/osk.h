@@ -66,6 +66,12 @@ int osk_gemm_bf16(const void* A, int64_t a_batch_stride, int64_t a_row_stride, i
  * never set in production code). */
 int osk_gemm_tile_choice(int M, int N, int K);
 int osk_gemm_tile_override(int tile_kind);
+/* ... and the kernel osk_gemm_bf16 launches for operands with THESE strides (elements), from the dispatch's own code: the estimate's
+ * choice where the large tiles take the operands, 0 otherwise.  The large tiles address every tile relative to its own origin: what
+ * has to fit their 32-bit lane offsets is each 256-row window of A and of W (2^32 - 1 bytes from the window's lowest row, a batch
+ * jump inside the window included) -- not the operand, which may span more than 4 GiB.  < 0: invalid arguments. */
+int osk_gemm_tile_choice_strided(int M, int N, int K, int64_t a_batch_stride, int64_t a_row_stride, int a_rows_per_batch,
+                                 int64_t w_row_stride);
 
 /* ---- TWO Linear layers that differ only in their operands and row count in ONE launch.
  * replaces the img-stream / txt-stream pairs of DoubleStreamBlockProcessor (layers.py:209-215 img_attn.qkv | txt_attn.qkv,
@@ -101,7 +107,8 @@ int osk_gemm_bf16_pair(const OskGemmOperands* first, const OskGemmOperands* seco
  *   and ONE rounding (the bias is added after the K loop instead of initialising the accumulators: results may differ from the
  *   two-kernel path in the last bf16 bit).  A stream stored behind another one on the key axis (img behind txt) passes
  *   C + its first position (a multiple of 64).
- * All tasks must qualify for the 256 x 256 tile kernel (M >= 256, N >= 128 (V^T: H * hd >= 256), operands within 4 GiB):
+ * All tasks must qualify for the 256 x 256 tile kernel (M >= 256, N >= 128 (V^T: H * hd >= 256), every 256-row window of the
+ * operands within 2^32 - 1 bytes of its own origin -- osk_gemm_tile_choice_strided; the operands may span more than 4 GiB):
  * otherwise OSK_EUNSUPPORTED is returned and NOTHING is launched (the caller runs the single calls). */
 typedef struct OskGemmTask {
   OskGemmOperands op;
@@ -135,7 +142,8 @@ int osk_gemm_geglu_bf16(const void* A, int64_t a_batch_stride, int64_t a_row_str
  *   out8 is contiguous [M, K] bytes.  K % 8 == 0.  Also used once per weight matrix at load time.
  * osk_gemm_fp8: C = epilogue(a_scale[m] * w_scale[n] * (A8 @ W8^T) + bias), the epilogue of osk_gemm_bf16, on
  *   v_mfma_f32_32x32x64_f8f6f4 (f32 accumulate).  Strides of A8 / W8 in bytes, multiples of 16; K % 128 == 0,
- *   M >= 256, N >= 128 (returns OSK_EUNSUPPORTED (-2) otherwise: such layers stay on osk_gemm_bf16). */
+ *   M >= 256, N >= 128, every 256-row window of A8 / W8 within 2^32 - 1 bytes of its own origin (the operands may span more than
+ *   4 GiB); returns OSK_EUNSUPPORTED (-2) otherwise: such layers stay on osk_gemm_bf16. */
 /* osk_ln_modulate_fp8: osk_ln_modulate_bf16 followed by osk_quantize_rows_fp8 in one pass (bit-identical to the pair:
  * the modulated row is rounded to bf16 first): out8 = e4m3 bytes [B*L, D] contiguous, scales f32 [B*L]. */
 int osk_ln_modulate_fp8(const void* x, int64_t x_batch_stride, int64_t x_row_stride, void* out8, float* scales,

@@ -33,6 +33,7 @@ SIGNATURES = {
     "osk_gemm_bf16_pair": [_vp, _vp, _i32, _i32, _i32, _vp],     # two OskGemmOperands structs by pointer
     "osk_gemm_group_bf16": [_vp, _i32, _i32, _vp],              # OskGemmTask array by pointer
     "osk_gemm_tile_choice": [_i32, _i32, _i32],
+    "osk_gemm_tile_choice_strided": [_i32, _i32, _i32, _i64, _i64, _i32, _i64],
     "osk_gemm_tile_override": [_i32],
     "osk_ln_modulate_fp8": [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _vp],
     "osk_quantize_rows_fp8": [_vp, _i64, _i64, _i32, _vp, _vp, _i32, _i32, _vp],
@@ -236,6 +237,16 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias, out: torch.Tensor, *, res=None,
     return out
 
 
+def gemm_tile_kind(a: torch.Tensor, w: torch.Tensor) -> int:
+    """the tile kernel gemm(a, w, ...) launches for these operands (osk_gemm_tile_choice_strided: the dispatch's own code, nothing is
+    launched): 2 = 256 x 256, 1 = 256 x 128, 0 = 128 x 128.  a bf16 [B, L, K] view, w bf16 [N, K]; the views may span more than 4 GiB."""
+    B, L, K = a.shape
+    kind = lib.osk_gemm_tile_choice_strided(B * L, w.shape[0], K, a.stride(0), a.stride(1), L, w.stride(0))
+    if kind < 0:
+        _check(kind, "osk_gemm_tile_choice_strided")
+    return kind
+
+
 def geglu_pack(w_value: torch.Tensor, w_gate: torch.Tensor, b_value=None, b_gate=None):
     """Weights of a GEGLU up-projection in the row order osk_gemm_geglu_bf16 wants: value and gate rows interleaved in blocks of 16
     (include/osk.h).  w_* [N_out, K] -> [2 N_out, K]; biases f32 [N_out] -> [2 N_out] (or None).  Done once, at plan time."""
@@ -365,9 +376,10 @@ def quantize_rows_fp8(x: torch.Tensor, out8: torch.Tensor | None = None, scales:
 
 def gemm_fp8_supported(M: int, N: int, K: int) -> bool:
     """shapes the fp8 instantiation of the large-tile kernel takes (include/osk.h); others stay on gemm().
-    Mirrors gemm256_fp8_supported (csrc/gemm256.hip): the kernel's 32-bit per-lane source offsets need both the
-    (contiguous, as the host passes them) activation and weight images to span < 4 GiB."""
-    return M >= 256 and N >= 128 and K % 128 == 0 and M * K < 0xFFFFFFFF and N * K < 0xFFFFFFFF
+    Mirrors gemm256_fp8_supported (csrc/gemm256.hip) for the contiguous images the host passes: the kernel addresses every tile
+    relative to its own origin, so what has to fit its 32-bit per-lane offsets is a 256-row window (256 K bytes), not the image --
+    M * K and N * K may exceed 4 GiB."""
+    return M >= 256 and N >= 128 and K % 128 == 0 and 256 * K <= 0xFFFFFFFF
 
 
 def gemm_fp8(a8: torch.Tensor, a_scale: torch.Tensor, w8: torch.Tensor, w_scale: torch.Tensor, bias,

@@ -174,14 +174,16 @@ __global__ void __launch_bounds__(512, 2) gemm256_kernel(const GemmParams p) {
   const osk_tile256::TileBlock t = osk_tile256::grouped_tile(xcd_remap(blockIdx.x, nbm * nbn), nbm, nbn, p.group > 0 ? p.group : 1);
   const int m0 = t.bm * 256, n0 = t.bn * BN;
 
-  // ---- LDS-DMA sources (tile256.h): 8 waves; byte offsets from the tensor base
+  // ---- LDS-DMA sources (tile256.h): 8 waves; byte offsets from the TILE's origins (the addressing rule of tile256.h)
+  const int64_t alo = osk_tile256::tile_window(m0, p.M, p.arpb, 0x7fffffff, p.abs_, p.ars).lo;
+  const int64_t wlo = osk_tile256::row_window(n0, n0 + BN - 1 < p.N ? n0 + BN - 1 : p.N - 1, 0x7fffffff, 0x7fffffff, 0, p.wrs).lo;
   unsigned aoff[4], woff[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int r = osk_tile256::dma_row<8>(wave, lane, i);
     const int c = osk_tile256::dma_chunk(lane, r);
-    aoff[i] = (unsigned)(osk_tile256::a_row_offset(p, m0 + r) * ES + c * 16);
-    woff[i] = (unsigned)(osk_tile256::w_row_offset(p, n0 + (r < BN ? r : 0)) * ES + c * 16);
+    aoff[i] = (unsigned)((osk_tile256::a_row_offset(p, m0 + r) - alo) * ES + c * 16);
+    woff[i] = (unsigned)((osk_tile256::w_row_offset(p, n0 + (r < BN ? r : 0)) - wlo) * ES + c * 16);
   }
   const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
   const int sw = (l31 >> 1) & 7;
@@ -192,7 +194,7 @@ __global__ void __launch_bounds__(512, 2) gemm256_kernel(const GemmParams p) {
     faA[ks] = lds_base + (wm * TM * 32 + l31) * 128 + sz;
     faW[ks] = lds_base + W_BASE + (wn * TN * 32 + l31) * 128 + sz;
   }
-  const uint64_t abase = rfl64((uint64_t)(uintptr_t)p.A), wbase = rfl64((uint64_t)(uintptr_t)p.W);
+  const uint64_t abase = rfl64((uint64_t)(uintptr_t)p.A + (uint64_t)(alo * ES)), wbase = rfl64((uint64_t)(uintptr_t)p.W + (uint64_t)(wlo * ES));
   const unsigned nk = rfl((unsigned)(p.K / (128 / ES)));
   const unsigned adst = rfl(lds_base + wave * 1024), wdst = rfl(lds_base + W_BASE + wave * 1024);
 
@@ -236,17 +238,18 @@ int launch_one(const GemmParams& p, hipStream_t st) {
 
 }  // namespace
 
-// the 32-bit per-lane source offsets require both operand tensors to span < 4 GiB from their base pointers
-bool gemm256_supported(const GemmParams& p, int64_t a_span_elems, int64_t w_span_elems) {
-  return p.K % 64 == 0 && p.M >= 256 && p.N >= 128 && a_span_elems * 2 < (int64_t)0xFFFFFFFF &&
-         w_span_elems * 2 < (int64_t)0xFFFFFFFF;
+// The support condition of every 256-row tile kernel (tile256.h, the addressing rule): every 256-row window of the kernel's A operand
+// and of its W operand -- a V^T task's activations with their batches and clamped keys included -- lies within 2^32 - 1 bytes of its
+// own origin.  The operands themselves may span more than 4 GiB.  (Stated for 256 rows also where a kernel's W tile has 128.)
+static bool tile_windows_fit(const GemmParams& p, int es) {
+  return p.arpb > 0 && p.wrpb > 0 && osk_tile256::windows_fit(p.M, p.arpb, 0x7fffffff, p.abs_, p.ars, p.K, es) &&
+         osk_tile256::windows_fit(p.N, p.wrpb, p.wvalid, p.wbs, p.wrs, p.K, es);
 }
 
-// fp8 operands (1 byte per element: spans in bytes), K % 128 == 0, per-row scales p.sa / p.sw
-bool gemm256_fp8_supported(const GemmParams& p, int64_t a_span_elems, int64_t w_span_elems) {
-  return p.K % 128 == 0 && p.M >= 256 && p.N >= 128 && a_span_elems < (int64_t)0xFFFFFFFF &&
-         w_span_elems < (int64_t)0xFFFFFFFF;
-}
+bool gemm256_supported(const GemmParams& p) { return p.K % 64 == 0 && p.M >= 256 && p.N >= 128 && tile_windows_fit(p, 2); }
+
+// fp8 operands (1 byte per element: strides in bytes), K % 128 == 0, per-row scales p.sa / p.sw
+bool gemm256_fp8_supported(const GemmParams& p) { return p.K % 128 == 0 && p.M >= 256 && p.N >= 128 && tile_windows_fit(p, 1); }
 
 int launch_gemm256_fp8(const GemmParams& p, int bn, int out_f32, hipStream_t st) {
   if (bn == 256) return out_f32 ? launch_one<256, true, true>(p, st) : launch_one<256, false, true>(p, st);

@@ -66,21 +66,25 @@ __global__ void __launch_bounds__(512, 2) gemm256p_kernel(const GemmParams p) {
     m0 = t.bm * 256;
     n0 = t.bn * BN;
   };
-  // LDS-DMA sources (tile256.h): 8 waves; byte offsets from the tensor bases
-  auto offsets = [&](int m0, int n0, unsigned* aoff, unsigned* woff) {
+  // LDS-DMA sources (tile256.h): 8 waves; byte offsets from the TILE's origins, which become the K loop's 64-bit bases (the
+  // addressing rule of tile256.h: one tile's window has to fit 32 bits, not the operand)
+  auto offsets = [&](int m0, int n0, unsigned* aoff, unsigned* woff, uint64_t& abase, uint64_t& wbase) {
+    const int64_t alo = osk_tile256::tile_window(m0, p.M, p.arpb, 0x7fffffff, p.abs_, p.ars).lo;
+    const int64_t wlo = osk_tile256::row_window(n0, n0 + BN - 1 < p.N ? n0 + BN - 1 : p.N - 1, 0x7fffffff, 0x7fffffff, 0, p.wrs).lo;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int r = osk_tile256::dma_row<8>(wave, lane, i);
       const int c = osk_tile256::dma_chunk(lane, r);
-      aoff[i] = (unsigned)(osk_tile256::a_row_offset(p, m0 + r) * 2 + c * 16);
-      woff[i] = (unsigned)(osk_tile256::w_row_offset(p, n0 + (r < BN ? r : 0)) * 2 + c * 16);
+      aoff[i] = (unsigned)((osk_tile256::a_row_offset(p, m0 + r) - alo) * 2 + c * 16);
+      woff[i] = (unsigned)((osk_tile256::w_row_offset(p, n0 + (r < BN ? r : 0)) - wlo) * 2 + c * 16);
     }
+    abase = rfl64((uint64_t)(uintptr_t)p.A + (uint64_t)(alo * 2));
+    wbase = rfl64((uint64_t)(uintptr_t)p.W + (uint64_t)(wlo * 2));
   };
   const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
   const unsigned sz0 = (unsigned)((hi ^ ((l31 >> 1) & 7)) << 4);   // k-sub-step ks: ^ (ks << 5) inside the asm
   const unsigned faA0 = lds_base + (wm * TM * 32 + l31) * 128 + sz0;
   const unsigned faW0 = lds_base + W_BASE + (wn * TN * 32 + l31) * 128 + sz0;
-  const uint64_t abase = rfl64((uint64_t)(uintptr_t)p.A), wbase = rfl64((uint64_t)(uintptr_t)p.W);
   const uint64_t bbase = rfl64((uint64_t)(uintptr_t)p.bias);
   const unsigned nk = rfl((unsigned)(p.K / 64));
   const unsigned adst = rfl(lds_base + wave * 1024), wdst = rfl(lds_base + W_BASE + wave * 1024);
@@ -96,8 +100,9 @@ __global__ void __launch_bounds__(512, 2) gemm256p_kernel(const GemmParams p) {
     tile_of(it, m0, n0);
     tile_of(has_next ? itn : it, m0n, n0n);
     unsigned aoff[4], woff[4], aoffn[4], woffn[4];
-    offsets(m0, n0, aoff, woff);
-    offsets(m0n, n0n, aoffn, woffn);
+    uint64_t abase, wbase, abasen, wbasen;
+    offsets(m0, n0, aoff, woff, abase, wbase);
+    offsets(m0n, n0n, aoffn, woffn, abasen, wbasen);
     const int m0w = m0 + wm * TM * 32, n0w = n0 + wn * TN * 32;
     const bool folded = p.bias != nullptr && n0w + TN * 32 <= p.N;                 // wave-uniform
     const unsigned boff = (unsigned)((n0w + hi * 4) * 4);
@@ -107,7 +112,7 @@ __global__ void __launch_bounds__(512, 2) gemm256p_kernel(const GemmParams p) {
   ::"v"(faA0), "v"(faW0), "v"(aoff[0]), "v"(aoff[1]), "v"(aoff[2]), "v"(aoff[3]), "v"(woff[0]), "v"(woff[1]),       \
       "v"(woff[2]), "v"(woff[3]), "v"(aoffn[0]), "v"(aoffn[1]), "v"(aoffn[2]), "v"(aoffn[3]), "v"(woffn[0]),         \
       "v"(woffn[1]), "v"(woffn[2]), "v"(woffn[3]), "v"(boff), "s"(abase), "s"(wbase), "s"(bbase), "s"(nk), "s"(adst), \
-      "s"(wdst), "s"(flags)
+      "s"(wdst), "s"(flags), "s"(abasen), "s"(wbasen)
     static_assert(BN == 128 && SCHED == 0, "shipped: the 128-wide tile, schedule 0 (256-wide tiles run on gemm256x.hip)");
     asm volatile(
 #include "gemm256p_body_n128_s0.inc"

@@ -61,15 +61,13 @@ struct LinearWalk {
   OSK_DEV int64_t a_row(const GemmParams& p, int m) { return osk_tile256::a_row_offset(p, m); }
   OSK_DEV int64_t w_row(const GemmParams& p, int n, bool) { return osk_tile256::w_row_offset(p, n); }
   // a tile whose 256 A rows lie inside M and inside one batch, and whose 256 W rows lie inside N: its per-lane source
-  // offsets are an affine function of (m0, n0), so the next tile's are this tile's plus a wave-uniform delta
+  // offsets are an affine function of (m0, n0) -- relative to the tile's origins they are the same in every such tile
   OSK_DEV bool affine(const GemmParams& p, int m0, int n0) {
     return m0 + 256 <= p.M && n0 + 256 <= p.N && m0 / p.arpb == (m0 + 255) / p.arpb;
   }
-  OSK_DEV int64_t a_origin(const GemmParams& p, int m0) {
-    const int b = m0 / p.arpb, l = m0 - b * p.arpb;
-    return (b * p.abs_ + (int64_t)l * p.ars) * 2;
-  }
-  OSK_DEV int64_t w_origin(const GemmParams& p, int n0) { return (int64_t)n0 * p.wrs * 2; }
+  // the tile's origins (tile256.h, the addressing rule): the smallest element offset of its 256 A rows / W rows
+  OSK_DEV int64_t a_origin(const GemmParams& p, int m0) { return osk_tile256::tile_window(m0, p.M, p.arpb, 0x7fffffff, p.abs_, p.ars).lo; }
+  OSK_DEV int64_t w_origin(const GemmParams& p, int n0) { return osk_tile256::tile_window(n0, p.N, 0x7fffffff, 0x7fffffff, 0, p.wrs).lo; }
   OSK_DEV bool folded(const GemmParams& p, int n0w) { return p.bias != nullptr && n0w + OSKX_NB * 16 <= p.N; }   // wave-uniform
   OSK_DEV void epilogue(const osk_v4f* aq, const GemmParams& p, int m0w, int n0w, int l15, int q4, bool folded) {
     constexpr int WT = OSKX_NB * 16;
@@ -107,11 +105,9 @@ struct VtWalk {
     const int wb = n0 / p.wrpb, pos0 = n0 - wb * p.wrpb;
     return m0 + 256 <= p.M && n0 + 256 <= p.N && pos0 + 256 <= p.wrpb && pos0 + 256 <= p.wvalid;
   }
-  OSK_DEV int64_t a_origin(const GemmParams& p, int m0) { return (int64_t)m0 * p.ars * 2; }
-  OSK_DEV int64_t w_origin(const GemmParams& p, int n0) {
-    const int wb = n0 / p.wrpb, pos0 = n0 - wb * p.wrpb;
-    return (wb * p.wbs + (int64_t)pos0 * p.wrs) * 2;
-  }
+  // (the keys of a tile are whole 64-key groups of its positions, those behind the sequence end clamped: row_window's `valid`)
+  OSK_DEV int64_t a_origin(const GemmParams& p, int m0) { return osk_tile256::tile_window(m0, p.M, 0x7fffffff, 0x7fffffff, 0, p.ars).lo; }
+  OSK_DEV int64_t w_origin(const GemmParams& p, int n0) { return osk_tile256::tile_window(n0, p.N, p.wrpb, p.wvalid, p.wbs, p.wrs).lo; }
   OSK_DEV bool folded(const GemmParams&, int) { return false; }   // (the per-ROW bias b_v is added by the epilogue)
   OSK_DEV void epilogue(const osk_v4f* aq, const GemmParams& p, int m0w, int n0w, int l15, int q4, bool) {
     epi16::vt_all<GeoX>(aq, p, m0w, n0w, l15, q4);
@@ -122,11 +118,12 @@ struct VtWalk {
   ::"v"(faA0), "v"(faW0), "v"(aoff[0]), "v"(aoff[1]), "v"(aoff[2]), "v"(aoff[3]), "v"(aoff[4]), "v"(aoff[5]),          \
       "v"(aoff[6]), "v"(aoff[7]), "v"(woff[0]), "v"(woff[1]), "v"(woff[2]), "v"(woff[3]), "v"(woff[4]), "v"(woff[5]),  \
       "v"(woff[6]), "v"(woff[7]), "v"(boff), "s"(abase), "s"(wbase), "s"(bbase), "s"(nk), "s"(adst), "s"(wdst),        \
-      "s"(flags), "s"(dAs), "s"(dWs), "v"(aoffp), "v"(woffp)
+      "s"(flags), "s"(abasen), "s"(wbasen), "v"(aoffp), "v"(woffp)
 
 // The persistent loop of both kernels: this workgroup's tiles it = blockIdx.x, + gridDim.x, ... of the pack's tile list (each problem's
 // tiles in the grouped order of tile256.h), each one the generated K loop -- which also fetches the first K steps of the NEXT tile where
-// that tile's source offsets are this tile's plus a wave-uniform delta -- and the walk's epilogue.
+// that tile's source offsets, relative to its own origins, are this tile's -- and the walk's epilogue.  Addressing (tile256.h): the
+// 64-bit bases of the K loop are operand + the tile's origin, the 32-bit per-lane offsets are relative to it.
 template <class Walk, int NP>
 OSK_DEV void tile_walk(const GemmPack<NP>& pk) {
   constexpr int WT = OSKX_NB * 16;   // wave tile side
@@ -168,34 +165,35 @@ OSK_DEV void tile_walk(const GemmPack<NP>& pk) {
     tile_of(it, sel, m0, n0);
     const GemmParams& p = pk.p[NP == 1 ? 0 : sel];                 // wave-uniform: kernel-argument loads at a scalar offset
     bool has_next = itn < ntiles;
-    unsigned dA = 0, dW = 0;
+    const int64_t alo = Walk::a_origin(p, m0), wlo = Walk::w_origin(p, n0);
+    int64_t alon = alo, wlon = wlo;
     if (has_next) {
       tile_of(itn, seln, m0n, n0n);
-      // cross-tile prefetch only between two affine tiles of the SAME problem (the deltas are relative to its bases; edge
-      // tiles and the first tile of the second problem start with their own cold fetch)
+      // cross-tile prefetch only between two affine tiles of the SAME problem (one operand pair; edge tiles and the first tile of
+      // the second problem start with their own cold fetch): the next tile's 64-bit origins under this tile's lane offsets
       has_next = seln == sel && Walk::affine(p, m0, n0) && Walk::affine(p, m0n, n0n);
-      dA = (unsigned)(Walk::a_origin(p, m0n) - Walk::a_origin(p, m0));
-      dW = (unsigned)(Walk::w_origin(p, n0n) - Walk::w_origin(p, n0));
+      alon = Walk::a_origin(p, m0n);
+      wlon = Walk::w_origin(p, n0n);
     }
-    const uint64_t abase = rfl64((uint64_t)(uintptr_t)p.A), wbase = rfl64((uint64_t)(uintptr_t)p.W);
+    const uint64_t abase = rfl64((uint64_t)(uintptr_t)p.A + (uint64_t)(alo * 2)), wbase = rfl64((uint64_t)(uintptr_t)p.W + (uint64_t)(wlo * 2));
+    const uint64_t abasen = rfl64((uint64_t)(uintptr_t)p.A + (uint64_t)(alon * 2)), wbasen = rfl64((uint64_t)(uintptr_t)p.W + (uint64_t)(wlon * 2));
     const uint64_t bbase = rfl64((uint64_t)(uintptr_t)p.bias);
-    // LDS-DMA sources (tile256.h): 4 waves; byte offsets from the bases
+    // LDS-DMA sources (tile256.h): 4 waves; byte offsets from the tile's origins
     unsigned aoff[8], woff[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const int r = osk_tile256::dma_row<4>(wave, lane, i);
       const int c = osk_tile256::dma_chunk(lane, r);
-      aoff[i] = (unsigned)(Walk::a_row(p, m0 + r) * 2 + c * 16);
-      woff[i] = (unsigned)(Walk::w_row(p, n0 + r, true) * 2 + c * 16);
+      aoff[i] = (unsigned)((Walk::a_row(p, m0 + r) - alo) * 2 + c * 16);
+      woff[i] = (unsigned)((Walk::w_row(p, n0 + r, true) - wlo) * 2 + c * 16);
     }
     const int m0w = m0 + wm * WT, n0w = n0 + wn * WT;
     const bool folded = Walk::folded(p, n0w);
     const unsigned boff = (unsigned)((n0w + q4 * 4) * 4);
     const unsigned flags = rfl(prefetched | (has_next ? 2u : 0u) | (folded ? 4u : 0u));
-    const unsigned dAs = rfl(dA), dWs = rfl(dW);
     // prefetch lanes: lane l of wave w touches row 64 w + l of the A tile and of the W tile (one dword per 128-byte line)
-    const unsigned aoffp = (unsigned)(Walk::a_row(p, m0 + wave * 64 + lane) * 2);
-    const unsigned woffp = (unsigned)(Walk::w_row(p, n0 + wave * 64 + lane, false) * 2);
+    const unsigned aoffp = (unsigned)((Walk::a_row(p, m0 + wave * 64 + lane) - alo) * 2);
+    const unsigned woffp = (unsigned)((Walk::w_row(p, n0 + wave * 64 + lane, false) - wlo) * 2);
     OSK_TT(0, tt0);
 #ifdef OSK_GEMM_TILE_TIMING
     const unsigned long long tt1 = __builtin_amdgcn_s_memtime();

@@ -149,12 +149,11 @@ static int tile_choice(int M, int N, int K, double* cost = nullptr) {
   return wide ? 2 : 1;
 }
 
-static bool large_tiles_ok(const GemmParams& p) {
-  const int nb = (p.M + p.arpb - 1) / p.arpb;
-  const int64_t a_span = (int64_t)(nb - 1) * p.abs_ + (int64_t)(p.arpb - 1) * p.ars + p.K;
-  const int64_t w_span = (int64_t)(p.N - 1) * p.wrs + p.K;
-  return osk_gemm::gemm256_supported(p, a_span, w_span);
-}
+static bool large_tiles_ok(const GemmParams& p) { return osk_gemm::gemm256_supported(p); }
+
+// the kernel osk_gemm_bf16 launches for these operands: the estimate's choice where the large tiles take them (every 256-row window
+// of A and of W within 32 bits of its origin: gemm256.hip), the 128 x 128 kernel of this file otherwise
+static int dispatch_kind(const GemmParams& p) { return large_tiles_ok(p) ? tile_choice(p.M, p.N, p.K) : 0; }
 
 // ---- GEGLU (f4): the fused path is gemm256x's epilogue class; shapes the 256 x 256 tiles do not take run the plain GEMM into the
 // caller's workspace ([M, 2 N_out] bf16, packed column order) and this row kernel
@@ -206,6 +205,16 @@ extern "C" int osk_gemm_geglu_bf16(const void* A, int64_t a_batch_stride, int64_
 // gemm256x_kernel, 1: 256 x 128 gemm256p_kernel, 0: 128 x 128 gemm_bf16_kernel), and an override for same-process A/B timing of the
 // three (tile_kind -1 restores the estimate; process-wide, not for production use)
 extern "C" int osk_gemm_tile_choice(int M, int N, int K) { return tile_choice(M, N, K); }
+// ... and for given operand strides: osk_gemm_bf16's own dispatch (no launch, host-only)
+extern "C" int osk_gemm_tile_choice_strided(int M, int N, int K, int64_t a_batch_stride, int64_t a_row_stride, int a_rows_per_batch,
+                                            int64_t w_row_stride) {
+  if (M <= 0 || N <= 0 || K <= 0 || (K % BK) || a_rows_per_batch <= 0) return OSK_EINVAL;
+  if ((a_batch_stride & 7) || (a_row_stride & 7) || (w_row_stride & 7)) return OSK_EINVAL;
+  GemmParams p{};
+  p.abs_ = a_batch_stride; p.ars = a_row_stride; p.arpb = a_rows_per_batch; p.wrs = w_row_stride;
+  p.M = M; p.N = N; p.K = K;
+  return dispatch_kind(p);
+}
 extern "C" int osk_gemm_tile_override(int tile_kind) {
   if (tile_kind < -1 || tile_kind > 2) return OSK_EINVAL;
   g_tile_override.store(tile_kind, std::memory_order_relaxed);
@@ -256,16 +265,9 @@ extern "C" int osk_gemm_bf16(const void* A, int64_t a_batch_stride, int64_t a_ro
                              c_row_stride, c_rows_per_batch, res, gate, gate_batch_stride, M, N, K, gelu_from, out_f32);
   if (rc != OSK_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
-  {
-    const int nb = (M + a_rows_per_batch - 1) / a_rows_per_batch;
-    const int64_t a_span = (int64_t)(nb - 1) * a_batch_stride + (int64_t)(a_rows_per_batch - 1) * a_row_stride + K;
-    const int64_t w_span = (int64_t)(N - 1) * w_row_stride + K;
-    if (osk_gemm::gemm256_supported(p, a_span, w_span)) {
-      const int kind = tile_choice(M, N, K);
-      if (kind == 2) return osk_gemm::launch_gemm256x(p, out_f32, st);    // 256 x 256 tiles, 4 waves, v_mfma_f32_16x16x32_bf16
-      if (kind == 1) return osk_gemm::launch_gemm256p(p, out_f32, st);    // 256 x 128 tiles, 8 waves, v_mfma_f32_32x32x16_bf16
-    }
-  }
+  const int kind = dispatch_kind(p);
+  if (kind == 2) return osk_gemm::launch_gemm256x(p, out_f32, st);    // 256 x 256 tiles, 4 waves, v_mfma_f32_16x16x32_bf16
+  if (kind == 1) return osk_gemm::launch_gemm256p(p, out_f32, st);    // 256 x 128 tiles, 8 waves, v_mfma_f32_32x32x16_bf16
   const int nblk = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
   dim3 grid(nblk), block(256);
   if (out_f32) hipLaunchKernelGGL((gemm_bf16_kernel<true>), grid, block, SMEM_BYTES, st, p);
@@ -332,9 +334,7 @@ extern "C" int osk_gemm_group_bf16(const OskGemmTask* tasks, int n_tasks, int K,
     p.M = t.N; p.N = B * Lp; p.K = K; p.gelu_from = p.N;
     p.group = 8;
     p.vt = hd == 128 ? 2 : 1;
-    const int64_t a_span = (int64_t)(t.N - 1) * o.w_row_stride + K;
-    const int64_t w_span = (int64_t)(B - 1) * o.a_batch_stride + (int64_t)(L - 1) * o.a_row_stride + K;
-    if (!osk_gemm::gemm256_supported(p, a_span, w_span)) return OSK_EUNSUPPORTED;
+    if (!osk_gemm::gemm256_supported(p)) return OSK_EUNSUPPORTED;   // (the windows of the weight and of the activations: gemm256.hip)
   }
   if (n_vt > 2 || n_plain > 2) return OSK_EUNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;

@@ -86,11 +86,8 @@ extern "C" int osk_gemm_fp8(const void* A8, int64_t a_batch_stride, int64_t a_ro
   p.M = M; p.N = N; p.K = K; p.gelu_from = gelu_from;
   p.sa = a_scale; p.sw = w_scale;
   p.group = (N + 255) / 256 <= 6 ? 4 : 8;
-  const int nb = (M + a_rows_per_batch - 1) / a_rows_per_batch;
-  const int64_t a_span = (int64_t)(nb - 1) * a_batch_stride + (int64_t)(a_rows_per_batch - 1) * a_row_stride + K;
-  const int64_t w_span = (int64_t)(N - 1) * w_row_stride + K;
   // only the large-tile kernel has an fp8 instantiation: small / odd shapes stay on osk_gemm_bf16 (the host decides)
-  if (!osk_gemm::gemm256_fp8_supported(p, a_span, w_span)) return OSK_EUNSUPPORTED;
+  if (!osk_gemm::gemm256_fp8_supported(p)) return OSK_EUNSUPPORTED;
   auto rounds = [](int64_t tiles, int64_t slots) { return (double)((tiles + slots - 1) / slots); };
   const int64_t m256 = (M + 255) / 256;
   const double c256 = rounds(m256 * ((N + 255) / 256), 256) * 4.0;

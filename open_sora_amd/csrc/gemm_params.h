@@ -53,8 +53,9 @@ static __host__ __device__ __forceinline__ int vt_perm64(int pos, int kind) {
   return g + grp + ((p16 < 4 || p16 >= 12) ? p16 : (p16 < 8 ? p16 + 4 : p16 - 4));
 }
 
-// large tiles need M >= 256, N >= 128, K % 64 == 0 and both operand tensors within the kernels' 32-bit per-lane offsets
-bool gemm256_supported(const GemmParams& p, int64_t a_span_elems, int64_t w_span_elems);
+// large tiles need M >= 256, N >= 128, K % 64 == 0 and every 256-row window of both operands within the kernels' 32-bit per-lane
+// offsets from the window's own origin (tile256.h; gemm256.hip) -- the operands may span more than 4 GiB
+bool gemm256_supported(const GemmParams& p);
 // gemm256p.hip: 256 x 128 tiles walked by one persistent 8-wave workgroup per CU (cross-tile prefetch, bias-initialised accumulators)
 int launch_gemm256p(const GemmParams& p, int out_f32, hipStream_t st);
 // gemm256x.hip: 256 x 256 tiles, 4 waves (one per SIMD, 128 x 128 wave tiles, 256 accumulator AGPRs) on v_mfma_f32_16x16x32_bf16
@@ -64,7 +65,7 @@ int launch_gemm256x_pair(const GemmParams& p0, const GemmParams& p1, hipStream_t
 // one or two V^T problems (gemm_params.h: vt != 0) that share K as ONE tile list (gemm256x_vt_kernel)
 int launch_gemm256x_vt(const GemmParams* ps, int n, hipStream_t st);
 // gemm256.hip: the one-tile-per-workgroup frame on OCP e4m3 operands (A, W point at bytes; strides in elements = bytes)
-bool gemm256_fp8_supported(const GemmParams& p, int64_t a_span_elems, int64_t w_span_elems);
+bool gemm256_fp8_supported(const GemmParams& p);
 int launch_gemm256_fp8(const GemmParams& p, int bn, int out_f32, hipStream_t st);
 
 }  // namespace osk_gemm

@@ -47,4 +47,53 @@ OSK_DEV int64_t w_row_offset(const osk_gemm::GemmParams& p, int n) {
   return (int64_t)n * p.wrs;
 }
 
+// ---- Addressing rule of the 256-row tiles.  An LDS-DMA instruction adds a 32-bit UNSIGNED per-lane byte offset to a wave-uniform
+// 64-bit base.  The base a kernel hands to its K loop is operand + the tile's ORIGIN -- the smallest element offset of the rows the
+// tile's loaders touch -- and the lane offsets are relative to it: only the WINDOW of one tile (its 256 rows, a batch jump in the
+// middle included, forwards or backwards) has to fit 32 bits, the operand may span any number of GiB.  The K axis advances the
+// 64-bit base.  row_window() is that window, for the device (origin = lo) and for the host's support condition (windows_fit).
+struct RowWindow { int64_t lo, hi; };   // smallest / largest element offset of the rows [first, last]
+
+// rows first .. last (first <= last, both inside the operand) where row r lies at (r / rpb) * bs + min(r % rpb, valid - 1) * rs:
+// batched rows whose positions behind `valid` read the last valid one (plain operands: rpb = valid = INT_MAX, bs = 0).  Inside a
+// batch the offset is monotonic in the row, and whole batches between the first and the last one are linear in the batch index:
+// the extremes are among the ends of the first, second, last-but-one and last batch's pieces.
+static __host__ __device__ __forceinline__ RowWindow row_window(int first, int last, int rpb, int valid, int64_t bs, int64_t rs) {
+  const int b0 = first / rpb, b1 = last / rpb;
+  auto at = [&](int b, int l) { return b * bs + (int64_t)(l < valid ? l : valid - 1) * rs; };
+  const int64_t x = at(b0, first - b0 * rpb), y = at(b0, b0 == b1 ? last - b1 * rpb : rpb - 1);
+  RowWindow w{x < y ? x : y, x < y ? y : x};
+  auto add = [&](int64_t v) { w.lo = v < w.lo ? v : w.lo; w.hi = v > w.hi ? v : w.hi; };
+  if (b1 != b0) {
+    add(at(b1, 0));
+    add(at(b1, last - b1 * rpb));
+    if (b1 - b0 > 1) {
+      add(at(b0 + 1, 0)); add(at(b0 + 1, rpb - 1));
+      add(at(b1 - 1, 0)); add(at(b1 - 1, rpb - 1));
+    }
+  }
+  return w;
+}
+// the window of the tile whose first row is r0: rows r0 .. r0 + 255, those behind the operand's last row read that row
+static __host__ __device__ __forceinline__ RowWindow tile_window(int r0, int rows, int rpb, int valid, int64_t bs, int64_t rs) {
+  return row_window(r0, r0 + 255 < rows ? r0 + 255 : rows - 1, rpb, valid, bs, rs);
+}
+
+// host: does every 256-row window of an operand of `rows` rows (K elements of es bytes read per row) lie within 2^32 - 1 bytes
+// of its own origin?  Forward strides and a whole operand inside 4 GiB: yes, without looking at the tiles.
+inline bool windows_fit(int rows, int rpb, int valid, int64_t bs, int64_t rs, int K, int es) {
+  constexpr int64_t LIMIT = 0xFFFFFFFFll;
+  if (bs >= 0 && rs >= 0) {
+    const int lmax = (rpb < rows ? rpb : rows) - 1;
+    if (((rows - 1) / rpb * bs + (lmax < valid ? lmax : valid - 1) * rs + K) * es <= LIMIT) return true;
+  }
+  // one batch: every tile's window is the first one's, or a shorter one
+  const int step = rpb >= rows ? rows : 256;
+  for (int r0 = 0; r0 < rows; r0 += step) {
+    const RowWindow w = tile_window(r0, rows, rpb, valid, bs, rs);
+    if (w.hi - w.lo > (LIMIT / es) - K) return false;
+  }
+  return true;
+}
+
 }  // namespace osk_tile256

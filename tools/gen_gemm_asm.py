@@ -178,7 +178,7 @@ def gen(c):
 
 PERS_OPERANDS = ["faA0", "faW0", "aoff0", "aoff1", "aoff2", "aoff3", "woff0", "woff1", "woff2", "woff3",
                  "aoffn0", "aoffn1", "aoffn2", "aoffn3", "woffn0", "woffn1", "woffn2", "woffn3", "boff",
-                 "abase", "wbase", "bias", "nk", "adst", "wdst", "flags"]
+                 "abase", "wbase", "bias", "nk", "adst", "wdst", "flags", "abasen", "wbasen"]
 POP = {n: "%%%d" % i for i, n in enumerate(PERS_OPERANDS)}
 S_PFLAGS, S_PBIAS = 52, 54          # flags; bias base (pair)
 PERS_S_LAST = 55
@@ -189,8 +189,10 @@ def gen_pers(c, sched=0):
     """K loop of gen() for a PERSISTENT workgroup (csrc/gemm256p.hip): the asm statement is executed once per output
     tile of the workgroup's tile list, and the fixed costs of a tile move off the matrix pipe's critical path:
       * exit: after the last barrier both LDS stages are free -> the LDS-DMA of the NEXT tile's K steps 0 and 1 (per-lane
-        source offsets aoffn / woffn) is issued in the shadows of the trailing k-sub-step, so it lands while the wrapper
-        runs this tile's epilogue (flags bit 1 = there is a next tile);
+        source offsets aoffn / woffn from the next tile's OWN 64-bit origins abasen / wbasen: every tile is addressed
+        relative to its origin, so only a tile's 256-row window has to fit the 32-bit lane offsets) is issued in the shadows
+        of the trailing k-sub-step, so it lands while the wrapper runs this tile's epilogue (flags bit 1 = there is a next
+        tile);
       * entry: flags bit 0 = stages 0 / 1 are already in flight (issued by the previous tile's exit): no load prologue;
       * the accumulators start from the bias (flags bit 2; 16 f32 per 32-column tile and lane, loaded once per tile
         into the idle fragment registers) instead of zero, so the epilogue of an un-gated Linear issues no load at all.
@@ -425,8 +427,8 @@ def gen_pers(c, sched=0):
     # both stages are free now (every fragment of the last K step is in registers): fetch the next tile's first two K steps
     e("s_bitcmp1_b32 s%d, %d" % (S_PFLAGS, PF_HAS_NEXT))
     e("s_cbranch_scc0 %s" % ref("last"))
-    e("s_mov_b64 s[%d:%d], %s" % (S_AB, S_AB + 1, POP["abase"]))
-    e("s_mov_b64 s[%d:%d], %s" % (S_WB, S_WB + 1, POP["wbase"]))
+    e("s_mov_b64 s[%d:%d], %s" % (S_AB, S_AB + 1, POP["abasen"]))
+    e("s_mov_b64 s[%d:%d], %s" % (S_WB, S_WB + 1, POP["wbasen"]))
     mf = mfmas(1)
     pieces = dma(0, nxt=True)
     e(pieces[0][0])
@@ -479,9 +481,9 @@ class Cfg4:
 
 
 W4_OPERANDS = ["faA0", "faW0"] + ["aoff%d" % i for i in range(8)] + ["woff%d" % i for i in range(8)] + \
-              ["boff", "abase", "wbase", "bias", "nk", "adst", "wdst", "flags", "dA", "dW", "aoffp", "woffp"]
+              ["boff", "abase", "wbase", "bias", "nk", "adst", "wdst", "flags", "abasen", "wbasen", "aoffp", "woffp"]
 WOP = {n: "%%%d" % i for i, n in enumerate(W4_OPERANDS)}
-S_DA, S_DW, S_PFA, S_PFW = 56, 57, 58, 60
+S_PFA, S_PFW = 58, 60
 S_RA, S_RW, S_KOFF = 64, 68, 72          # buffer resources of A and W (4 SGPRs each), K-step byte offset (dmak = 1)
 W4_S_LAST = 72
 
@@ -490,9 +492,10 @@ def gen_w4(c, pf=0, abl=0, dmak=0, spread=1, rd_per=2):
     """Persistent-workgroup K loop (see gen_pers) for the 4-wave layout of Cfg4.  Differences: 16 MFMAs, 8 fragment
     reads and 16 LDS-DMA pieces per k-sub-step / K step and wave, placed "matrix pipe first" (schedule 1 of gen_pers:
     behind a barrier the trailing sub-step starts at once, reads ride two per shadow at the head of a sub-step, one
-    LDS-DMA piece per shadow behind them); the next tile's source offsets are this tile's plus a wave-uniform byte
-    delta (dA, dW: valid when both tiles are interior -- the wrapper clears flags bit 1 otherwise), computed into the
-    idle fragment registers at the exit."""
+    LDS-DMA piece per shadow behind them); the per-lane source offsets are relative to the tile's own
+    64-bit origin (abase / wbase), and between two interior tiles they are equal -- so the exit fetches the next tile with THIS
+    tile's offset registers from the next tile's origins (abasen / wbasen; the wrapper clears flags bit 1 where either tile
+    is not interior).  The step between two origins is a 64-bit quantity: an operand may span more than 4 GiB."""
     L = []
     e = lambda t: L.append("  " + t)
     lab = lambda n: L.append(".L%s_%s_%%=:" % (c.tag, n))
@@ -571,8 +574,6 @@ def gen_w4(c, pf=0, abl=0, dmak=0, spread=1, rd_per=2):
     e("s_mov_b32 s%d, %s" % (S_ADST, WOP["adst"]))
     e("s_mov_b32 s%d, %s" % (S_WDST, WOP["wdst"]))
     e("s_mov_b32 s%d, %s" % (S_PFLAGS, WOP["flags"]))
-    e("s_mov_b32 s%d, %s" % (S_DA, WOP["dA"]))
-    e("s_mov_b32 s%d, %s" % (S_DW, WOP["dW"]))
     if dmak:   # raw buffer resources: base, stride 0, num_records 2^32 - 1 bytes, gfx9 data-format word
         for rs, base in ((S_RA, WOP["abase"]), (S_RW, WOP["wbase"])):
             e("s_mov_b64 s[%d:%d], %s" % (rs, rs + 1, base))
@@ -748,15 +749,11 @@ def gen_w4(c, pf=0, abl=0, dmak=0, spread=1, rd_per=2):
         e("s_barrier")
     e("s_bitcmp1_b32 s%d, %d" % (S_PFLAGS, PF_HAS_NEXT))
     e("s_cbranch_scc0 %s" % ref("last"))
-    e("s_mov_b64 s[%d:%d], %s" % (S_AB, S_AB + 1, WOP["abase"]))
-    e("s_mov_b64 s[%d:%d], %s" % (S_WB, S_WB + 1, WOP["wbase"]))
-    # next tile's per-lane source offsets into fragment set 0 (its last MFMAs were issued before the barrier)
-    an = [vr(c.V0 + i) for i in range(c.NA)]
-    wn = [vr(c.V0 + c.NA + i) for i in range(c.NW)]
-    for i in range(c.NA):
-        e("v_add_u32_e32 %s, s%d, %s" % (an[i], S_DA, WOP["aoff%d" % i]))
-    for i in range(c.NW):
-        e("v_add_u32_e32 %s, s%d, %s" % (wn[i], S_DW, WOP["woff%d" % i]))
+    assert not dmak, "the buffer-resource form was an experiment of the absolute-offset frame: no next-tile resources"
+    # the next tile: its own origins, this tile's per-lane offsets (two interior tiles: equal relative to their origins)
+    e("s_mov_b64 s[%d:%d], %s" % (S_AB, S_AB + 1, WOP["abasen"]))
+    e("s_mov_b64 s[%d:%d], %s" % (S_WB, S_WB + 1, WOP["wbasen"]))
+    an = wn = None
     mf = mfmas(1)
     pieces = dma(0, an, wn, koff="0")
     e(pieces[0][0])
@@ -879,8 +876,6 @@ def gen_x4(c, spread=4, rd_per=1):
     e("s_mov_b32 s%d, %s" % (S_ADST, WOP["adst"]))
     e("s_mov_b32 s%d, %s" % (S_WDST, WOP["wdst"]))
     e("s_mov_b32 s%d, %s" % (S_PFLAGS, WOP["flags"]))
-    e("s_mov_b32 s%d, %s" % (S_DA, WOP["dA"]))
-    e("s_mov_b32 s%d, %s" % (S_DW, WOP["dW"]))
     e("s_mov_b32 s%d, 0" % S_T)
     e("s_mov_b32 s%d, 0" % S_KL)
     e("v_xor_b32_e32 %s, 64, %s" % (fa[("A", 1)], WOP["faA0"]))     # k 32..63: 16-byte chunk index + 4 = ^ 4 under the swizzle
@@ -962,17 +957,12 @@ def gen_x4(c, spread=4, rd_per=1):
     lab("exit")
     e("s_bitcmp1_b32 s%d, %d" % (S_PFLAGS, PF_HAS_NEXT))
     e("s_cbranch_scc0 %s" % ref("last"))
-    e("s_mov_b64 s[%d:%d], %s" % (S_AB, S_AB + 1, WOP["abase"]))
-    e("s_mov_b64 s[%d:%d], %s" % (S_WB, S_WB + 1, WOP["wbase"]))
-    # next tile's per-lane source offsets into fragment set 0 (its last MFMAs were issued before the barrier)
-    an = [vr(c.V0 + i) for i in range(c.NA)]
-    wn = [vr(c.V0 + c.NA + i) for i in range(c.NW)]
-    for i in range(c.NA):
-        e("v_add_u32_e32 %s, s%d, %s" % (an[i], S_DA, WOP["aoff%d" % i]))
-    for i in range(c.NW):
-        e("v_add_u32_e32 %s, s%d, %s" % (wn[i], S_DW, WOP["woff%d" % i]))
+    # the next tile: its own 64-bit origins (abasen / wbasen) under THIS tile's per-lane offsets -- relative to their origins the
+    # offsets of two interior tiles are equal, and the step between two origins does not have to fit 32 bits
+    e("s_mov_b64 s[%d:%d], %s" % (S_AB, S_AB + 1, WOP["abasen"]))
+    e("s_mov_b64 s[%d:%d], %s" % (S_WB, S_WB + 1, WOP["wbasen"]))
     mf = mfmas(1)
-    pieces = dma(0, an, wn)
+    pieces = dma(0)
     e(pieces[0][0])
     for i, m in enumerate(mf):
         e(m)
@@ -987,7 +977,7 @@ def gen_x4(c, spread=4, rd_per=1):
     e("s_addc_u32 s%d, s%d, 0" % (S_AB + 1, S_AB + 1))
     e("s_add_u32 s%d, s%d, s%d" % (S_WB, S_WB, S_STEP))
     e("s_addc_u32 s%d, s%d, 0" % (S_WB + 1, S_WB + 1))
-    plain(dma(1, an, wn))
+    plain(dma(1))
     e("s_branch %s" % ref("end"))
     lab("last")
     for m in mfmas(1):
