@@ -325,6 +325,35 @@ int osk_attention_fwd_pv8_bf16(const void* q, int64_t q_batch_stride, int64_t q_
                                float scale, int q_prescaled, int kv_batches, void* workspace, int64_t workspace_bytes,
                                void* stream);
 
+/* ---- fp8 QK^T + fp8 P.V variant of the attention (opt-in fp8 mode, qk8; head_dim 128 only, other head dims: OSK_EUNSUPPORTED).
+ * Reference call site: attention() of opensora/models/mmdit/math.py:16-36, like the entries above.  Both products of a 64-key
+ * tile run on v_mfma_f32_32x32x64_f8f6f4; P.V, V^T (osk_v_transpose_fp8), the softmax bookkeeping and the output are those of
+ * osk_attention_fwd_pv8_bf16.
+ * osk_k_pack_fp8: K bf16 [B, L, H*128] view (the output of osk_qknorm_rope_bf16, strides in elements, last dim contiguous) ->
+ *   k8 e4m3 bytes [B, H, Lp, 128], Lp = L rounded up to 64.  Quantisation rule: byte d of row l of head (b, h) =
+ *   e4m3(clamp(K[b, l, h, d] / scales[b*H + h], -448, 448)), the division in f32 (IEEE), the conversion round-to-nearest-even,
+ *   saturating.  Byte order: natural -- dim d is byte d of its row; the kernel's LDS image is a straight LDS-DMA copy of 16-byte
+ *   pieces of these rows (the bank swizzle is in the copy's addresses, not in the tensor).  Rows L .. Lp-1 repeat row L-1, so
+ *   the scores of a ragged last tile stay finite; key validity comes from the baked row of vt8.  scales f32 [B, H]: what
+ *   osk_v_scale_fp8 computes when it is pointed at K (absmax over the head / 448, 1.0 for an all-zero head).  With several key
+ *   segments: one call per segment with the SAME scales (their maximum over the segments).
+ * osk_attention_fwd_qk8_bf16: the arguments of osk_attention_fwd_pv8_bf16 except that k8 (from the call above, per key segment)
+ *   replaces k with k8_seg_stride and k8_batch_stride in BYTES (multiples of 16; batch stride of one segment's tensor =
+ *   H * Lp * 128), k8_row_stride = 128 (bytes; anything else: OSK_EUNSUPPORTED), and k_scale = the scales the pack used, indexed
+ *   by (key batch, head).  Q stays bf16 in memory; the kernel quantises it in its prologue, per query row and head:
+ *   qf = f32(q) * (q_prescaled ? 1 : scale * log2(e)), s_q = absmax over the head's 128 dims of qf / 448 (1.0 for an all-zero
+ *   row), q8 = e4m3(clamp(qf / s_q, -448, 448)), same rounding.  A score in log2 units is s_q * k_scale * (q8 . k8), applied
+ *   with one f32 FMA per score.  No allocation, no synchronisation, no memset: capturable in a hipGraph. */
+int osk_k_pack_fp8(const void* k, int64_t k_batch_stride, int64_t k_row_stride, const float* scales, void* k8,
+                   int B, int L, int H, int hd, void* stream);
+int osk_attention_fwd_qk8_bf16(const void* q, int64_t q_batch_stride, int64_t q_row_stride,
+                               const void* k8, int64_t k8_seg_stride, int64_t k8_batch_stride, int64_t k8_row_stride,
+                               const float* k_scale, const void* vt8, int64_t vt8_seg_stride, const float* v_scale,
+                               void* out, int64_t o_batch_stride, int64_t o_row_stride,
+                               float* lse, int B, int H, int Lq, int n_seg, int seg_len, int hd,
+                               float scale, int q_prescaled, int kv_batches, void* workspace, int64_t workspace_bytes,
+                               void* stream);
+
 /* ---- short-sequence attention with an optional ALiBi bias (the STDiT-generation block's temporal
  * self-attention over T <= 64 frames, B * H * W independent sequences, "RoPE/ALiBi" in BASELINE.json's north_star).  The mounted
  * v2.0 reference passes alibi_slopes=None at every flash-attn call site (opensora/models/mmdit/math.py:22-36), so this entry is

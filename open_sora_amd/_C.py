@@ -59,6 +59,9 @@ SIGNATURES = {
     "osk_v_transpose_fp8": [_vp, _i64, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
     "osk_attention_fwd_pv8_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _vp,
                                    _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _vp, _i64, _vp],
+    "osk_k_pack_fp8": [_vp, _i64, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
+    "osk_attention_fwd_qk8_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp,
+                                   _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _vp, _i64, _vp],
     "osk_attention_tail_split_factor": [_i32, _i32, _i32, _i32, _i32, _i32, _i64],
     "osk_attention_launch_shape": [_i32, _i32, _i32, _i32, _i32, _i32, _f32, _i64, C.POINTER(_i32)],
     "osk_attention_rows_override": [_i32],
@@ -643,6 +646,54 @@ def attention_fwd_pv8(q: torch.Tensor, k: torch.Tensor, vt8: torch.Tensor, v_sca
     """attention_fwd with the P.V product on the fp8 MFMA: vt8 / v_scale from v_transpose_fp8 (vt_seg_stride in bytes)."""
     return _attn_call("osk_attention_fwd_pv8_bf16", q, k, vt8, out, H, hd, scale, lse, n_seg, seg_len, k_seg_stride, vt_seg_stride,
                       q_prescaled, kv_batches, workspace, after_vt=(v_scale.data_ptr(),))
+
+
+def k8_shape(B: int, H: int, L: int, hd: int = 128) -> tuple:
+    """shape of the e4m3 K tensor of one key segment of L keys: [B, H, L rounded up to 64, 128] (head_dim 128 only)"""
+    assert hd == 128, f"the fp8 QK^T kernel exists for head_dim 128 only, not {hd}"
+    return (B, H, (L + 63) // 64 * 64, 128)
+
+
+def k_pack_fp8(k: torch.Tensor, scales: torch.Tensor, k8: torch.Tensor, H: int, hd: int) -> torch.Tensor:
+    """k bf16 [B, L, H*128] view, scales f32 [B, H] (v_scale_fp8 of k) -> k8 uint8 [B, H, Lp, 128]: e4m3 bytes of k / scale in
+    natural dim order, rows L .. Lp-1 = row L-1 (osk_k_pack_fp8)."""
+    assert k.dim() == 3, k.shape
+    B, L, C_ = k.shape
+    assert hd == 128, f"the fp8 QK^T kernel exists for head_dim 128 only, not {hd}"
+    assert k.dtype == torch.bfloat16 and C_ == H * hd, (k.dtype, k.shape)
+    assert k.stride(2) == 1 and k.stride(0) % 8 == 0 and k.stride(1) % 8 == 0 and k.data_ptr() % 16 == 0, (k.stride(), k.data_ptr() % 16)
+    assert k8.dtype == torch.uint8 and k8.is_contiguous() and tuple(k8.shape) == k8_shape(B, H, L, hd) and k8.data_ptr() % 16 == 0, (k8.dtype, k8.shape)
+    assert scales.dtype == torch.float32 and scales.is_contiguous() and scales.numel() == B * H, (scales.dtype, scales.shape)
+    _check(lib.osk_k_pack_fp8(k.data_ptr(), k.stride(0), k.stride(1), scales.data_ptr(), k8.data_ptr(), B, L, H, hd, _stream()),
+           "osk_k_pack_fp8")
+    return k8
+
+
+def attention_fwd_qk8(q: torch.Tensor, k8: torch.Tensor, k_scale: torch.Tensor, vt8: torch.Tensor, v_scale: torch.Tensor,
+                      out: torch.Tensor, H: int, hd: int, scale: float, *, seg_len: int, lse=None, n_seg: int = 1,
+                      k_seg_stride: int = 0, vt_seg_stride: int = 0, q_prescaled: bool = False, kv_batches: int = 0,
+                      workspace: torch.Tensor | None = None):
+    """attention_fwd_pv8 with QK^T on the fp8 MFMA as well (head_dim 128): k8 / k_scale from k_pack_fp8 -- k8 is segment 0's
+    [Bkv, H, Lp, 128] tensor, further segments k_seg_stride BYTES apart; seg_len = keys per segment (k8 only shows Lp)."""
+    assert hd == 128, f"the fp8 QK^T kernel exists for head_dim 128 only, not {hd}"
+    assert q.dtype == torch.bfloat16 and out.dtype == torch.bfloat16 and q.dim() == 3 and q.shape[2] == H * hd, (q.dtype, out.dtype, q.shape)
+    assert q.stride(2) == 1 and out.stride(2) == 1, (q.stride(), out.stride())
+    B = q.shape[0]
+    Bkv = kv_batches or B
+    assert k8.dtype == torch.uint8 and k8.dim() == 4 and k8.stride(3) == 1 and k8.stride(2) == 128, (k8.dtype, k8.shape, k8.stride())
+    assert tuple(k8.shape) == k8_shape(Bkv, H, seg_len, hd) and k8.stride(1) == k8.shape[2] * 128, (k8.shape, k8.stride())
+    assert k8.data_ptr() % 16 == 0 and k8.stride(0) % 16 == 0 and k_seg_stride % 16 == 0, (k8.stride(), k_seg_stride)
+    for s_ in (k_scale, v_scale):
+        assert s_.dtype == torch.float32 and s_.is_contiguous() and s_.numel() == Bkv * H, (s_.dtype, s_.shape)
+    assert vt8.dtype == torch.uint8 and vt8.shape[-2] == vt8_rows(hd) and vt8.shape[-1] == k8.shape[2], (vt8.dtype, vt8.shape)
+    Lq = q.shape[1]
+    with _attn_prof():
+        _check(lib.osk_attention_fwd_qk8_bf16(q.data_ptr(), q.stride(0), q.stride(1), k8.data_ptr(), k_seg_stride, k8.stride(0), 128,
+                                              k_scale.data_ptr(), vt8.data_ptr(), vt_seg_stride, v_scale.data_ptr(), out.data_ptr(),
+                                              out.stride(0), out.stride(1), _p(lse), B, H, Lq, n_seg, seg_len, hd, scale,
+                                              int(q_prescaled), kv_batches, _p(workspace),
+                                              0 if workspace is None else workspace.numel(), _stream()), "osk_attention_fwd_qk8_bf16")
+    return out
 
 
 def copy_rows_ok(src: torch.Tensor, dst: torch.Tensor) -> bool:

@@ -516,3 +516,85 @@ extern "C" int osk_attention_fwd_pv8_bf16(const void* q, int64_t q_batch_stride,
   rc = hd == 128 ? osk_attn::launch_asm128p8(p, st) : osk_attn::launch_asm72p8(p, st);
   return then_merge(rc, p, hd, st);
 }
+
+// =============================================================================================
+// fp8 QK^T variant (head_dim 128): K -> e4m3 in the layout the kernel's LDS-DMA copies; entry point
+// =============================================================================================
+namespace {
+
+// K [B, L, H * 128] bf16 (strided) -> k8 [B, H, Lp, 128] e4m3 bytes, Lp = L rounded up to 64: byte d of row l = e4m3(clamp(k[b, l, h, d]
+// / scales[b, h], +-448)), dims in their natural order; rows L .. Lp - 1 repeat row L - 1.  One block = one 64-key tile of one
+// head; a thread converts 16-dim pieces (32 bytes in, 16 bytes out), all loads of a block in flight before the first use.
+__global__ void __launch_bounds__(256) k_pack_fp8_kernel(const unsigned short* __restrict__ k, int64_t bs, int64_t rs,
+                                                         const float* __restrict__ scales, unsigned char* __restrict__ k8, int L,
+                                                         int Lp, int H) {
+  const int kt = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+  const float sc = scales[b * H + h];
+  uint4 u[2][2];
+  int row[2], c[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int j = threadIdx.x + 256 * i;       // 64 rows x 8 pieces
+    row[i] = kt * 64 + (j >> 3);
+    c[i] = j & 7;
+    const int src = row[i] < L ? row[i] : L - 1;
+    const unsigned short* px = k + b * bs + (int64_t)src * rs + h * 128 + c[i] * 16;
+    u[i][0] = *reinterpret_cast<const uint4*>(px);
+    u[i][1] = *reinterpret_cast<const uint4*>(px + 8);
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    float f[16];
+    unpack8(u[i][0], f);
+    unpack8(u[i][1], f + 8);
+    unsigned w[4];
+#pragma unroll
+    for (int q4 = 0; q4 < 4; ++q4) {
+      float g[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) g[e] = fminf(fmaxf(f[q4 * 4 + e] / sc, -448.0f), 448.0f);
+      int r = 0;
+      r = __builtin_amdgcn_cvt_pk_fp8_f32(g[0], g[1], r, false);
+      r = __builtin_amdgcn_cvt_pk_fp8_f32(g[2], g[3], r, true);
+      w[q4] = (unsigned)r;
+    }
+    *reinterpret_cast<uint4*>(k8 + ((int64_t)(b * H + h) * Lp + row[i]) * 128 + c[i] * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+  }
+}
+
+}  // namespace
+
+extern "C" int osk_k_pack_fp8(const void* k, int64_t bs, int64_t rs, const float* scales, void* k8, int B, int L, int H, int hd,
+                              void* stream) {
+  if (!k || !k8 || !scales || B <= 0 || L <= 0 || H <= 0 || (bs & 7) || (rs & 7) || ((uintptr_t)k & 15) || ((uintptr_t)k8 & 15) ||
+      ((uintptr_t)scales & 3))
+    return OSK_EINVAL;
+  if (hd != 128) return OSK_EUNSUPPORTED;
+  const int Lp = (L + 63) / 64 * 64;
+  dim3 grid(Lp / 64, H, B), block(256);
+  hipLaunchKernelGGL(k_pack_fp8_kernel, grid, block, 0, (hipStream_t)stream, (const unsigned short*)k, bs, rs, scales,
+                     (unsigned char*)k8, L, Lp, H);
+  return (int)hipGetLastError();
+}
+
+extern "C" int osk_attention_fwd_qk8_bf16(const void* q, int64_t q_batch_stride, int64_t q_row_stride,
+                                          const void* k8, int64_t k8_seg_stride, int64_t k8_batch_stride,
+                                          int64_t k8_row_stride, const float* k_scale, const void* vt8, int64_t vt8_seg_stride,
+                                          const float* v_scale, void* out, int64_t o_batch_stride, int64_t o_row_stride,
+                                          float* lse, int B, int H, int Lq, int n_seg, int seg_len, int hd,
+                                          float scale, int q_prescaled, int kv_batches, void* workspace,
+                                          int64_t workspace_bytes, void* stream) {
+  if (!v_scale || !k_scale || ((uintptr_t)k_scale & 3) || ((uintptr_t)v_scale & 3)) return OSK_EINVAL;
+  if ((k8_seg_stride & 15) || (k8_batch_stride & 15) || k8_seg_stride < 0 || k8_batch_stride < 0) return OSK_EINVAL;
+  AttnParams p;
+  int rc = attn_params(p, q, q_batch_stride, q_row_stride, k8, k8_seg_stride, k8_batch_stride, k8_row_stride, vt8, vt8_seg_stride, 15,
+                       out, o_batch_stride, o_row_stride, lse, B, H, Lq, n_seg, seg_len, hd, {128}, scale, q_prescaled,
+                       kv_batches, workspace, workspace_bytes);
+  if (rc != OSK_OK) return rc;
+  if (k8_row_stride != 128) return OSK_EUNSUPPORTED;   // the packed layout: rows of 128 bytes, heads seg_lp rows apart
+  p.k = nullptr; p.k8 = (const unsigned char*)k8; p.k_scale = k_scale;
+  p.vt = nullptr; p.vt8 = (const unsigned char*)vt8; p.v_scale = v_scale;
+  osk_attn::split_tail(p, osk_attn::attn_units(p), hd, workspace, workspace_bytes);
+  hipStream_t st = (hipStream_t)stream;
+  return then_merge(osk_attn::launch_asm128q8(p, st), p, hd, st);
+}

@@ -35,6 +35,10 @@ struct AttnParams {
   // osk_v_transpose_fp8, one f32 scale per (key batch, head)
   const unsigned char* vt8 = nullptr;
   const float* v_scale = nullptr;
+  // fp8 QK^T variant (attention_asm128q8.hip): K as e4m3 [Bkv, H, seg_lp, 128] per segment from osk_k_pack_fp8 (kss, kbs in BYTES,
+  // krs = 128), one f32 scale per (key batch, head)
+  const unsigned char* k8 = nullptr;
+  const float* k_scale = nullptr;
   // device-derived score bound (round 6, osk_attention_fwd_auto_bf16): squared row-norm maxima of the q and k the kernel receives,
   // per (batch, head) -- qn2 [B, H], kn2 [Bkv, H], from osk_rownorm2_max_bf16.  With both set, every workgroup derives ITS bound
   // sqrt(qn2 kn2) (Cauchy-Schwarz on the actual operands) and the launch is one of a PAIR over the same grid: the FAST kernel's
@@ -189,5 +193,7 @@ int launch_asm128(const AttnParams& p, hipStream_t st);
 // attention_asm128p8.hip / attention_asm72p8.hip: the same with the P.V product on the fp8 MFMA
 int launch_asm128p8(const AttnParams& p, hipStream_t st);
 int launch_asm72p8(const AttnParams& p, hipStream_t st);
+// attention_asm128q8.hip: head_dim 128 with QK^T on the fp8 MFMA as well (K e4m3 from osk_k_pack_fp8, Q quantised in the prologue)
+int launch_asm128q8(const AttnParams& p, hipStream_t st);
 
 }  // namespace osk_attn

@@ -370,6 +370,7 @@ class _DoublePlan:
     txt_mlp: tuple = ()
     mod_layers: list = field(default_factory=list)  # [(w bf16, b bf16)] img then txt
     pv8: bool = False   # fp8 mode: attention with the P.V product on the fp8 MFMA
+    qk8: bool = False   # ... and, at head_dim 128 outside sequence parallelism, QK^T too (enable_fp8(qk8=True))
     key: tuple = ()     # _param_key of the block the plan was built from
     score_bound: float = 0.0   # bound on |q . k| as the attention kernel sees it (log2 units): _score_bound()
 
@@ -384,6 +385,7 @@ class _SinglePlan:
     k_scale: Tensor
     mod_layers: list = field(default_factory=list)
     pv8: bool = False
+    qk8: bool = False
     key: tuple = ()
     score_bound: float = 0.0
 
@@ -444,7 +446,7 @@ def plan_double(block) -> _DoublePlan:
             img_mlp=(wr(_w(block.img_mlp[0].weight)), _b32(block.img_mlp[0].bias), wr(_w(block.img_mlp[2].weight)), _b32(block.img_mlp[2].bias)),
             txt_mlp=(wr(_w(block.txt_mlp[0].weight)), _b32(block.txt_mlp[0].bias), wr(_w(block.txt_mlp[2].weight)), _b32(block.txt_mlp[2].bias)),
             mod_layers=[_mod_layer(block.img_mod), _mod_layer(block.txt_mod)],
-            pv8=bool(getattr(block, "_osk_fp8", False)),
+            pv8=bool(getattr(block, "_osk_fp8", False)), qk8=bool(getattr(block, "_osk_qk8", False)),
         )
         hd = block.head_dim if hasattr(block, "head_dim") else block.hidden_size // block.num_heads
         p.score_bound = _score_bound(hd, (p.img.q_scale, p.txt.q_scale), (p.img.k_scale, p.txt.k_scale))
@@ -466,7 +468,8 @@ def plan_single(block) -> _SinglePlan:
         wr = _wrap_for(block)
         p = _SinglePlan(wr(w1), b1, wr(_w(block.linear2.weight)), _b32(block.linear2.bias),
                         _w(block.norm.query_norm.scale), _w(block.norm.key_norm.scale),
-                        mod_layers=[_mod_layer(block.modulation)], pv8=bool(getattr(block, "_osk_fp8", False)))
+                        mod_layers=[_mod_layer(block.modulation)], pv8=bool(getattr(block, "_osk_fp8", False)),
+                        qk8=bool(getattr(block, "_osk_qk8", False)))
         hd = block.head_dim if hasattr(block, "head_dim") else block.hidden_size // block.num_heads
         p.score_bound = _score_bound(hd, (p.q_scale,), (p.k_scale,))
         p.key = _param_key(block)
@@ -615,9 +618,10 @@ def _bf16_operands(*xs) -> bool:
 
 
 def _joint_attention(ws: _Workspace, q: Tensor, k: Tensor, v: Tensor, H: int, hd: int, pv8: bool = False,
-                     score_bound: float = 0.0, vt_ready: bool = False):
+                     score_bound: float = 0.0, vt_ready: bool = False, qk8: bool = False):
     """attention() of math.py:22-36 on the joint [txt;img] sequence; the output overwrites the (dead) v slot.
     pv8 (fp8 mode, head_dim 72 / 128): V^T as e4m3 with one scale per (batch, head), P.V on the fp8 MFMA.
+    qk8 (with pv8, head_dim 128 only; any other head dim takes the pv8 path): K as e4m3 too, QK^T on the fp8 MFMA.
     vt_ready: ws.vt was already written by the projection (osk_gemm_group_bf16's V^T task) -- v then only names the output slot."""
     wsp = _OPS.attention_workspace(q.device)
     if pv8 and hd in (72, 128):
@@ -627,6 +631,14 @@ def _joint_attention(ws: _Workspace, q: Tensor, k: Tensor, v: Tensor, H: int, hd
             vt8 = ws.vt8 = torch.empty(B, H, _OPS.vt8_rows(hd), ws.vt.shape[-1], dtype=torch.uint8, device=v.device)
         sv = v_scale_fp8(v, H, hd)
         _OPS.v_transpose_fp8(v, sv, vt8, H, hd)
+        if qk8 and hd == 128:
+            k8 = getattr(ws, "k8", None)
+            if k8 is None or tuple(k8.shape) != _OPS.k8_shape(B, H, k.shape[1], hd):
+                k8 = ws.k8 = torch.empty(_OPS.k8_shape(B, H, k.shape[1], hd), dtype=torch.uint8, device=k.device)
+            sk = v_scale_fp8(k, H, hd)
+            _OPS.k_pack_fp8(k, sk, k8, H, hd)
+            _OPS.attention_fwd_qk8(q, k8, sk, vt8, sv, v, H, hd, hd ** -0.5, seg_len=k.shape[1], q_prescaled=True, workspace=wsp)
+            return
         _OPS.attention_fwd_pv8(q, k, vt8, sv, v, H, hd, hd ** -0.5, q_prescaled=True, workspace=wsp)
         return
     if not vt_ready:
@@ -698,7 +710,7 @@ def run_double_block(plan: _DoublePlan, ws: _Workspace, mod: Tensor, col_img: in
             _linear(act, aw.qkv_w, aw.qkv_b, y_s)
     if sp is None:
         _OPS.qknorm_rope(q, k, *scales, Lt, rope.cos, rope.sin, csb, H, hd, rope.mode, q_mult=q_mult(hd))
-        _joint_attention(ws, q, k, v, H, hd, plan.pv8, plan.score_bound, vt_ready)
+        _joint_attention(ws, q, k, v, H, hd, plan.pv8, plan.score_bound, vt_ready, qk8=plan.qk8)
     else:
         # K, V first: their exchange overlaps the Q projection.  All-gather mode, bf16: V goes straight into this rank's slot of the
         # gathered V^T buffer (osk_gemm_group_bf16's V^T task, round 6) -- no token-major V, no osk_v_transpose_bf16 pass on the rank
@@ -774,7 +786,7 @@ def run_single_block(plan: _SinglePlan, ws: _Workspace, mod: Tensor, col: int, r
         if not vt_ready:
             _linear(act, plan.w1, plan.b1, y, gelu_from=3 * D)
         _OPS.qknorm_rope(q, k, *scales, 0, rope.cos, rope.sin, csb, H, hd, rope.mode, q_mult=q_mult(hd))
-        _joint_attention(ws, q, k, v, H, hd, plan.pv8, plan.score_bound, vt_ready)
+        _joint_attention(ws, q, k, v, H, hd, plan.pv8, plan.score_bound, vt_ready, qk8=plan.qk8)
     else:
         b1 = plan.b1
         vt_ready = False
@@ -938,13 +950,18 @@ class MMDiTModel(_OskState, nn.Module):
         self.forward = self.forward_ckpt  # instance attribute, as the reference does (model.py:143-146)
 
     # ------------------------------------------------------------------ fp8 mode
-    def enable_fp8(self, on: bool = True):
+    def enable_fp8(self, on: bool = True, qk8: bool = False):
         """Opt-in reduced-precision mode (BASELINE configs[4], "fp8 MFMA"): the Linear layers of the double / single
         blocks (QKV, proj, MLP, linear1, linear2 -- >99 % of the GEMM FLOPs) run on the fp8 MFMA with per-row dynamic
         activation scales and per-output-row weight scales; attention, norms, modulation, embedders and the final
-        layer stay bf16.  The reference computes in bf16: results differ by the e4m3 quantisation error."""
+        layer stay bf16.  The reference computes in bf16: results differ by the e4m3 quantisation error.
+        qk8 (opt-in on top, head_dim 128): the attention's QK^T runs on the fp8 MFMA as well -- K packed to e4m3 per (batch, head),
+        Q per (row, head) inside the kernel (osk_attention_fwd_qk8_bf16).  Any other head dim, and every call under sequence
+        parallelism, keeps the pv8 attention.  Recommended for head_dim 128: the attention launch takes 0.77 - 0.79 of the pv8 time
+        with the K pack counted (A/B spread under 2 %) at the same model-level error; DESIGN.md section 4, profiles/attn_qk8.md."""
         for b in list(self.double_blocks) + list(self.single_blocks):
             object.__setattr__(b, "_osk_fp8", bool(on))
+            object.__setattr__(b, "_osk_qk8", bool(on and qk8))
         self.invalidate_plan()
         return self
 

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Generator of the hand-scheduled gfx950 main loops of the flash-attention kernels for head_dim 72
 (open_sora_amd/csrc/attention_asm72.hip includes the emitted attention_asm72_n{NU}_v{VAR}.inc) and head_dim 128
-(attention_asm128.hip, attention_asm128_n2_v{VAR}.inc); class Geometry holds what differs between the two.
+(attention_asm128.hip, attention_asm128_n2_v{VAR}.inc; fp8 P.V: attention_asm{72,128}p8; fp8 QK^T as well: attention_asm128q8, the
+`qk8` flag of Geometry / Layout); class Geometry holds what differs between them.
 
 Why a generator: the MFMA shadow (32 cycles, ~5 issue slots) has to be filled by hand; hipcc's scheduler clusters
 the softmax VALU work behind the MFMAs and shuffles accumulators between the VGPR and AGPR halves
@@ -50,8 +51,15 @@ class Geometry:
     hd 128: 8 real k-steps + 1 pure padding step whose K fragment is a CONSTANT register quad {1.0, 0...} (no LDS
             read) and whose Q fragment carries M; 4 real O^T row tiles + a 5th that only holds the ones row 128."""
 
-    def __init__(self, hd, pv8=False, pv16=False, nom=False):
+    def __init__(self, hd, pv8=False, pv16=False, nom=False, qk8=False):
         self.HD = hd
+        # qk8 (head_dim 128 with pv8): QK^T on the fp8 MFMA too.  K and Q are OCP e4m3: 2 k-steps of v_mfma_f32_32x32x64_f8f6f4 (64
+        # dims each) instead of 8 + 1 bf16 ones; the K tile is ONE swizzled image of 64 keys x 128 bytes (8 LDS-DMA instructions);
+        # a K / Q fragment is 8 registers (key / query l % 32, bytes 64 ks + 32 (l / 32) .. + 31).  No padding k-step: the scores
+        # leave the MFMA raw and one v_fma_f32 per score applies the lane's dequantisation factor c and the reference max M
+        # (s = c raw - M), in the P.V shadows in front of the max chains -- from there on the body is the pv8 one.
+        self.QK8 = qk8
+        assert not qk8 or (hd == 128 and pv8)
         # nom (head_dim 128 FAST body): no padding k-step at all.  That step exists only to carry the reference max through the
         # MFMA; with a score bound B <= 56 no reference is needed for range control -- P = exp2(s), |s| <= B, stays inside
         # [2^-56, 2^56] and every sum inside f32 -- so QK^T is 8 k-steps instead of 9 (72 instead of 76 MFMAs per tile)
@@ -76,8 +84,12 @@ class Geometry:
             self.NKD = self.NVD = 16
         else:
             raise ValueError(hd)
+        self.QW = 4                              # registers of a K / Q fragment
+        if qk8:
+            self.NKS, self.KIMG, self.NKD, self.QW = 2, 1, 8, 8
+            self.M_KS = None                     # no padding k-step: M lives in a register
         self.NPK = 2 * (self.NKS - (1 if nom else 0))   # QK^T fragment pairs (k-step, 32-key half)
-        self.NPK_READ = 2 * (self.NKS - (0 if self.HAS_COL else 1))   # ... that are read from LDS
+        self.NPK_READ = self.NPK if qk8 else 2 * (self.NKS - (0 if self.HAS_COL else 1))   # ... that are read from LDS
         self.KTILE = self.KIMG * 8192 + (1024 if self.HAS_COL else 0)
         if pv8:
             # V^T tile in e4m3: 64-byte rows (64 keys), ONE fp8 MFMA (K = 64) per O^T row tile.  The global tensor
@@ -135,8 +147,9 @@ def operand_names(geo, nslot_k, nslot_v):
     """asm operands (order = operand numbers in the wrapper's asm statement); at most 30"""
     names = ["m0out", "m1out"] + ["koff%d" % i for i in range(nslot_k)] + ["voff%d" % i for i in range(nslot_v)] + \
             ["fo0", "fo1", "fo2", "fo3"] + (["kc0", "kc1"] if geo.HAS_COL else []) + \
-            ["koffL%d" % i for i in range(nslot_k)] + \
+            ([] if geo.QK8 else ["koffL%d" % i for i in range(nslot_k)]) + \
             (["vf0", "vf1"] if geo.PV8 else ["maskval", "onesaddr"]) + \
+            (["c0", "c1"] if geo.QK8 else []) + \
             (["vo0", "vo1"] if geo.PV16 else []) + \
             ["kbase", "vbase", "kstep", "kjump", "vjump"] + (["tpsnt"] if geo.PV16 else ["tps", "nt"]) + ["kdst", "vdst"]
     # the K loader's conditional last slot only exists when 4 | NKD does not hold; otherwise no slot count is needed
@@ -154,7 +167,7 @@ def ar(base, n=1):
     return "a%d" % base if n == 1 else "a[%d:%d]" % (base, base + n - 1)
 
 
-N2_BUDGET = {"m32": 24, "pv16": 9, "pv8": 60}   # filler cycles per MFMA shadow of the 256-row bodies (round 5: 24 / 9 instead of 30 / 13, as in
+N2_BUDGET = {"m32": 24, "pv16": 9, "pv8": 60, "qk8": 96}   # filler cycles per MFMA shadow of the 256-row bodies (round 5: 24 / 9 instead of 30 / 13, as in
 # the wide body -- the MFMA's own issue takes 4.4 cycles of its shadow; --n2-budget: experiments)
 FAST_WINDOWS_OVERRIDE = {}   # (hd, nu) -> [a0, a1, b0, b1, c0, c1]; set by --fast-windows (experiments) or below (production)
 
@@ -162,10 +175,13 @@ FAST_WINDOWS_OVERRIDE = {}   # (hd, nu) -> [a0, a1, b0, b1, c0, c1]; set by --fa
 class Layout:
     """register file and schedule geometry for NU query blocks per wave"""
 
-    def __init__(self, nu, hd=72, pv8=False, pv16=False, nom=False):
+    def __init__(self, nu, hd=72, pv8=False, pv16=False, nom=False, qk8=False):
         self.NU = nu
-        self.G = G = Geometry(hd, pv8, pv16, nom)
+        self.G = G = Geometry(hd, pv8, pv16, nom, qk8)
         self.PV8 = pv8
+        self.QK8 = qk8
+        assert not qk8 or nu == 2
+        self.KRD = 2 if qk8 else 4             # depth of the K fragment ring, in QK^T pairs (qk8: 2 slots x 8 registers)
         self.PV16 = pv16
         self.MPP = 2 * nu if pv16 else nu      # MFMAs per P.V pair (pv16: query blocks of 16: two per 32-row block u)
         NKS, NDT = G.NKS, G.NDT
@@ -180,7 +196,7 @@ class Layout:
         self.RD = 2 if pv8 else 4              # depth of the V^T fragment ring, in P.V pairs
         self.NTP = 1 if pv8 else 2             # P.V pairs whose MFMAs trail across the tile barrier
         self.V_FIRST = 48 if G.HAS_COL else 44
-        self.KC0 = None if G.HAS_COL else 44   # constant K fragment of the padding k-step: 4 registers
+        self.KC0 = None if (G.HAS_COL or qk8) else 44   # constant K fragment of the padding k-step: 4 registers
         self.SA0 = 48
         self.SB0 = self.SA0 + 32 * nu
         self.PB0 = self.SB0 + 32 * nu
@@ -194,7 +210,7 @@ class Layout:
         self.V_END = self.TMP0 + 16
         self.A_O0 = 0
         self.A_Q0 = (4 * G.NDB * 2 * nu) if pv16 else 16 * NDT * nu
-        self.A_END = self.A_Q0 + 4 * NKS * nu
+        self.A_END = self.A_Q0 + G.QW * NKS * nu
         self.NTRAIL = self.NTP * self.MPP      # MFMAs of the trailing P.V pairs
         self.NQK = G.NPK * nu
         self.NPVB = (G.NPV - self.NTP) * self.MPP    # P.V MFMAs inside the body
@@ -209,6 +225,8 @@ class Layout:
             # (64-cycle) P.V MFMAs
             self.WINDOWS = [self.I_QK0, self.I_PV0 - 3, self.I_QK0 + self.NQK // 2, self.I_PV0 - 2, self.I_PV0 + 1, last]
             self.C_T2_RELEASE = self.I_PV0 + 2
+            if qk8:   # 8 QK^T shadows of 64 cycles carry all 64 exp2 + 32 packs (640 cycles of VALU): paced evenly up to the last one
+                self.WINDOWS = [self.I_QK0, self.I_PV0 - 1, self.I_QK0 + 2, self.I_PV0 - 1, self.I_PV0 + 1, last]
         elif pv16:
             # shadows: 8 trailing P.V (16 cycles) | 20 QK^T (32 cycles) from I_QK0 = 8 | 32 P.V from I_PV0 = 28; class A = exp2 +
             # pack + lane-row swaps of keys 0..31 (before the first P.V MFMA, shadow 28), B = keys 32..63 (before pair 5,
@@ -243,7 +261,7 @@ class Layout:
         return self.A_O0 + ((u * 2 + qb) * self.G.NDB + db) * 4
 
     def AQ(self, u, ks):
-        return self.A_Q0 + (u * self.G.NKS + ks) * 4
+        return self.A_Q0 + (u * self.G.NKS + ks) * self.G.QW
 
 
 class Stream:
@@ -285,6 +303,8 @@ class Stream:
 # ------------------------------------------------------------------------------------------ pieces
 def k_frag(L, p):
     """register quad that holds the K fragment of pair p: a ring slot, or the constant padding fragment (hd 128)"""
+    if L.QK8:
+        return L.KR0 + (p % 2) * 8
     return L.KR0 + (p % 4) * 4 if p < L.G.NPK_READ else L.KC0
 
 
@@ -292,6 +312,11 @@ def k_read(st, L, slot, p, tag):
     """K fragment of pair p = (ks, t2) of the tile in ring slot `slot` -> K ring"""
     ks, t2 = p // 2, p % 2
     assert p < L.G.NPK_READ
+    if L.QK8:   # key row 32 t2 + l % 32, bytes 64 ks + 32 (l / 32) .. + 31 = two swizzled 16-byte chunks (fo[2 ks], fo[2 ks + 1])
+        dst = k_frag(L, p)
+        st.ds_read(dst, L.OP["fo%d" % (2 * ks)], L.G.KOFF[slot] + t2 * 4096, ("kx", tag[1]))
+        st.ds_read(dst + 4, L.OP["fo%d" % (2 * ks + 1)], L.G.KOFF[slot] + t2 * 4096, tag)
+        return
     dst = L.KR0 + (p % 4) * 4
     if ks < 4 * L.G.KIMG:
         st.ds_read(dst, L.OP["fo%d" % (ks % 4)], L.G.KOFF[slot] + (ks // 4) * 8192 + t2 * 4096, tag)
@@ -317,6 +342,10 @@ def qk_mfma(st, L, sn, a):
     p, u = a // L.NU, a % L.NU
     ks, t2 = p // 2, p % 2
     dst = vr(L.S(sn, u, t2), 16)
+    if L.QK8:
+        st.emit("v_mfma_f32_32x32x64_f8f6f4 %s, %s, %s, %s" % (dst, vr(k_frag(L, p), 8), ar(L.AQ(u, ks), 8),
+                                                             "0" if ks == 0 else dst), "Q")
+        return
     st.emit("v_mfma_f32_32x32x16_bf16 %s, %s, %s, %s" % (dst, vr(k_frag(L, p), 4), ar(L.AQ(u, ks), 4),
                                                        "0" if ks == 0 else dst), "M")
 
@@ -404,6 +433,13 @@ def _check_swap_distance(st):
                 assert n - last_swap.get(r, -99) > 2, "MFMA too close behind the swap of v%d" % r
 
 
+def dequant(L, sn, u, t2):
+    """qk8: the 16 raw scores of (block u, key half t2) -> log2 units relative to the reference max: s = c raw - M, one v_fma_f32
+    each (c = q scale x K scale of the lane's query, an asm operand; M in its register)"""
+    return [("v", "v_fma_f32 %s, %s, %s, -%s" % (vr(L.S(sn, u, t2, r)), vr(L.S(sn, u, t2, r)), L.OP["c%d" % u], vr(L.MM[u])))
+            for r in range(16)]
+
+
 def max_chain(L, sn, u, t2, tmp):
     x = lambda r: vr(L.S(sn, u, t2, r))
     ops = [("v", "v_max3_f32 %s, %s, %s, %s" % (vr(tmp), x(0), x(1), x(2)))]
@@ -450,12 +486,15 @@ def k_dma(st, L, slot, i, part=3):
     of a key segment (lane mask S_KRG) the rows past the segment re-fetch its last key (offsets koffL)."""
     if part & 1:
         st.emit("s_add_u32 m0, s%d, %d" % (S_KDST, L.G.KOFF[slot] + 1024 * L.NW * i), "s")
-        if not FAST:
+        if L.QK8:     # the packed K tensor repeats a segment's last key up to the tile boundary: one set of offsets
+            if part == 3:
+                st.emit("s_nop 0", "n")
+        elif not FAST:
             st.emit("v_cndmask_b32_e64 %s, %s, %s, s[%d:%d]" % (vr(L.TX[3]), L.OP["koff%d" % i], L.OP["koffL%d" % i], S_KRG, S_KRG + 1), "v")
         elif part == 3:
             st.emit("s_nop 0", "n")
     if part & 2:   # FAST: the offsets in force (koff, or koffL while the loader sits on a ragged tile) live in KCUR registers
-        st.emit("global_load_lds_dwordx4 %s, s[%d:%d]" % (vr(L.KCUR + i) if FAST else vr(L.TX[3]), S_KB, S_KB + 1), "g")
+        st.emit("global_load_lds_dwordx4 %s, s[%d:%d]" % (L.OP["koff%d" % i] if L.QK8 else (vr(L.KCUR + i) if FAST else vr(L.TX[3])), S_KB, S_KB + 1), "g")
 
 
 def v_dma(st, L, slot, i, part=3):
@@ -700,11 +739,12 @@ def fixup(st, L, sx, init):
         if not init:
             st.emit("v_exp_f32 %s, %s" % (vr(al), vr(de)))                      # alpha = 2^(M_old - M_new)
         # Q's padding dim that carries -M: word 0 of the k-step-M_KS fragment, in the half-wave S_HIM selects
-        st.emit("v_accvgpr_read_b32 %s, %s" % (vr(t), ar(L.AQ(u, L.G.M_KS))))
-        st.emit("s_nop 0", "n")
-        st.emit("v_cndmask_b32_e64 %s, %s, %s, s[%d:%d]" % (vr(t), vr(t), vr(pk), S_HIM, S_HIM + 1))
-        st.emit("s_nop 0", "n")
-        st.emit("v_accvgpr_write_b32 %s, %s" % (ar(L.AQ(u, L.G.M_KS)), vr(t)))
+        if not L.QK8:   # (qk8: M is applied by the dequantisation FMA out of its register)
+            st.emit("v_accvgpr_read_b32 %s, %s" % (vr(t), ar(L.AQ(u, L.G.M_KS))))
+            st.emit("s_nop 0", "n")
+            st.emit("v_cndmask_b32_e64 %s, %s, %s, s[%d:%d]" % (vr(t), vr(t), vr(pk), S_HIM, S_HIM + 1))
+            st.emit("s_nop 0", "n")
+            st.emit("v_accvgpr_write_b32 %s, %s" % (ar(L.AQ(u, L.G.M_KS)), vr(t)))
         for t2 in range(2):
             for r in range(16):
                 x = vr(L.S(sx, u, t2, r))
@@ -777,7 +817,7 @@ def body(st, L, k, safe):
     uid = "b%d" % k
     st.label(".L@@_body%d" % k)
     # -- top: K fragment reads of pairs 0..3 (tile t+1 sits in ring slot cur^1)
-    for p in range(4):
+    for p in range(L.KRD):
         k_read(st, L, cur ^ 1, p, ("k", p))
     # -- trailing P.V MFMAs of tile t-1 (the last two fragment pairs were read before the barrier); in their shadows the
     #    first LDS-DMA pieces of K(t+2) -> slot cur and V(t+1) -> slot cur^1 (M0 write BEFORE the MFMA: no s_nop)
@@ -825,8 +865,9 @@ def body(st, L, k, safe):
         if L.PV16 and g % 2 == 1:
             for u in range(NU):
                 (clsA if g < 2 else clsB).extend(swap_group(L, u, g // 2))
-    ca = [max_chain(L, sn, u, 0, chain_tmp(L, u, 0)) for u in range(NU)]
-    cb = [max_chain(L, sn, u, 1, chain_tmp(L, u, 1)) for u in range(NU)]
+    dq = (lambda u, t2: dequant(L, sn, u, t2)) if L.QK8 else (lambda u, t2: [])
+    ca = [dq(u, 0) + max_chain(L, sn, u, 0, chain_tmp(L, u, 0)) for u in range(NU)]
+    cb = [dq(u, 1) + max_chain(L, sn, u, 1, chain_tmp(L, u, 1)) for u in range(NU)]
     clsC.extend([o for grp in zip(*ca) for o in grp])
     n_first_b = len(clsC)
     clsC.extend([o for grp in zip(*cb) for o in grp])
@@ -844,6 +885,9 @@ def body(st, L, k, safe):
         if kind == "pv" and L.PV8:
             if u == 0:
                 st.need(("v", pair))
+        elif L.QK8:
+            if u == 0:
+                st.need(("k", pair))
         elif u == 0 and pair % 2 == 0:   # pairs 2m and 2m+1 with one wait (both were issued >= 3 pairs ago)
             st.need(("k" if kind == "qk" else "v", pair + 1))
         if kind == "qk":
@@ -857,11 +901,11 @@ def body(st, L, k, safe):
         if u == per - 1:
             if kind == "qk":
                 NR = L.G.NPK_READ
-                if pair + 4 < NR:
-                    k_read(st, L, cur ^ 1, pair + 4, ("k", pair + 4))
-                    used += 4
-                elif pair < NR and pair + 4 - NR < L.RD:
-                    v_read(st, L, cur, pair + 4 - NR, ("v", pair + 4 - NR))   # first V pairs behind the last K pairs
+                if pair + L.KRD < NR:
+                    k_read(st, L, cur ^ 1, pair + L.KRD, ("k", pair + L.KRD))
+                    used += 8 if L.QK8 else 4
+                elif pair < NR and pair + L.KRD - NR < L.RD:
+                    v_read(st, L, cur, pair + L.KRD - NR, ("v", pair + L.KRD - NR))   # first V pairs behind the last K pairs
                     used += 8 if L.PV8 else 4
             elif pair + L.RD < L.G.NPV:
                 v_read(st, L, cur, pair + L.RD, ("v", pair + L.RD))
@@ -881,7 +925,8 @@ def body(st, L, k, safe):
                     break
                 if totals[ci] * frac - c[4] <= 0 and i < last:
                     break
-                if used >= (N2_BUDGET["pv8"] if kind == "pv" and L.PV8 else (N2_BUDGET["pv16"] if kind == "pv" and L.PV16 else N2_BUDGET["m32"])) and i < last:
+                if used >= (N2_BUDGET["pv8"] if kind == "pv" and L.PV8 else (N2_BUDGET["pv16"] if kind == "pv" and L.PV16 else
+                                                                              (N2_BUDGET["qk8"] if L.QK8 else N2_BUDGET["m32"]))) and i < last:
                     break
                 st.emit(text, kind_)
                 used += cost(kind_)
@@ -943,9 +988,10 @@ def _generate(L, safe, ablate):
         e("s_mov_b32 s%d, 0" % (S_HIM + 1))
         e("s_mov_b32 s%d, 0" % S_HI2)
         e("s_mov_b32 s%d, -1" % (S_HI2 + 1))
-        e("v_mov_b32 %s, 0x3f80" % vr(L.KC0))          # K fragment of the padding k-step: dim HD = 1.0, the rest 0
-        for i in range(1, 4):
-            e("v_mov_b32 %s, 0" % vr(L.KC0 + i))
+        if L.KC0 is not None:
+            e("v_mov_b32 %s, 0x3f80" % vr(L.KC0))          # K fragment of the padding k-step: dim HD = 1.0, the rest 0
+            for i in range(1, 4):
+                e("v_mov_b32 %s, 0" % vr(L.KC0 + i))
     # nvw = valid V^T loader slots | (no ragged tile in this launch) << 8 | (this wave maintains the ones rows) << 9
     e("s_lshr_b32 s%d, s%d, 8" % (S_FLG, S_NVW))
     e("s_and_b32 s%d, s%d, 1" % (S_NRG, S_FLG))
@@ -978,15 +1024,15 @@ def _generate(L, safe, ablate):
     if not FAST:   # (fast: Q's padding dim already carries the bound, the scores above are final)
         for t2 in range(2):
             for u in range(L.NU):
-                for op in max_chain(L, L.SA0, u, t2, chain_tmp(L, u, t2)):
-                    e(op[1])
+                for op in (dequant(L, L.SA0, u, t2) if L.QK8 else []) + max_chain(L, L.SA0, u, t2, chain_tmp(L, u, t2)):
+                    e(op[1])     # (qk8: M == 0 here, the scores become c raw)
         fixup(st, L, L.SA0, init=True)
     # what body 0 does before its entry point: the first LDS-DMA pieces of K(2) -> slot 0 and V(1) -> slot 1 (the
     # same ones body() puts into the trailing shadows), the first K fragment reads of tile 1
     pieces = body(Stream(), L, 0, False)
     for w, i in pieces:
         (k_dma if w == "k" else v_dma)(st, L, 0 if w == "k" else 1, i)
-    for p in range(4):
+    for p in range(L.KRD):
         k_read(st, L, 1, p, ("k", p))
     e("s_branch .L@@_entry0")
     # ---- the two loop bodies
@@ -1308,6 +1354,7 @@ def main():
     ap.add_argument("--table", type=int, default=0, help="print the schedule of layout NU (1 or 2) shadow by shadow")
     ap.add_argument("--hd", type=int, default=72, help="head dim of the schedule --table prints")
     ap.add_argument("--pv8", action="store_true", help="--table: the fp8 P.V variant")
+    ap.add_argument("--qk8", action="store_true", help="--table: the fp8 QK^T + fp8 P.V variant (head_dim 128, layout 2; implies --pv8)")
     ap.add_argument("--exp", default="", help="emit an EXPERIMENTAL body in place of the production one (never into the shipped tree: "
                     "point --out at a scratch copy of csrc, see tools/make_ablated_libs.sh): safe = hazard-padded debug schedule | "
                     "dmagapN[cC] = LDS-DMA items every N shadows | timing ablations joined by + (noexp nobar nodma nolds novalu "
@@ -1346,9 +1393,9 @@ def main():
             FAST_WINDOWS_OVERRIDE[(int(hd_), 2)] = w_ + [w_[3], w_[3]]
     # shipped: the 4 waves x 64 rows layout (NU = 2) of both head dims, bf16 and fp8 P.V.  The 8 waves x 32 rows layout
     # (NU = 1, head_dim 72) tied it in rounds 1-2 and stays a generator option (--table 1) without a shipped body.
-    layouts = [(72, 2, False), (128, 2, False), (72, 2, True), (128, 2, True)]
-    mk = lambda nu, hd, pv8: Layout(nu, hd, pv8, pv16=(hd == 72 and not pv8 and not args.no_pv16))
-    tagof = lambda hd, pv8: "%d%s" % (hd, "p8" if pv8 else "")
+    layouts = [(72, 2, False, False), (128, 2, False, False), (72, 2, True, False), (128, 2, True, False), (128, 2, True, True)]
+    mk = lambda nu, hd, pv8, qk8=False: Layout(nu, hd, pv8, pv16=(hd == 72 and not pv8 and not args.no_pv16), qk8=qk8)
+    tagof = lambda hd, pv8, qk8=False: "%d%s" % (hd, "q8" if qk8 else ("p8" if pv8 else ""))
     global DMAGAP, DMACOST
     safe = args.exp == "safe"
     gap = args.exp.startswith("dmagap")
@@ -1356,11 +1403,11 @@ def main():
     if (args.exp or args.fast_windows or args.fast_exp or args.no_pv16 or args.wide_exp or args.n2_budget) and os.path.realpath(args.out) == os.path.realpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "open_sora_amd", "csrc")):
         raise SystemExit("--exp bodies are experiments: give --out a scratch directory, not the shipped csrc")
     if args.table:
-        L = mk(args.table, args.hd, args.pv8) if args.table == 2 else Layout(args.table, args.hd, args.pv8)
+        L = mk(args.table, args.hd, args.pv8 or args.qk8, args.qk8) if args.table == 2 else Layout(args.table, args.hd, args.pv8)
         st = generate(L, False, frozenset())
         row = []
         for kind, text in st.table:
-            if kind in ("M", "F", "X"):
+            if kind in ("M", "F", "X", "Q"):
                 print("".join(row)); row = [kind + " "]
             elif kind == "L":
                 print("".join(row)); row = []; print(text + ":")
@@ -1368,8 +1415,8 @@ def main():
                 row.append({"x": "v"}.get(kind, kind))
         print("".join(row))
         return
-    for hd, nu, pv8 in layouts:
-        L = mk(nu, hd, pv8)
+    for hd, nu, pv8, qk8 in layouts:
+        L = mk(nu, hd, pv8, qk8)
         DMAGAP, DMACOST = 1, 12
         if gap:
             spec = args.exp[len("dmagap"):].split("c")
@@ -1378,11 +1425,11 @@ def main():
         DMAGAP, DMACOST = 1, 12
         what = "production" if not args.exp else ("hazard-padded (debug)" if safe else ("schedule experiment " + args.exp if gap else
                                                                                          "timing ablation " + "+".join(sorted(ablate))))
-        with open(os.path.join(args.out, "attention_asm%s_n%d_v0.inc" % (tagof(hd, pv8), nu)), "w") as f:
+        with open(os.path.join(args.out, "attention_asm%s_n%d_v0.inc" % (tagof(hd, pv8, qk8), nu)), "w") as f:
             f.write("// GENERATED by tools/gen_attn_asm.py -- do not edit.  head_dim %d%s, layout NU=%d: %s\n" %
-                    (hd, ", fp8 P.V" if pv8 else "", nu, what))
+                    (hd, ", fp8 QK^T and P.V" if qk8 else (", fp8 P.V" if pv8 else ""), nu, what))
             for ln in st.lines:
-                f.write('"%s\\n"\n' % ln.replace("@@", "osk%sn%dv0_%%=" % (tagof(hd, pv8), nu)))
+                f.write('"%s\\n"\n' % ln.replace("@@", "osk%sn%dv0_%%=" % (tagof(hd, pv8, qk8), nu)))
         if not pv8:   # the bounded / single-segment / whole-tile body of the same layout
             fexp = args.fast_exp or args.exp
             if fexp.startswith("dmagap"):
@@ -1419,18 +1466,18 @@ def main():
             for qb in range(2):
                 assert all(LW.AO16W(u, qb, db) == 4 * LW.G.NDB * (2 * u + qb) + 4 * db for db in range(LW.G.NDB))
         f.write("#define OSK72W_AO_REGS %d\n" % (4 * LW.G.NDB * 2 * LW.NUW))
-        for hd, pv8 in sorted({(h, p8) for h, _, p8 in layouts}):
-            G = mk(2, hd, pv8).G
-            P = "OSK%s_" % tagof(hd, pv8).upper()
+        for hd, pv8, qk8 in sorted({(h, p8, q8) for h, _, p8, q8 in layouts}):
+            G = mk(2, hd, pv8, qk8).G
+            P = "OSK%s_" % tagof(hd, pv8, qk8).upper()
             f.write("#define %sSMEM %d\n#define %sCONST_OFF %d\n" % (P, G.SMEM, P, G.CONST_OFF))
             f.write("#define %sKTILE %d\n#define %sVTILE %d\n#define %sVOFF0 %d\n#define %sKOFF0 %d\n" % (P, G.KTILE, P, G.VTILE, P, G.VOFF[0], P, G.KOFF[0]))
             f.write("#define %sNKS %d\n#define %sNDT %d\n#define %sNKD %d\n#define %sKIMG %d\n" % (P, G.NKS, P, G.NDT, P, G.NKD, P, G.KIMG))
             if pv8:
                 f.write("#define %sRP %d\n#define %sNVD %d\n" % (P, G.RP, P, G.NVD))
-        for hd, nu, pv8 in layouts:
-            L = mk(nu, hd, pv8)
+        for hd, nu, pv8, qk8 in layouts:
+            L = mk(nu, hd, pv8, qk8)
             G = L.G
-            P = "OSK%sN%d_" % (tagof(hd, pv8).upper(), nu)
+            P = "OSK%sN%d_" % (tagof(hd, pv8, qk8).upper(), nu)
             if L.PV16:
                 f.write("#define %sPV16 1\n#define OSK%s_NDB %d\n" % (P, tagof(hd, pv8).upper(), G.NDB))
             clob = ['"v%d"' % i for i in range(L.V_FIRST, L.V_END)] + ['"a%d"' % i for i in range(0, L.A_END)] + \
@@ -1443,6 +1490,8 @@ def main():
             # register map the wrapper binds as asm operands (acc_quads.h): Q fragment words of block u = AGPRs AQ(u) .. + 4 NKS
             for u in range(nu):
                 f.write("#define %sAQ%d %d\n" % (P, u, L.AQ(u, 0)))
+            if qk8:
+                f.write("#define %sA_END %d\n" % (P, L.A_END))
             if L.PV16:   # O^T of (u, 16-query block qb) = AGPRs 4 NDB (2 u + qb) .. (row block db, register i at + 4 db + i)
                 assert all(L.AO16(u, qb, db) == 4 * G.NDB * (2 * u + qb) + 4 * db for u in range(nu) for qb in range(2) for db in range(G.NDB))
                 f.write("#define %sAO_REGS %d\n" % (P, 4 * G.NDB * 2 * nu))

@@ -100,6 +100,65 @@ def attention_rank(dev, H, hd, P, Lloc, B, layout, fp8=False, iters=5, warm=2):
             "roofline": {"bound": "mfma", "achieved": round(ach, 1), "peak": peak, "unit": "TFLOP/s", "frac": round(ach / peak, 4)}}
 
 
+QK8_SHAPES = {   # (B, H, Lq, key segments, keys per segment)
+    "11b_bench": (3, 24, 16896, 1, 16896),        # the 11B bench shape (one GPU, CFG triple)
+    "cfg4_rank": (1, 24, 28864, 8, 28864),        # a rank of BASELINE configs[4]: L / 8 query rows against 8 gathered key segments
+}
+
+
+def attention_qk8_ab(dev, name, rounds=5, iters=3, warm=2):
+    """pv8 against qk8 (fp8 QK^T as well) at head_dim 128, same operands, one process: warm back-to-back launches, the two entries
+    ALTERNATING round by round so that clock and neighbour drift hits both; per entry the median of the rounds' medians and the
+    rounds' own spread (max - min) / median.  Also the K scale + pack pass qk8 adds (once per key tensor)."""
+    from open_sora_amd import _C
+
+    B, H, Lq, P, Lloc = QK8_SHAPES[name]
+    hd, D = 128, H * 128
+    g = torch.Generator(device=dev).manual_seed(5)
+    q = (_unit_rms(torch.randn(B, Lq, D, device=dev, generator=g), H, hd) * (hd ** -0.5 * LOG2E)).to(BF)
+    k = _unit_rms(torch.randn(P, B, Lloc, D, device=dev, generator=g), H, hd).to(BF)
+    v = torch.randn(P, B, Lloc, D, device=dev, generator=g).to(BF)
+    segp = (Lloc + 63) // 64 * 64
+    ws = _C.attention_workspace(q.device)
+    sv = (v.float().abs().view(P, B, Lloc, H, hd).amax(dim=(0, 2, 4)) / 448.0).contiguous()
+    vt8 = torch.zeros(P, B, H, _C.vt8_rows(hd), segp, dtype=torch.uint8, device=dev)
+    k8 = torch.zeros(P, *_C.k8_shape(B, H, Lloc), dtype=torch.uint8, device=dev)
+    for s_ in range(P):
+        _C.v_transpose_fp8(v[s_], sv, vt8[s_], H, hd)
+
+    def pack():
+        sk = _C.v_scale_fp8(k.view(P * B, Lloc, D), H, hd).view(P, B, H).amax(0).contiguous() if P > 1 else _C.v_scale_fp8(k[0], H, hd)
+        for s_ in range(P):
+            _C.k_pack_fp8(k[s_], sk, k8[s_], H, hd)
+        return sk
+
+    sk = pack()
+    outs = {n: torch.empty(B, Lq, D, dtype=BF, device=dev) for n in ("pv8", "qk8")}
+    fns = {"pv8": lambda: _C.attention_fwd_pv8(q, k[0], vt8, sv, outs["pv8"], H, hd, hd ** -0.5, n_seg=P, seg_len=Lloc, k_seg_stride=k.stride(0),
+                                                vt_seg_stride=vt8.stride(0), q_prescaled=True, workspace=ws),
+           "qk8": lambda: _C.attention_fwd_qk8(q, k8[0], sk, vt8, sv, outs["qk8"], H, hd, hd ** -0.5, seg_len=Lloc, n_seg=P,
+                                                k_seg_stride=k8.stride(0), vt_seg_stride=vt8.stride(0), q_prescaled=True, workspace=ws)}
+    ms = {n: [] for n in fns}
+    for r in range(rounds):
+        for n in (("pv8", "qk8") if r % 2 == 0 else ("qk8", "pv8")):
+            ms[n].append(_events(fns[n], iters, warm))
+    t_pack = _events(pack, 5, 2)
+    assert all(torch.isfinite(o.float()).all() for o in outs.values())
+    rel = ((outs["qk8"].double() - outs["pv8"].double()).norm() / outs["pv8"].double().norm()).item()
+    fl = 4.0 * B * H * Lq * (P * Lloc) * hd
+    med = lambda x: sorted(x)[len(x) // 2]
+    res = {"shape": {"B": B, "H": H, "Lq": Lq, "n_seg": P, "seg_len": Lloc}, "flops_per_launch": fl, "k_scale_pack_ms": round(t_pack, 3),
+           "rel_l2_qk8_vs_pv8": round(rel, 5)}
+    for n, peak in (("pv8", 2.0 / (1.0 / PEAK_BF16 + 1.0 / PEAK_FP8)), ("qk8", PEAK_FP8)):
+        m = med(ms[n])
+        res[n] = {"ms_per_launch": round(m, 3), "rounds_ms": [round(x, 3) for x in ms[n]], "spread": round((max(ms[n]) - min(ms[n])) / m, 4),
+                  "tflops": round(fl / m / 1e9, 1), "peak": round(peak, 1), "frac_of_peak": round(fl / m / 1e9 / peak, 4)}
+    res["pv8"]["peak_is"] = "mixed: QK^T at the bf16 MFMA rate, P.V at the fp8 rate, equal FLOP shares"
+    res["qk8"]["peak_is"] = "fp8 MFMA rate for both products"
+    res["qk8_plus_pack_vs_pv8"] = round((res["qk8"]["ms_per_launch"] + t_pack) / res["pv8"]["ms_per_launch"], 4)
+    return res
+
+
 def block_gemms_rank(dev, D, M, fp8=False, iters=8, warm=3):
     """the two Linear layers of a single-stream block (24 D^2 FLOP per token, the same count as a double block's five) at a
     rank's M rows: linear1 (N = 3 D + 4 D, GELU from column 3 D) and linear2 (K = 5 D, gate * x + residual, in place)"""
