@@ -7,6 +7,8 @@ import re
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "open_sora_amd", "csrc")
 TOOLS = os.path.join(ROOT, "tools")
@@ -246,8 +248,8 @@ def test_asm_accumulators_are_values_the_compiler_knows():
     the sources: no wrapper names an AGPR any more, every loop statement is followed by the binding, the generators emit the
     register map the wrappers static_assert, and the binding header is what its generator writes."""
     files = ["gemm256x.hip", "gemm256p.hip", "gemm256.hip", "conv3d_256.hip", "attention_asm72.hip", "attention_asm72w.hip",
-             "attention_asm72p8.hip", "attention_asm128.hip", "attention_asm128p8.hip"]
-    for name in files + ["gemm_epilogue.h", "gemm_epilogue16.h"]:
+             "attention_asm72p8.hip", "attention_asm128.hip", "attention_asm128p8.hip", "attention_asm128q8.hip"]
+    for name in files + ["gemm_epilogue.h", "gemm_epilogue16.h", "attention_asm_wrap.h"]:
         src = open(os.path.join(CSRC, name)).read()
         code = "\n".join(ln.split("//")[0] for ln in src.split("\n"))
         assert not re.search(r"v_accvgpr_\w+ [^\n\"]*\ba\d+\b", code), f"{name}: an asm statement names an AGPR"
@@ -259,8 +261,8 @@ def test_asm_accumulators_are_values_the_compiler_knows():
         # one binding per kernel body (a constexpr chain of alternative loop statements shares the one behind it)
         assert len(re.findall(r"OSK_AQ_OUT_0_\d+\(|OSKCX_ACC\(NBJ", src)) >= 1, name
         assert "static_assert(OSK" in src, f"{name}: the generated register map is not asserted"
-        if name.startswith("attention_asm"):
-            assert src.count("OSK_AQ_IN_") >= 2, f"{name}: the Q fragments are not bound as loop inputs"
+        if name.startswith("attention_asm"):   # (the fp8 QK^T wrapper binds its 8 Q quads with ONE macro)
+            assert src.count("OSK_AQ_IN_") >= (1 if name == "attention_asm128q8.hip" else 2), f"{name}: the Q fragments are not bound as loop inputs"
     regs = open(os.path.join(CSRC, "attention_asm_regs.inc")).read() + open(os.path.join(CSRC, "gemm256x_regs.inc")).read()
     assert "accvgpr" not in regs and "OSKX_ACC_QUADS 64" in regs and "OSK72W_AQ0 160" in regs
     import subprocess as sp
@@ -273,12 +275,8 @@ def test_asm_accumulators_are_values_the_compiler_knows():
         assert open(os.path.join(d, "acc_quads.h")).read() == open(os.path.join(CSRC, "acc_quads.h")).read(), "acc_quads.h is stale: re-run tools/gen_acc_quads.py"
 
 
-def test_no_compiler_instruction_writes_an_agpr_in_the_gemm_kernels(tmp_path):
-    """ADVICE r5 (low): the accumulators become compiler-visible through an empty asm statement BEHIND the K-loop statement, which only
-    clobbers a0..a255 -- nothing in the constraints forbids the compiler to park a value of its own in an AGPR between the two
-    statements.  The by-construction argument is that it has no reason to (its values live in VGPRs, spills go to scratch); this test
-    pins it on the compiler's actual output: in the device assembly of gemm256x.hip (the hottest wrapper, 256 accumulators + ~250
-    VGPRs: the highest register pressure of the library) no instruction OUTSIDE the inline-asm blocks has an AGPR destination."""
+def _scan_between_loop_and_binding(name, tmp_path, min_loops):
+    """Compile csrc/<name> to device assembly; return what the compiler put between every K-loop statement and the statement behind it."""
     import shutil
     import subprocess as sp
 
@@ -287,8 +285,8 @@ def test_no_compiler_instruction_writes_an_agpr_in_the_gemm_kernels(tmp_path):
         pytest.skip("hipcc not found")
     from open_sora_amd.build import flags_for
 
-    src = os.path.join(CSRC, "gemm256x.hip")
-    out = str(tmp_path / "gemm256x.s")
+    src = os.path.join(CSRC, name)
+    out = str(tmp_path / (name + ".s"))
     flags = [f for f in flags_for(src) if f != "-fPIC"]
     r = sp.run([hipcc, *flags, "--cuda-device-only", "-S", src, "-o", out], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -315,6 +313,28 @@ def test_no_compiler_instruction_writes_an_agpr_in_the_gemm_kernels(tmp_path):
                 assert lines[k + 1].strip().startswith(";;#ASMEND"), "the statement behind a K loop is not the empty accumulator binding"
             i = j
         i += 1
-    assert n_loops >= 4, "the assembly does not look like the GEMM wrappers'"
-    bad = [t for t in between if re.search(r"\ba\d+\b|\ba\[\d", t) or "accvgpr" in t]
+    assert n_loops >= min_loops, f"the assembly of {name} does not look like the wrappers': {n_loops} loop statements"
+    return between
+
+
+def _touches_agpr(between):
+    return [t for t in between if re.search(r"\ba\d+\b|\ba\[\d", t) or "accvgpr" in t]
+
+
+def test_no_compiler_instruction_writes_an_agpr_in_the_gemm_kernels(tmp_path):
+    """ADVICE r5 (low): the accumulators become compiler-visible through an empty asm statement BEHIND the K-loop statement, which only
+    clobbers a0..a255 -- nothing in the constraints forbids the compiler to park a value of its own in an AGPR between the two
+    statements.  The by-construction argument is that it has no reason to (its values live in VGPRs, spills go to scratch); this test
+    pins it on the compiler's actual output: in the device assembly of gemm256x.hip (the hottest wrapper, 256 accumulators + ~250
+    VGPRs: the highest register pressure of the library) no instruction OUTSIDE the inline-asm blocks has an AGPR destination."""
+    bad = _touches_agpr(_scan_between_loop_and_binding("gemm256x.hip", tmp_path, 4))
     assert not bad, f"the compiler touches AGPRs between a K loop and its accumulator binding: {bad[:5]}"
+
+
+@pytest.mark.parametrize("name,min_loops", [("attention_asm72.hip", 4), ("attention_asm72w.hip", 2), ("attention_asm72p8.hip", 1),
+                                            ("attention_asm128.hip", 2), ("attention_asm128p8.hip", 1), ("attention_asm128q8.hip", 1)])
+def test_no_compiler_instruction_writes_an_agpr_in_the_attention_wrappers(tmp_path, name, min_loops):
+    """The attention wrappers rely on the same construction (loop statement, then the empty OSK_AQ_OUT binding; the epilogues of
+    csrc/attention_asm_wrap.h read the quads as operands): the same scan over every instantiation of each of the six."""
+    bad = _touches_agpr(_scan_between_loop_and_binding(name, tmp_path, min_loops))
+    assert not bad, f"{name}: the compiler touches AGPRs between a loop statement and its accumulator binding: {bad[:5]}"
