@@ -373,7 +373,9 @@ __global__ void __launch_bounds__(256) v_transpose_fp8_kernel(const unsigned sho
     dst[0] = u.x; dst[1] = u.y; dst[2] = u.z; dst[3] = u.w;
   }
   __syncthreads();
-  const float inv = 1.0f / scales[b * H + h];
+  // V / scale with an IEEE f32 division, as include/osk.h states and osk_k_pack_fp8 does: a product with the rounded reciprocal
+  // moves a quotient that is an exact e4m3 tie (84.0 between 80 and 88) off the tie and rounds it away from the even neighbour
+  const float scale = scales[b * H + h];
   unsigned char* obase = vt8 + ((int64_t)(b * H + h) * RP) * Lp + key0;
   // thread = (row, 16-byte chunk of the 64-byte row)
   for (int i = threadIdx.x; i < RP * 4; i += 256) {
@@ -388,7 +390,7 @@ __global__ void __launch_bounds__(256) v_transpose_fp8_kernel(const unsigned sho
         float f[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-          f[e] = fminf(fmaxf(bf16_bits_to_f32(tile[k0 + e][d]) * inv, -448.0f), 448.0f);
+          f[e] = fminf(fmaxf(bf16_bits_to_f32(tile[k0 + e][d]) / scale, -448.0f), 448.0f);
         int r = 0;
         r = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], r, false);
         r = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], r, true);
