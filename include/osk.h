@@ -672,6 +672,29 @@ int osk_gemm_quickgelu_bf16(const void* A, int64_t a_batch_stride, int64_t a_row
                             int64_t w_row_stride, const float* bias, void* C, int64_t c_batch_stride, int64_t c_row_stride,
                             int c_rows_per_batch, int M, int N, int K, void* stream);
 
+/* ---- LoRA adapters merged into a Linear weight, on the device, at plan-build time.
+ * replaces the peft wrapping of the MMDiT in prepare_api (opensora/utils/sampling.py:542-545: `pretrained_lora_path` ->
+ * PeftModel.from_pretrained(model, path, is_trainable=False)), for the adapters the trainer writes (scripts/diffusion/train.py:208-216,
+ * opensora/utils/ckpt.py:421-422) on the Linear layers of the double / single blocks (opensora/models/mmdit/model.py:198):
+ *   out[n, k] = bf16_rne( f32(w[n, k]) + sum_i scale_i * sum_j B_i[n, j] * A_i[j, k] ),      n < N, k < K
+ * w, out bf16 [N, K] with rows w_row_stride / out_row_stride elements apart (>= K, % 8 == 0, base pointers 16-byte aligned): a row
+ * slice of a concatenated weight (q_proj | k_proj | v_proj) is merged in place through its stride.  out may be w itself (same pointer
+ * and stride); any other overlap of the two is undefined.  Nothing outside the [N, K] window is read or written.
+ * Adapter i: A_i bf16 [r, K] (lora_A.weight; rows a_row_stride apart, >= K, % 8 == 0, 16-byte aligned), B_i bf16 [N, r]
+ * (lora_B.weight; rows b_row_stride apart, >= r, any alignment), 1 <= r <= 256 arbitrary (padded with zeros inside the kernel),
+ * scale finite (lora_alpha / r times the adapter's weight; may be negative or zero).  `adapters` is a HOST array, read before the
+ * call returns.  0 <= n_adapters <= 8; with 0 the call is a strided copy, bit for bit.
+ * The bf16 x bf16 products are exact in f32 and every sum is kept in f32 (MFMA accumulation over the rank per adapter, one fma per
+ * adapter by its scale, W added last): ONE rounding to bf16, not one per adapter.  A delta below half a bf16 ulp of w[n, k] is lost.
+ * N >= 1 arbitrary, K % 8 == 0.  No allocation, no synchronisation: may be captured in a hipGraph. */
+typedef struct OskLoraAdapter {
+  const void* a; int64_t a_row_stride;
+  const void* b; int64_t b_row_stride;
+  int r; float scale;
+} OskLoraAdapter;
+int osk_lora_merge_bf16(const void* w, int64_t w_row_stride, void* out, int64_t out_row_stride, int N, int K,
+                        const OskLoraAdapter* adapters, int n_adapters, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -96,6 +96,7 @@ SIGNATURES = {
     "osk_layernorm_affine_bf16": [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _f32, _vp],
     "osk_attention_causal_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _f32, _vp],
     "osk_gemm_quickgelu_bf16": [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp],
+    "osk_lora_merge_bf16": [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _i32, _vp],     # OskLoraAdapter array (host) by pointer
 }
 
 
@@ -1105,4 +1106,28 @@ def gemm_quickgelu(a: torch.Tensor, w: torch.Tensor, bias, out: torch.Tensor) ->
     with _gemm_prof(2.0 * B * L * N * K):
         _check(lib.osk_gemm_quickgelu_bf16(a.data_ptr(), a.stride(0), a.stride(1), L, w.data_ptr(), w.stride(0), _p(bias), out.data_ptr(),
                                            out.stride(0), out.stride(1), L, B * L, N, K, _stream()), "osk_gemm_quickgelu_bf16")
+    return out
+
+
+class OskLoraAdapter(C.Structure):
+    """include/osk.h::OskLoraAdapter"""
+    _fields_ = [("a", _vp), ("a_row_stride", _i64), ("b", _vp), ("b_row_stride", _i64), ("r", _i32), ("scale", _f32)]
+
+
+def lora_merge(w: torch.Tensor, out: torch.Tensor, adapters) -> torch.Tensor:
+    """out = bf16(w + sum_i scale_i B_i A_i) with f32 sums and one rounding (osk_lora_merge_bf16).  w, out bf16 [N, K] views with
+    contiguous last dim (row slices of a concatenated weight included; out may be w); adapters: up to 8 tuples (A bf16 [r, K],
+    B bf16 [N, r], scale), 1 <= r <= 256.  No adapters: a strided copy."""
+    N, K = w.shape
+    assert tuple(out.shape) == (N, K) and w.dtype == out.dtype == torch.bfloat16, (w.shape, out.shape, w.dtype, out.dtype)
+    assert w.stride(1) == 1 and out.stride(1) == 1, (w.stride(), out.stride())
+    adapters = list(adapters)
+    arr = (OskLoraAdapter * max(len(adapters), 1))()
+    for t, (a, b, scale) in zip(arr, adapters):
+        r = a.shape[0]
+        assert tuple(a.shape) == (r, K) and tuple(b.shape) == (N, r), (a.shape, b.shape, (N, K))
+        assert a.dtype == b.dtype == torch.bfloat16 and a.stride(1) == 1 and b.stride(1) == 1 and a.device == b.device == w.device
+        t.a, t.a_row_stride, t.b, t.b_row_stride, t.r, t.scale = a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), r, float(scale)
+    _check(lib.osk_lora_merge_bf16(w.data_ptr(), w.stride(0), out.data_ptr(), out.stride(0), N, K, C.addressof(arr), len(adapters),
+                                   _stream()), "osk_lora_merge_bf16")
     return out

@@ -274,8 +274,50 @@ def _b32(t: Tensor | None) -> Tensor | None:
     return None if t is None else t.detach().float().contiguous()
 
 
+# LoRA adapters active on a Linear (open_sora_amd/lora.py fills it): nn.Linear -> [(A bf16 [r, in], B bf16 [out, r], scale)].
+# A weak side table, as _WATCHERS above: it never travels with copy.deepcopy / pickle / torch.save (a copy is the base model), and
+# the parameters and state_dict() of the model are never touched -- the PLAN gets merged copies of the adapted weights.
+_LORA: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
+
+
+def _lora_key(module) -> tuple:
+    """adapter epoch of a model / block (bumped by load_lora / set_lora_weights / unload_lora): part of _param_key"""
+    return (getattr(module, "_osk_lora_epoch", 0),)
+
+
+def _lora_merge(w: Tensor, out: Tensor, ads) -> Tensor:
+    """out = bf16(w + sum_i scale_i B_i A_i), f32 sums, ONE rounding: osk_lora_merge_bf16.  w / out bf16 [N, K] views (row slices of a
+    concatenated weight included).  A kernel table without `lora_merge` (the CPU emulation of tests/) gets the same arithmetic from
+    torch in f32."""
+    ads = [(a.to(w.device), b.to(w.device), float(s)) for a, b, s in ads]
+    if hasattr(_OPS, "lora_merge"):
+        return _OPS.lora_merge(w, out, ads)
+    acc = torch.zeros(w.shape, dtype=torch.float32, device=w.device)
+    for a, b, s in ads:
+        acc += s * (b.float() @ a.float())
+    out.copy_((w.float() + acc).to(BF16) if ads else w)
+    return out
+
+
+def _lin_w(lin) -> Tensor:
+    """the bf16 weight the plan uses for a Linear: today's zero-copy view, or -- adapters active on it -- one merged copy"""
+    w = _w(lin.weight)
+    ads = _LORA.get(lin)
+    return _lora_merge(w, torch.empty_like(w), ads) if ads else w
+
+
 def _cat_linear(*lins):
-    w = torch.cat([_w(l.weight) for l in lins], 0).contiguous() if len(lins) > 1 else _w(lins[0].weight)
+    if len(lins) == 1:
+        w = _lin_w(lins[0])
+    elif not any(_LORA.get(l) for l in lins):
+        w = torch.cat([_w(l.weight) for l in lins], 0).contiguous()
+    else:   # q_proj | k_proj | v_proj (v_mlp): every piece merged (or, without adapters, copied) straight into its row slice
+        ws = [_w(l.weight) for l in lins]
+        w = torch.empty(sum(t.shape[0] for t in ws), ws[0].shape[1], dtype=BF16, device=ws[0].device)
+        row = 0
+        for l, t in zip(lins, ws):
+            _lora_merge(t, w[row: row + t.shape[0]], _LORA.get(l) or ())
+            row += t.shape[0]
     if lins[0].bias is None:
         return w, None
     b = torch.cat([l.bias.detach().float() for l in lins], 0).contiguous()
@@ -406,7 +448,7 @@ def _attn_weights(sa, wrap=lambda w: w) -> _AttnW:
         w, b = _cat_linear(sa.qkv)
     else:
         w, b = _cat_linear(sa.q_proj, sa.k_proj, sa.v_proj)
-    return _AttnW(wrap(w), b, _w(sa.norm.query_norm.scale), _w(sa.norm.key_norm.scale), wrap(_w(sa.proj.weight)),
+    return _AttnW(wrap(w), b, _w(sa.norm.query_norm.scale), _w(sa.norm.key_norm.scale), wrap(_lin_w(sa.proj)),
                   _b32(sa.proj.bias))
 
 
@@ -416,7 +458,7 @@ def _wrap_for(block):
 
 
 def _mod_layer(mod) -> tuple:
-    return (_w(mod.lin.weight), None if mod.lin.bias is None else _w(mod.lin.bias))
+    return (_lin_w(mod.lin), None if mod.lin.bias is None else _w(mod.lin.bias))
 
 
 def _tensor_key(p: Tensor) -> tuple:
@@ -430,8 +472,9 @@ def _param_key(module):
     """_tensor_key of every parameter of the module: a cached plan built from other values is stale.  Detected: a storage
     swap (load_state_dict, .to(), a new Parameter) and autograd-visible in-place writes (`p.mul_()`, `p.copy_()` under
     no_grad, an optimizer step).  NOT detected: writes through `p.data` (`.data` is a detached alias with its own version
-    counter) and writes to inference tensors -- after those, call `model.invalidate_plan()`."""
-    return tuple(_tensor_key(p) for p in module.parameters())
+    counter) and writes to inference tensors -- after those, call `model.invalidate_plan()`.  The key ends with the module's LoRA
+    epoch (_lora_key): a plan built under another set of adapters or adapter weights is stale too."""
+    return tuple(_tensor_key(p) for p in module.parameters()) + _lora_key(module)
 
 
 def plan_double(block) -> _DoublePlan:
@@ -443,8 +486,8 @@ def plan_double(block) -> _DoublePlan:
         p = _DoublePlan(
             img=_attn_weights(block.img_attn, wr),
             txt=_attn_weights(block.txt_attn, wr),
-            img_mlp=(wr(_w(block.img_mlp[0].weight)), _b32(block.img_mlp[0].bias), wr(_w(block.img_mlp[2].weight)), _b32(block.img_mlp[2].bias)),
-            txt_mlp=(wr(_w(block.txt_mlp[0].weight)), _b32(block.txt_mlp[0].bias), wr(_w(block.txt_mlp[2].weight)), _b32(block.txt_mlp[2].bias)),
+            img_mlp=(wr(_lin_w(block.img_mlp[0])), _b32(block.img_mlp[0].bias), wr(_lin_w(block.img_mlp[2])), _b32(block.img_mlp[2].bias)),
+            txt_mlp=(wr(_lin_w(block.txt_mlp[0])), _b32(block.txt_mlp[0].bias), wr(_lin_w(block.txt_mlp[2])), _b32(block.txt_mlp[2].bias)),
             mod_layers=[_mod_layer(block.img_mod), _mod_layer(block.txt_mod)],
             pv8=bool(getattr(block, "_osk_fp8", False)), qk8=bool(getattr(block, "_osk_qk8", False)),
         )
@@ -466,7 +509,7 @@ def plan_single(block) -> _SinglePlan:
         else:
             w1, b1 = _cat_linear(block.q_proj, block.k_proj, block.v_mlp)
         wr = _wrap_for(block)
-        p = _SinglePlan(wr(w1), b1, wr(_w(block.linear2.weight)), _b32(block.linear2.bias),
+        p = _SinglePlan(wr(w1), b1, wr(_lin_w(block.linear2)), _b32(block.linear2.bias),
                         _w(block.norm.query_norm.scale), _w(block.norm.key_norm.scale),
                         mod_layers=[_mod_layer(block.modulation)], pv8=bool(getattr(block, "_osk_fp8", False)),
                         qk8=bool(getattr(block, "_osk_qk8", False)))
@@ -1000,7 +1043,8 @@ class MMDiTModel(_OskState, nn.Module):
         """_param_key of the whole model: the plan is rebuilt when a weight's storage was swapped or the weight was written
         in place through the parameter itself (`p.copy_()` / `p.add_()` under no_grad, an optimizer step) since it was
         built.  Writes through `p.data` (a LoRA merge done as `p.data += ...`) are invisible to the version counter:
-        call `invalidate_plan()` after them (see _param_key)."""
+        call `invalidate_plan()` after them (see _param_key) -- or load the adapter with open_sora_amd.lora.load_lora, which
+        leaves the parameters alone and whose epoch is part of this key."""
         return _param_key(self)
 
     def _build_plan(self, device):
