@@ -315,6 +315,20 @@ int osk_attention_fwd_auto_bf16(const void* q, int64_t q_batch_stride, int64_t q
  * osk_v_transpose_fp8 / osk_attention_fwd_pv8_bf16 take.  (Under sequence parallelism max-reduce them over the ranks.) */
 int osk_v_scale_fp8(const void* v, int64_t v_batch_stride, int64_t v_row_stride, float* scales, int B, int L, int H,
                     int hd, void* stream);
+/* osk_kv_scale_fp8: the scales of K and of V from ONE launch, into one contiguous buffer scales f32 [2, B, H]:
+ *   scales[0][b][h] = what osk_v_scale_fp8 returns when it is pointed at K, scales[1][b][h] = what it returns for V, bit for bit
+ *   (absmax / 448, the division in IEEE f32, 1.0 for an all-zero head).  k, v: bf16 [B, L, H*hd] views with their own batch and
+ *   row strides (elements, multiples of 8; 16-byte aligned pointers; last dim contiguous); hd a multiple of 8 (<= 8192), H <= 256.
+ *   For the qk8 attention under sequence parallelism: both vectors must be the same on every rank, and one buffer means ONE
+ *   max-reducing collective per block (open_sora_amd/seqpar.py), after which osk_k_pack_fp8 and osk_v_transpose_fp8 take the two
+ *   halves.  One workgroup per (tensor, batch, head) walks all L rows of its head with the loads of a round in flight before the
+ *   first use: a workgroup's maximum is final when it ends, which is what lets one launch do without a zeroed accumulator.  The
+ *   price: 2 * B * H workgroups is all the parallelism there is -- HBM-bound from about 150 of them, below that bound by the
+ *   CUs in use (48 workgroups of a rank of the 11B model: 2.0 TB/s, 0.17 ms for 355 MB; profiles/attn_qk8_sp.md).  No
+ *   allocation, no memset, no atomics on global memory, no synchronisation: capturable in a hipGraph. */
+int osk_kv_scale_fp8(const void* k, int64_t k_batch_stride, int64_t k_row_stride,
+                     const void* v, int64_t v_batch_stride, int64_t v_row_stride, float* scales,
+                     int B, int L, int H, int hd, void* stream);
 int osk_v_transpose_fp8(const void* v, int64_t v_batch_stride, int64_t v_row_stride, const float* scales, void* vt8,
                         int B, int L, int H, int hd, void* stream);
 int osk_attention_fwd_pv8_bf16(const void* q, int64_t q_batch_stride, int64_t q_row_stride,
@@ -336,7 +350,10 @@ int osk_attention_fwd_pv8_bf16(const void* q, int64_t q_batch_stride, int64_t q_
  *   pieces of these rows (the bank swizzle is in the copy's addresses, not in the tensor).  Rows L .. Lp-1 repeat row L-1, so
  *   the scores of a ragged last tile stay finite; key validity comes from the baked row of vt8.  scales f32 [B, H]: what
  *   osk_v_scale_fp8 computes when it is pointed at K (absmax over the head / 448, 1.0 for an all-zero head).  With several key
- *   segments: one call per segment with the SAME scales (their maximum over the segments).
+ *   segments: one call per segment with the SAME scales (their maximum over the segments).  Sequence parallelism uses exactly
+ *   that: every rank packs its own segment with the max-reduced scales of osk_kv_scale_fp8, the packed segments are all-gathered
+ *   (K travels at 1 byte per element), and the gathered bytes are the ones one device packs from the whole K (padding rows of a
+ *   ragged segment aside).
  * osk_attention_fwd_qk8_bf16: the arguments of osk_attention_fwd_pv8_bf16 except that k8 (from the call above, per key segment)
  *   replaces k with k8_seg_stride and k8_batch_stride in BYTES (multiples of 16; batch stride of one segment's tensor =
  *   H * Lp * 128), k8_row_stride = 128 (bytes; anything else: OSK_EUNSUPPORTED), and k_scale = the scales the pack used, indexed

@@ -56,6 +56,7 @@ SIGNATURES = {
     "osk_rownorm2_max_bf16": [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp],
     "osk_attention_workspace_bytes": [],
     "osk_v_scale_fp8": [_vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _vp],
+    "osk_kv_scale_fp8": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _vp],
     "osk_v_transpose_fp8": [_vp, _i64, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
     "osk_attention_fwd_pv8_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _vp,
                                    _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _vp, _i64, _vp],
@@ -628,6 +629,22 @@ def v_scale_fp8(v: torch.Tensor, H: int, hd: int) -> torch.Tensor:
     _check(lib.osk_v_scale_fp8(v.data_ptr(), v.stride(0), v.stride(1), scales.data_ptr(), B, L, H, hd, _stream()),
            "osk_v_scale_fp8")
     return scales
+
+
+def kv_scale_fp8(k: torch.Tensor, v: torch.Tensor, H: int, hd: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """k, v bf16 [B, L, H*hd] views (their own strides) -> f32 [2, B, H]: [0] = v_scale_fp8(k), [1] = v_scale_fp8(v), bit for bit,
+    from one launch into one contiguous buffer (osk_kv_scale_fp8) -- what sequence parallelism max-reduces with ONE collective."""
+    assert k.dim() == 3 and k.shape == v.shape, (k.shape, v.shape)
+    B, L, C_ = k.shape
+    assert k.dtype == torch.bfloat16 and v.dtype == torch.bfloat16 and C_ == H * hd and hd % 8 == 0, (k.dtype, v.dtype, k.shape, H, hd)
+    for t in (k, v):
+        assert t.stride(2) == 1 and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0 and t.data_ptr() % 16 == 0, (t.stride(), t.data_ptr() % 16)
+    if out is None:
+        out = torch.empty(2, B, H, dtype=torch.float32, device=k.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (2, B, H) and out.device == k.device, (out.dtype, out.shape)
+    _check(lib.osk_kv_scale_fp8(k.data_ptr(), k.stride(0), k.stride(1), v.data_ptr(), v.stride(0), v.stride(1), out.data_ptr(),
+                                B, L, H, hd, _stream()), "osk_kv_scale_fp8")
+    return out
 
 
 def v_transpose_fp8(v: torch.Tensor, scales: torch.Tensor, vt8: torch.Tensor, H: int, hd: int) -> torch.Tensor:

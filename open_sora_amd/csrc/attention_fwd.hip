@@ -484,6 +484,73 @@ extern "C" int osk_v_scale_fp8(const void* v, int64_t bs, int64_t rs, float* sca
   return (int)hipGetLastError();
 }
 
+namespace {
+
+// absmax of K AND of V per (batch, head) -> both e4m3 scale vectors from ONE launch: grid (H, B, 2), z = 0 K, z = 1 V.  A block
+// owns one head of one batch item of one tensor over ALL L rows, so its maximum is final when it ends: no accumulator to zero,
+// no cross-block atomic, no finalize pass (the three launches of osk_v_scale_fp8).  1024 threads = rpp rows x (hd / 8) 16-byte
+// chunks of the head's columns per pass; the loads of U passes (U x 16 KB per workgroup at head_dim 128) are all issued before
+// the first is folded.  Row indices past the end are clamped to L - 1: a repeated row does not move a maximum, and the tail
+// needs no predicate.  Only 2 B H workgroups exist (48 for a rank of the 11B model at B = 1): a CU streamed 42 GB/s here with
+// 8 and with 16 passes in flight alike, so below about 150 workgroups the CUs in use bound the launch, not HBM
+// (profiles/attn_qk8_sp.md); splitting a head's rows over workgroups would need a zeroed accumulator, i.e. a second launch.
+// The same integer maximum of |bf16| bit patterns and the same f32 division as v_absmax_kernel / v_scale_finalize_kernel.
+constexpr int KV_SCALE_THREADS = 1024, KV_SCALE_U = 8;
+
+__device__ __forceinline__ unsigned absmax_bits8(const uint4& u, unsigned m) {
+  const unsigned w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const unsigned a = w[j] & 0x7FFF7FFFu;
+    m = max(m, max(a & 0xFFFFu, a >> 16));
+  }
+  return m;
+}
+
+__global__ void __launch_bounds__(KV_SCALE_THREADS) kv_scale_fp8_kernel(const unsigned short* __restrict__ k, int64_t kbs, int64_t krs,
+                                                                        const unsigned short* __restrict__ v, int64_t vbs, int64_t vrs,
+                                                                        float* __restrict__ scales, int L, int H, int cpr, int rpp) {
+  constexpr int U = KV_SCALE_U;
+  __shared__ unsigned smax;
+  const int h = blockIdx.x, b = blockIdx.y, z = blockIdx.z, B = gridDim.y;
+  if (threadIdx.x == 0) smax = 0;
+  __syncthreads();
+  const int rl = threadIdx.x / cpr, c = threadIdx.x - rl * cpr;
+  if (rl < rpp) {            // (hd / 8 does not divide 1024: the last few threads have no row)
+    const unsigned short* p = (z ? v + b * vbs : k + b * kbs) + (int64_t)h * cpr * 8 + c * 8;
+    const int64_t rs = z ? vrs : krs;
+    unsigned m = 0;
+    const int64_t last = L - 1;
+    for (int64_t r = rl; r < L; r += (int64_t)U * rpp) {
+      uint4 u[U];
+#pragma unroll
+      for (int i = 0; i < U; ++i) u[i] = *reinterpret_cast<const uint4*>(p + min(r + (int64_t)i * rpp, last) * rs);
+#pragma unroll
+      for (int i = 0; i < U; ++i) m = absmax_bits8(u[i], m);
+    }
+    if (m) atomicMax(&smax, m);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float amax = __uint_as_float(smax << 16);
+    scales[((int64_t)z * B + b) * H + h] = amax > 0.f ? amax / 448.0f : 1.0f;
+  }
+}
+
+}  // namespace
+
+extern "C" int osk_kv_scale_fp8(const void* k, int64_t kbs, int64_t krs, const void* v, int64_t vbs, int64_t vrs, float* scales,
+                                int B, int L, int H, int hd, void* stream) {
+  if (!k || !v || !scales || B <= 0 || B > 65535 || L <= 0 || H <= 0 || H > 256 || hd <= 0 || (hd & 7) || (kbs & 7) || (krs & 7) ||
+      (vbs & 7) || (vrs & 7) || ((uintptr_t)k & 15) || ((uintptr_t)v & 15) || ((uintptr_t)scales & 3))
+    return OSK_EINVAL;
+  const int cpr = hd >> 3;
+  if (cpr > KV_SCALE_THREADS) return OSK_EUNSUPPORTED;   // (a head row wider than one pass of the block: hd > 8192)
+  hipLaunchKernelGGL(kv_scale_fp8_kernel, dim3(H, B, 2), dim3(KV_SCALE_THREADS), 0, (hipStream_t)stream, (const unsigned short*)k,
+                     kbs, krs, (const unsigned short*)v, vbs, vrs, scales, L, H, cpr, KV_SCALE_THREADS / cpr);
+  return (int)hipGetLastError();
+}
+
 extern "C" int osk_v_transpose_fp8(const void* v, int64_t bs, int64_t rs, const float* scales, void* vt8, int B, int L,
                                    int H, int hd, void* stream) {
   if (!v || !vt8 || !scales || B <= 0 || L <= 0 || H <= 0 || (bs & 7) || (rs & 7) || ((uintptr_t)vt8 & 15)) return OSK_EINVAL;

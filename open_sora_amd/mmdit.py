@@ -412,7 +412,7 @@ class _DoublePlan:
     txt_mlp: tuple = ()
     mod_layers: list = field(default_factory=list)  # [(w bf16, b bf16)] img then txt
     pv8: bool = False   # fp8 mode: attention with the P.V product on the fp8 MFMA
-    qk8: bool = False   # ... and, at head_dim 128 outside sequence parallelism, QK^T too (enable_fp8(qk8=True))
+    qk8: bool = False   # ... and, at head_dim 128, QK^T too (enable_fp8(qk8=True)); sharded or not (seqpar.gather_kv_start)
     key: tuple = ()     # _param_key of the block the plan was built from
     score_bound: float = 0.0   # bound on |q . k| as the attention kernel sees it (log2 units): _score_bound()
 
@@ -427,7 +427,7 @@ class _SinglePlan:
     k_scale: Tensor
     mod_layers: list = field(default_factory=list)
     pv8: bool = False
-    qk8: bool = False
+    qk8: bool = False   # (see _DoublePlan)
     key: tuple = ()
     score_bound: float = 0.0
 
@@ -701,6 +701,14 @@ def _joint_attention(ws: _Workspace, q: Tensor, k: Tensor, v: Tensor, H: int, hd
     _OPS.attention_fwd(q, k, ws.vt, v, H, hd, hd ** -0.5, q_prescaled=True, workspace=wsp, score_bound=score_bound)
 
 
+def _sp_qk8(sp, plan) -> dict:
+    """the qk8 argument of sp.gather_kv_start, for a plan that asks for it and an sp object that knows it (seqpar.SeqPar.kv_qk8;
+    guarded like local_vt: a caller's own sp object without it keeps the pv8 exchange) and a kernel table that has the scale
+    entry the exchange needs (looked up like attention_fwd_auto in _joint_attention: the HIP library always has it -- a missing
+    symbol fails its import -- while a substituted table from before the entry keeps the exchange it was written against)"""
+    return {"qk8": True} if plan.qk8 and getattr(sp, "kv_qk8", False) and hasattr(_OPS, "kv_scale_fp8") else {}
+
+
 def run_double_block(plan: _DoublePlan, ws: _Workspace, mod: Tensor, col_img: int, col_txt: int, rope: _RopeTable,
                      H: int, hd: int, sp=None, x_in=None, x_out=None):
     """DoubleStreamBlockProcessor.__call__ (layers.py:195-253) on the workspace's joint buffers.
@@ -774,7 +782,7 @@ def run_double_block(plan: _DoublePlan, ws: _Workspace, mod: Tensor, col_img: in
             for (aw, x_s, xm_s, y_s, sh1, sc1), act in zip(streams, acts):
                 _linear(act, aw.qkv_w[D:], None if aw.qkv_b is None else aw.qkv_b[D:], y_s[:, :, D:])
         _OPS.qknorm_rope(None, k, *scales, Lt, rope.cos, rope.sin, csb, H, hd, rope.mode)
-        pending = sp.gather_kv_start(ws, k, v, H, hd, plan.pv8, vt_ready=vt_ready)
+        pending = sp.gather_kv_start(ws, k, v, H, hd, plan.pv8, vt_ready=vt_ready, **_sp_qk8(sp, plan))
         for (aw, x_s, xm_s, y_s, sh1, sc1), act in zip(streams, acts):
             _linear(act, aw.qkv_w[:D], None if aw.qkv_b is None else aw.qkv_b[:D], y_s[:, :, :D])
         _OPS.qknorm_rope(q, None, *scales, Lt, rope.cos, rope.sin, csb, H, hd, rope.mode, q_mult=q_mult(hd))
@@ -844,7 +852,7 @@ def run_single_block(plan: _SinglePlan, ws: _Workspace, mod: Tensor, col: int, r
         if not vt_ready:
             _linear(act, plan.w1[D: 3 * D], None if b1 is None else b1[D: 3 * D], y[:, :, D: 3 * D])
         _OPS.qknorm_rope(None, k, *scales, 0, rope.cos, rope.sin, csb, H, hd, rope.mode)
-        pending = sp.gather_kv_start(ws, k, v, H, hd, plan.pv8, vt_ready=vt_ready)
+        pending = sp.gather_kv_start(ws, k, v, H, hd, plan.pv8, vt_ready=vt_ready, **_sp_qk8(sp, plan))
         mlp_up = lambda: _linear(act, plan.w1[3 * D:], None if b1 is None else b1[3 * D:], y[:, :, 3 * D:], gelu_from=0)
         head_mode = sp.head_parallel(H)
         if not head_mode:    # K / V^T all-gather: the MLP-up and Q projections both overlap it
@@ -999,9 +1007,12 @@ class MMDiTModel(_OskState, nn.Module):
         activation scales and per-output-row weight scales; attention, norms, modulation, embedders and the final
         layer stay bf16.  The reference computes in bf16: results differ by the e4m3 quantisation error.
         qk8 (opt-in on top, head_dim 128): the attention's QK^T runs on the fp8 MFMA as well -- K packed to e4m3 per (batch, head),
-        Q per (row, head) inside the kernel (osk_attention_fwd_qk8_bf16).  Any other head dim, and every call under sequence
-        parallelism, keeps the pv8 attention.  Recommended for head_dim 128: the attention launch takes 0.77 - 0.79 of the pv8 time
-        with the K pack counted (A/B spread under 2 %) at the same model-level error; DESIGN.md section 4, profiles/attn_qk8.md."""
+        Q per (row, head) inside the kernel (osk_attention_fwd_qk8_bf16).  Any other head dim keeps the pv8 attention.  Under
+        sequence parallelism (seqpar.enable) every rank runs it too: in all-gather mode K travels packed as e4m3 with scales that
+        one max-reduction over a [2, B, H] buffer (K's and V's, osk_kv_scale_fp8) makes equal on every rank; in head-exchange mode
+        K is packed after the all-to-all, with no collective.  Recommended for head_dim 128: the attention launch takes
+        0.77 - 0.79 of the pv8 time with the K pack counted (A/B spread under 2 %) at the same model-level error; DESIGN.md
+        section 4, profiles/attn_qk8.md, profiles/attn_qk8_sp.md (a rank's launch at the sharded shape)."""
         for b in list(self.double_blocks) + list(self.single_blocks):
             object.__setattr__(b, "_osk_fp8", bool(on))
             object.__setattr__(b, "_osk_qk8", bool(on and qk8))

@@ -167,6 +167,7 @@ class SeqPar:
 
     # ------------------------------------------------------------------ K/V exchange
     MAX_GEOMETRIES = 4   # exchange-buffer sets kept (least recently used first out)
+    kv_qk8 = True        # gather_kv_start takes qk8 (mmdit._sp_qk8 asks before it passes the argument)
 
     def _cached(self, key, make):
         """exchange buffers of one (kind, geometry, device, stream), least-recently-used eviction: an i2v run that alternates between
@@ -196,6 +197,18 @@ class SeqPar:
 
         return self._cached(("pv8", B, Lloc, H, hd, str(device), mmdit._stream_key(device)), make)
 
+    def _buffers_qk8(self, B: int, Lloc: int, H: int, hd: int, device):
+        """qk8 (head_dim 128): K travels packed as e4m3 too -- [P, B, H, Lp, 128] bytes, no bf16 K buffer -- plus the [2, B, H]
+        scale buffer (K's scales, then V's) that the one reducing collective of the block works on"""
+        def make():
+            ops = mmdit.ops()
+            Lp = (Lloc + 63) // 64 * 64
+            return (torch.empty(self.P, *ops.k8_shape(B, H, Lloc, hd), dtype=torch.uint8, device=device),
+                    torch.zeros(self.P, B, H, ops.vt8_rows(hd), Lp, dtype=torch.uint8, device=device),
+                    torch.empty(2, B, H, dtype=torch.float32, device=device))
+
+        return self._cached(("qk8", B, Lloc, H, hd, str(device), mmdit._stream_key(device)), make)
+
     def local_vt(self, B: int, Lloc: int, H: int, hd: int, device):
         """this rank's slot [B, H, hd, round_up(L/P, 64)] of the gathered V^T buffer (all-gather mode, bf16), or None: the projection
         may write V straight into it as V^T (osk_gemm_group_bf16's V^T task, round 6) -- gather_kv_start(..., vt_ready=True) then
@@ -204,15 +217,32 @@ class SeqPar:
             return None
         return self._buffers(B, Lloc, H, hd, device)[1][self.rank]
 
-    def gather_kv_start(self, ws, k: Tensor, v: Tensor, H: int, hd: int, pv8: bool = False, vt_ready: bool = False):
+    def gather_kv_start(self, ws, k: Tensor, v: Tensor, H: int, hd: int, pv8: bool = False, vt_ready: bool = False,
+                        qk8: bool = False):
         """k, v: this rank's [B, L/P, D] views (K already normed + rotated with GLOBAL positions).  Starts the
         exchange of K and V and returns the handles; the caller keeps computing.
         pv8 (fp8 mode): V travels as e4m3 V^T (half the bytes); its per-(batch, head) scale must be the same on
-        every rank -- the kernel accumulates P.V across all key segments -- so the local absmax is max-reduced first."""
+        every rank -- the kernel accumulates P.V across all key segments -- so the local absmax is max-reduced first.
+        qk8 (with pv8, head_dim 128 only; anything else behaves as without it): K travels as e4m3 as well, packed by osk_k_pack_fp8
+        with scales that are the same on every rank, so the gathered bytes are the ones a single device would pack (padding rows
+        aside).  K's and V's scales come from one osk_kv_scale_fp8 launch into one [2, B, H] buffer: still ONE reducing collective."""
         pv8 = pv8 and hd in (72, 128)
+        qk8 = qk8 and pv8 and hd == 128
         if self.head_parallel(H):
-            return self._heads_kv_start(k, v, H, hd, pv8)
+            return self._heads_kv_start(k, v, H, hd, pv8, qk8)
         B, Lloc, _ = k.shape
+        if qk8:
+            ops = mmdit.ops()
+            k8_all, vt8_all, s2 = self._buffers_qk8(B, Lloc, H, hd, k.device)
+            ops.kv_scale_fp8(k, v, H, hd, out=s2)
+            # (the co-residency rule of the pv8 branch below: the only REDUCING collective of the block; both packs need its result,
+            #  so the compute stream runs nothing under it)
+            self._timed_wait(self.tp.all_reduce_max(s2), "kvmax")
+            ops.k_pack_fp8(k, s2[0], k8_all[self.rank], H, hd)
+            wk = self.tp.all_gather(k8_all.view(-1), k8_all[self.rank].view(-1))
+            ops.v_transpose_fp8(v, s2[1], vt8_all[self.rank], H, hd)
+            wv = self.tp.all_gather(vt8_all.view(-1), vt8_all[self.rank].view(-1))
+            return "qk8", k8_all, vt8_all, s2, wk, wv
         if pv8:
             sv = mmdit.v_scale_fp8(v, H, hd)
             # (co-residency rule of INTEGRATION.md section 4: the only REDUCING collective of this file; until its wait() below the
@@ -241,6 +271,14 @@ class SeqPar:
             return self._heads_attention(pending, q, out, H, hd, score_bound)
         B, Lloc, D = q.shape
         ops = mmdit.ops()
+        if isinstance(pending[0], str) and pending[0] == "qk8":
+            _, k8_all, vt8_all, s2, wk, wv = pending
+            self._timed_wait(wk, "k")
+            self._timed_wait(wv, "v")
+            ops.attention_fwd_qk8(q, k8_all[0], s2[0], vt8_all, s2[1], out, H, hd, hd ** -0.5, seg_len=Lloc, n_seg=self.P,
+                                  k_seg_stride=k8_all.stride(0), vt_seg_stride=vt8_all.stride(0), q_prescaled=True,
+                                  workspace=ops.attention_workspace(q.device))
+            return
         if isinstance(pending[0], str):   # "pv8"
             _, k_all, vt8_all, sv, wk, wv = pending
             self._timed_wait(wk, "k")
@@ -280,9 +318,15 @@ class SeqPar:
         B, Lloc, D = out.shape
         mmdit.ops().copy_rows(src, out.view(B, Lloc, self.P, D // self.P).permute(2, 0, 1, 3))
 
-    def _heads_kv_start(self, k: Tensor, v: Tensor, H: int, hd: int, pv8: bool = False):
+    def _heads_kv_start(self, k: Tensor, v: Tensor, H: int, hd: int, pv8: bool = False, qk8: bool = False):
+        """K and V travel in bf16 whatever the fp8 mode (packing K before the all-to-all would need per-segment K scales in the
+        kernel); the handle's last element says what _heads_attention does with them: False, True (pv8) or "qk8" """
         B, Lloc, _ = k.shape
         bufs = self._heads_buffers(B, Lloc, H, hd, k.device)
+        if qk8:
+            pv8 = "qk8"
+            if "k8" not in bufs:    # e4m3 K of the received chunks: only a model that asked for qk8 pays for it
+                bufs["k8"] = torch.empty(self.P, *mmdit.ops().k8_shape(B, H // self.P, Lloc, hd), dtype=torch.uint8, device=k.device)
         self._to_head_chunks(bufs["ks"], k)
         wk = self.tp.all_to_all(bufs["kr"].view(-1), bufs["ks"].view(-1))
         self._to_head_chunks(bufs["vs"], v)
@@ -311,7 +355,17 @@ class SeqPar:
         # received chunk s = source rank s's tokens = key segment s; [P, B] is also the query "batch" axis
         ops = mmdit.ops()
         qr, kr, os_ = bufs["qr"].view(P * B, Lloc, Hg * hd), bufs["kr"], bufs["os"].view(P * B, Lloc, Hg * hd)
-        if pv8:   # this rank holds the WHOLE sequence of its heads: the e4m3 scale needs no collective
+        if pv8 == "qk8":   # (the whole sequence of its heads is here: no collective for either scale vector)
+            kr3, vr3 = kr.view(P * B, Lloc, Hg * hd), bufs["vr"].view(P * B, Lloc, Hg * hd)
+            s2 = ops.kv_scale_fp8(kr3, vr3, Hg, hd).view(2, P, B, Hg).amax(1).contiguous()                      # [2, B, Hg]
+            s2p = s2.repeat(1, P, 1)                                                                          # [2, P * B, Hg]
+            k8, vt8 = bufs["k8"], bufs["vt8"]
+            ops.k_pack_fp8(kr3, s2p[0], k8.view(P * B, Hg, k8.shape[-2], 128), Hg, hd)
+            ops.v_transpose_fp8(vr3, s2p[1], vt8.view(P * B, Hg, vt8.shape[-2], vt8.shape[-1]), Hg, hd)
+            ops.attention_fwd_qk8(qr, k8[0], s2[0], vt8, s2[1], os_, Hg, hd, hd ** -0.5, seg_len=Lloc, n_seg=P,
+                                  k_seg_stride=k8.stride(0), vt_seg_stride=vt8.stride(0), q_prescaled=True, kv_batches=B,
+                                  workspace=ops.attention_workspace(q.device))
+        elif pv8:   # this rank holds the WHOLE sequence of its heads: the e4m3 scale needs no collective
             vr = bufs["vr"]
             sv = ops.v_scale_fp8(vr.view(P * B, Lloc, Hg * hd), Hg, hd).view(P, B, Hg).amax(0).contiguous()   # [B, Hg]
             vt8 = bufs["vt8"]
