@@ -3,7 +3,7 @@
 //     C = epi(A[M,K] @ W[N,K]^T + bias)
 //
 // Tile 256 (M) x BN (N, 256 or 128) x 64 (K), 512 threads = 8 waves (two per SIMD).  The K loop is ONE asm
-// statement emitted by tools/gen_gemm_asm.py (gemm256_body_n*.inc): two LDS stages filled by LDS-DMA one K step
+// statement emitted by tools/gen_gemm_asm.py::gen_fp8 (gemm256_fp8_body_n*.inc): two LDS stages filled by LDS-DMA one K step
 // ahead, fragment sets double-buffered in registers, the last k-sub-step of a K step issued AFTER the tile barrier
 // so that the first LDS reads of the next stage and its DMA sit in MFMA shadows, accumulators in AGPRs.
 // Operand convention, LDS image (128-byte rows, source-side XOR swizzle) and the fused epilogue (bias / GELU-tanh /

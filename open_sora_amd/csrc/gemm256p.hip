@@ -40,9 +40,9 @@ struct Geo {
   OSK_DEV void read(const osk_v4f* aq, float* v16) { read_acc<T>(aq, v16); }
 };
 
-// SCHED: K-step schedule of the generated body (tools/gen_gemm_asm.py::gen_pers): 0 = the round-1 order (fragment reads
-// of a new stage issued in a block right behind the barrier, one prefetch read per MFMA shadow), 1 = matrix pipe first
-// (the trailing sub-step starts behind the barrier, reads two per shadow at the head of every sub-step)
+// SCHED: K-step schedule of the generated body (tools/gen_gemm_asm.py::gen_pers).  Only 0 exists: the round-1 order (fragment
+// reads of a new stage issued in a block right behind the barrier, one prefetch read per MFMA shadow).  The generator's other
+// schedules lost their A/B runs in round 2 and were removed from it (profiles/r02_gemm_experiments.md).
 template <int BN, bool OUT_F32, int SCHED>
 __global__ void __launch_bounds__(512, 2) gemm256p_kernel(const GemmParams p) {
   constexpr int TM = BN == 256 ? OSKG256_TM : OSKG128_TM;
@@ -141,8 +141,8 @@ int launch_one(const GemmParams& p, hipStream_t st) {
 
 }  // namespace
 
-// 256 x 128 tiles, 8 waves, persistent workgroups (the generator's other K-step schedules and the 256-wide instantiation of
-// this frame lost their A/B runs in round 2 -- profiles/r02_gemm_experiments.md -- and are generator options only)
+// 256 x 128 tiles, 8 waves, persistent workgroups (other K-step schedules and the 256-wide instantiation of this frame lost
+// their A/B runs in round 2 -- profiles/r02_gemm_experiments.md -- and the generator no longer emits them)
 int launch_gemm256p(const GemmParams& p, int out_f32, hipStream_t st) {
   return out_f32 ? launch_one<128, true, 0>(p, st) : launch_one<128, false, 0>(p, st);
 }

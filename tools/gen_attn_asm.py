@@ -41,6 +41,8 @@ K(t+2), V(t+1), exp2 + pack of tile t, max of tile t+1.
 import argparse
 import os
 
+from asm_emit import ar, clobbers, header, vr, write_body
+
 THR_BITS = "0x41000000"                    # 8.0: move M when a score exceeds the reference by > 2^8
 
 
@@ -157,14 +159,6 @@ def operand_names(geo, nslot_k, nslot_v):
     names += ["nkvw"] if geo.PV16 else ((["nkw"] if geo.NKD % 4 or geo.NKD % 8 else []) + ["nvw"])
     assert len(names) <= 30, len(names)
     return names
-
-
-def vr(base, n=1):
-    return "v%d" % base if n == 1 else "v[%d:%d]" % (base, base + n - 1)
-
-
-def ar(base, n=1):
-    return "a%d" % base if n == 1 else "a[%d:%d]" % (base, base + n - 1)
 
 
 N2_BUDGET = {"m32": 24, "pv16": 9, "pv8": 60, "qk8": 96}   # filler cycles per MFMA shadow of the 256-row bodies (round 5: 24 / 9 instead of 30 / 13, as in
@@ -1415,6 +1409,10 @@ def main():
                 row.append({"x": "v"}.get(kind, kind))
         print("".join(row))
         return
+
+    def body(name, note, lines, labels):         # "@@" in a label -> a prefix that is unique per body and per emitted copy of it
+        write_body(os.path.join(args.out, name), "gen_attn_asm.py", note, [ln.replace("@@", labels) for ln in lines])
+
     for hd, nu, pv8, qk8 in layouts:
         L = mk(nu, hd, pv8, qk8)
         DMAGAP, DMACOST = 1, 12
@@ -1425,11 +1423,8 @@ def main():
         DMAGAP, DMACOST = 1, 12
         what = "production" if not args.exp else ("hazard-padded (debug)" if safe else ("schedule experiment " + args.exp if gap else
                                                                                          "timing ablation " + "+".join(sorted(ablate))))
-        with open(os.path.join(args.out, "attention_asm%s_n%d_v0.inc" % (tagof(hd, pv8, qk8), nu)), "w") as f:
-            f.write("// GENERATED by tools/gen_attn_asm.py -- do not edit.  head_dim %d%s, layout NU=%d: %s\n" %
-                    (hd, ", fp8 QK^T and P.V" if qk8 else (", fp8 P.V" if pv8 else ""), nu, what))
-            for ln in st.lines:
-                f.write('"%s\\n"\n' % ln.replace("@@", "osk%sn%dv0_%%=" % (tagof(hd, pv8, qk8), nu)))
+        body("attention_asm%s_n%d_v0.inc" % (tagof(hd, pv8, qk8), nu), "head_dim %d%s, layout NU=%d: %s" %
+             (hd, ", fp8 QK^T and P.V" if qk8 else (", fp8 P.V" if pv8 else ""), nu, what), st.lines, "osk%sn%dv0_%%=" % (tagof(hd, pv8, qk8), nu))
         if not pv8:   # the bounded / single-segment / whole-tile body of the same layout
             fexp = args.fast_exp or args.exp
             if fexp.startswith("dmagap"):
@@ -1438,25 +1433,17 @@ def main():
             Lf = Layout(nu, hd, pv8, pv16=L.PV16, nom=(hd == 128))   # hd 128: the padding k-step is dropped too
             stf = generate(Lf, safe, ablate, fast=True)
             DMAGAP, DMACOST = 1, 12
-            with open(os.path.join(args.out, "attention_asm%s_n%d_f0.inc" % (tagof(hd, pv8), nu)), "w") as f:
-                f.write("// GENERATED by tools/gen_attn_asm.py -- do not edit.  head_dim %d, layout NU=%d, FAST body (score bound, one "
-                        "segment of whole tiles): %s\n" % (hd, nu, what))
-                for ln in stf.lines:
-                    f.write('"%s\\n"\n' % ln.replace("@@", "osk%sn%df0_%%=" % (tagof(hd, pv8), nu)))
+            body("attention_asm%s_n%d_f0.inc" % (tagof(hd, pv8), nu), "head_dim %d, layout NU=%d, FAST body (score bound, one "
+                 "segment of whole tiles): %s" % (hd, nu, what), stf.lines, "osk%sn%df0_%%=" % (tagof(hd, pv8), nu))
     # the wide layout of head_dim 72 (4 query blocks per wave, 32-key sub-tiles): FAST body only
     LW = LayoutW()
     stw = generate_wide(LW, safe)
-    with open(os.path.join(args.out, "attention_asm72w_f0.inc"), "w") as f:
-        f.write("// GENERATED by tools/gen_attn_asm.py -- do not edit.  head_dim 72, WIDE layout (4 waves x 128 query rows, one 32-key half per "
-                "body), FAST body: %s\n" % ("production" if not args.exp else "experiment " + args.exp))
-        for ln in stw.lines:
-            f.write('"%s\\n"\n' % ln.replace("@@", "osk72wf0_%="))
+    body("attention_asm72w_f0.inc", "head_dim 72, WIDE layout (4 waves x 128 query rows, one 32-key half per "
+         "body), FAST body: %s" % ("production" if not args.exp else "experiment " + args.exp), stw.lines, "osk72wf0_%=")
     # register / operand contract for the wrapper
     with open(os.path.join(args.out, "attention_asm_regs.inc"), "w") as f:
-        f.write("// GENERATED by tools/gen_attn_asm.py -- do not edit.\n")
-        clobw = ['"v%d"' % i for i in range(LW.V_FIRST, LW.V_END)] + ['"a%d"' % i for i in range(0, LW.A_END)] + \
-                ['"s%d"' % i for i in range(S_FIRST, S_LAST + 1)] + ['"vcc"', '"scc"', '"memory"']
-        f.write("#define OSK72W_CLOBBERS %s\n" % ", ".join(clobw))
+        f.write(header("gen_attn_asm.py"))
+        f.write("#define OSK72W_CLOBBERS %s\n" % clobbers(LW.V_FIRST, LW.V_END - LW.V_FIRST, LW.A_END, S_FIRST, S_LAST))
         f.write("#define OSK72W_A_CLOBBERS %s\n" % ", ".join('"a%d"' % i for i in range(0, LW.A_END)))
         f.write("#define OSK72W_NSLOT %d\n" % LW.NSLOT)
         # register map the wrapper binds as asm operands (acc_quads.h): Q fragment words of block u = AGPRs AQ(u) .. + 4 NKS,
@@ -1480,9 +1467,7 @@ def main():
             P = "OSK%sN%d_" % (tagof(hd, pv8, qk8).upper(), nu)
             if L.PV16:
                 f.write("#define %sPV16 1\n#define OSK%s_NDB %d\n" % (P, tagof(hd, pv8).upper(), G.NDB))
-            clob = ['"v%d"' % i for i in range(L.V_FIRST, L.V_END)] + ['"a%d"' % i for i in range(0, L.A_END)] + \
-                   ['"s%d"' % i for i in range(S_FIRST, S_LAST + 1)] + ['"vcc"', '"scc"', '"memory"']
-            f.write("#define %sCLOBBERS %s\n" % (P, ", ".join(clob)))
+            f.write("#define %sCLOBBERS %s\n" % (P, clobbers(L.V_FIRST, L.V_END - L.V_FIRST, L.A_END, S_FIRST, S_LAST)))
             f.write("#define %sA_CLOBBERS %s\n" % (P, ", ".join('"a%d"' % i for i in range(0, L.A_END))))
             f.write("#define %sNSLOT %d\n" % (P, L.NSLOT))
             if pv8:

@@ -42,6 +42,8 @@ wait, no LDS region is refilled before a barrier behind its last read or read be
 import argparse
 import os
 
+from asm_emit import ar, clobbers, header, vr, write_body
+
 NB = 8                      # 16-voxel row blocks per wave tile
 TAPS = 27
 BODY = 2 * TAPS             # steps per loop body (two channel blocks)
@@ -70,14 +72,6 @@ S_G = 64                                         # GN form, 64-bit: the (scale, 
 S_MASK, S_NL2E = 66, 67                          # GN form: 0xffff0000, -log2(e) (4-byte encodings instead of 8 with a literal)
 S_FIRST, S_LAST = 40, 63
 S_X = [S_X0, S_X1, S_X2, S_X3]
-
-
-def vr(b, n=1):
-    return "v%d" % b if n == 1 else "v[%d:%d]" % (b, b + n - 1)
-
-
-def ar(b, n=1):
-    return "a%d" % b if n == 1 else "a[%d:%d]" % (b, b + n - 1)
 
 
 class Cfg:
@@ -539,11 +533,6 @@ def body_lines(c):
     return [o.text if o.kind == "L" else "  " + o.text for o in generate(c)]
 
 
-def clobbers(c):
-    return ['"v%d"' % i for i in range(c.V0, c.V0 + c.VN)] + ['"a%d"' % i for i in range(c.NACC)] + \
-           ['"s%d"' % i for i in range(S_FIRST, c.S_LAST + 1)] + ['"vcc"', '"scc"', '"memory"']
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "open_sora_amd", "csrc"))
@@ -555,30 +544,26 @@ def main():
         if "windows" in exp:       # {"f2" | "plain": {start: [slot, T0, T1]}}
             exp["windows"] = {k == "f2": {int(st): tuple(v) for st, v in d.items()} for k, d in exp["windows"].items()}
         GN_EXP.update(exp)
-    c = Cfg(8, f2=True)
-    with open(os.path.join(args.out, "convswf_body_n128.inc"), "w") as f:
-        f.write("// GENERATED by tools/gen_conv_sw_asm.py -- do not edit.  Sliding-window CausalConv3d K loop, two-frame form: 16 x 16 voxel "
-                "brick of 2 frames x 128 channels, two 32-channel blocks x 27 taps per body.\n")
-        for ln in body_lines(c):
-            f.write('"%s\\n"\n' % ln)
+
+    def body(name, note, c):
+        write_body(os.path.join(args.out, name), "gen_conv_sw_asm.py", "Sliding-window CausalConv3d K loop" + note, body_lines(c))
+
+    def regs_of(c):
+        return clobbers(c.V0, c.VN, c.NACC, S_FIRST, c.S_LAST)
+
+    body("convswf_body_n128.inc", ", two-frame form: 16 x 16 voxel brick of 2 frames x 128 channels, two 32-channel blocks x 27 taps per body.",
+         Cfg(8, f2=True))
     for up in (False, True):
         for nbj in (8, 4):
             c = Cfg(nbj, up)
-            with open(os.path.join(args.out, "convsw%s_body_n%d.inc" % ("u" if up else "", c.BN)), "w") as f:
-                f.write("// GENERATED by tools/gen_conv_sw_asm.py -- do not edit.  Sliding-window CausalConv3d K loop%s: 16 x 16 voxel brick x "
-                        "%d channels, two 32-channel blocks x 27 taps per body.\n" % (" (nearest 2x upsample folded in)" if up else "", c.BN))
-                for ln in body_lines(c):
-                    f.write('"%s\\n"\n' % ln)
+            body("convsw%s_body_n%d.inc" % ("u" if up else "", c.BN), "%s: 16 x 16 voxel brick x %d channels, two 32-channel blocks x 27 taps per body."
+                 % (" (nearest 2x upsample folded in)" if up else "", c.BN), c)
     for f2 in (False, True):
         c = Cfg(8, f2=f2, gn=True)
-        with open(os.path.join(args.out, "convswg%s_body_n%d.inc" % ("f" if f2 else "", c.BN)), "w") as f:
-            f.write("// GENERATED by tools/gen_conv_sw_asm.py -- do not edit.  Sliding-window CausalConv3d K loop, GN form (the input is "
-                    "silu(GroupNorm(x)), applied in the halo refill)%s: 16 x 16 voxel brick x %d channels, two 32-channel blocks x 27 taps per body.\n"
-                    % (", two-frame form" if f2 else "", c.BN))
-            for ln in body_lines(c):
-                f.write('"%s\\n"\n' % ln)
+        body("convswg%s_body_n%d.inc" % ("f" if f2 else "", c.BN), ", GN form (the input is silu(GroupNorm(x)), applied in the halo refill)%s: "
+             "16 x 16 voxel brick x %d channels, two 32-channel blocks x 27 taps per body." % (", two-frame form" if f2 else "", c.BN), c)
     with open(os.path.join(args.out, "convsw_regs.inc"), "w") as f:
-        f.write("// GENERATED by tools/gen_conv_sw_asm.py -- do not edit.\n")
+        f.write(header("gen_conv_sw_asm.py"))
         for up in (False, True):
             for nbj in (8, 4):
                 c = Cfg(nbj, up)
@@ -588,10 +573,10 @@ def main():
         f.write("#define OSKSWF128_SMEM %d\n#define OSKSWF128_SLOT %d\n" % (c.SMEM, c.SLOT))
         for nbj in (8, 4):                       # the register footprint does not depend on the halo geometry
             c = Cfg(nbj)
-            f.write("#define OSKSW%d_CLOBBERS %s\n" % (c.BN, ", ".join(clobbers(c))))
+            f.write("#define OSKSW%d_CLOBBERS %s\n" % (c.BN, regs_of(c)))
         for f2 in (False, True):                 # GN form: + the register ring (6 / 8 quads), 16 scale / shift registers, 8 temporaries
             c = Cfg(8, f2=f2, gn=True)
-            f.write("#define OSKSWG%s_CLOBBERS %s\n" % ("F128" if f2 else "256", ", ".join(clobbers(c))))
+            f.write("#define OSKSWG%s_CLOBBERS %s\n" % ("F128" if f2 else "256", regs_of(c)))
 
 
 if __name__ == "__main__":
