@@ -26,7 +26,8 @@
 extern "C" {
 #endif
 
-/* (round 6 added osk_gemm_group_bf16 without changing any existing contract: the version stays 2.)
+/* (osk_attention_merge_bf16 was added the same way: a new entry, no existing contract changed.)
+ * (round 6 added osk_gemm_group_bf16 without changing any existing contract: the version stays 2.)
  * 2 (round 5): osk_copy_rows_bf16 added; and the contracts that changed under version 1 during round 4 are now versioned -- the
  * key order osk_v_transpose_bf16 bakes into V^T for head_dim 64 (the 16x16x32 order of head_dim 72: attention_fwd.hip), the entry
  * points osk_gemm_geglu_bf16 / osk_attention_short_bf16 / osk_attention_hd512_fwd_ws_bf16 / osk_causal_conv3d_gnin_ndhwc_bf16.
@@ -301,6 +302,24 @@ int osk_attention_fwd_auto_bf16(const void* q, int64_t q_batch_stride, int64_t q
                            float* lse, int B, int H, int Lq, int n_seg, int seg_len, int hd,
                            float scale, int q_prescaled, int kv_batches, const float* q_norm2_max, const float* k_norm2_max,
                            void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- merge of S attention results over DISJOINT key sets by their log-sum-exp.
+ * replaces _rescale_out_lse / the per-hop update of the ring attention (opensora/models/mmdit/distributed.py:223-313), applied
+ * once to all S parts: the sequence-parallel K / V^T all-gather cut into S key slices (open_sora_amd/seqpar.py, kv_chunks) runs
+ * osk_attention_fwd_bounded_bf16 on slice s as soon as gather s has arrived and combines the S (out, lse) pairs here.
+ * parts   bf16 [S, B, L, H*hd]: row (s, b, l) at parts + s*part_stride + b*p_batch_stride + l*p_row_stride (elements, multiples
+ *         of 8; row strides >= H*hd; 16-byte aligned pointer; last dim contiguous)
+ * lse     f32 [S, B, H, L] contiguous, natural log, as osk_attention_fwd_bf16 writes it; -inf = a part that saw no key
+ * out     bf16 [B, L, H*hd] with its own batch / row strides (same rules); must not overlap parts
+ * lse_out f32 [B, H, L] contiguous, or NULL
+ * Per (b, l, h):  m = max_s lse_s,  w_s = exp(lse_s - m) (0 for lse_s = -inf),  out = bf16(sum_s w_s part_s / sum_s w_s) with the
+ * sums in f32 and ONE rounding,  lse_out = m + log sum_s w_s.  Every lse_s = -inf: out = 0 and lse_out = -inf, never NaN.
+ * 1 <= S <= 8 and hd % 8 == 0 (else OSK_EINVAL); H <= 512 and B <= 65535 (else OSK_EUNSUPPORTED).  HBM-bound: (S + 1) row images,
+ * 16-byte loads and stores, each lse value read once per (row, head).  No allocation, no memset, no synchronisation: capturable
+ * in a hipGraph. */
+int osk_attention_merge_bf16(const void* parts, int64_t part_stride, int64_t p_batch_stride, int64_t p_row_stride,
+                             const float* lse, void* out, int64_t o_batch_stride, int64_t o_row_stride, float* lse_out,
+                             int S, int B, int H, int L, int hd, void* stream);
 
 /* ---- fp8 P.V variant of the attention (opt-in fp8 mode, BASELINE configs[4]; head_dim 72 / 128): QK^T, the softmax and
  * the output as osk_attention_fwd_ws_bf16, but P (<= 2^8 by construction) and V^T are OCP e4m3 and a 64-key tile's P.V

@@ -53,6 +53,7 @@ SIGNATURES = {
                                        _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _f32, _vp, _i64, _vp],
     "osk_attention_fwd_auto_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp,
                                     _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _vp, _vp, _vp, _i64, _vp],
+    "osk_attention_merge_bf16": [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "osk_rownorm2_max_bf16": [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp],
     "osk_attention_workspace_bytes": [],
     "osk_v_scale_fp8": [_vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _vp],
@@ -543,6 +544,26 @@ def attention_fwd_auto(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: 
     assert qn2.dtype == kn2.dtype == torch.float32 and qn2.numel() == B * H and kn2.numel() == (kv_batches or B) * H
     return _attn_call("osk_attention_fwd_auto_bf16", q, k, vt, out, H, hd, scale, lse, n_seg, seg_len, k_seg_stride, vt_seg_stride,
                       q_prescaled, kv_batches, workspace, own=(qn2.data_ptr(), kn2.data_ptr()))
+
+
+def attention_merge(parts: torch.Tensor, lse: torch.Tensor, out: torch.Tensor, H: int, hd: int,
+                    lse_out: torch.Tensor | None = None) -> torch.Tensor:
+    """out = the S attention results `parts` over disjoint key sets, merged by their log-sum-exp (osk_attention_merge_bf16):
+    parts bf16 [S, B, L, H*hd] view (last dim contiguous, the other strides its own), lse f32 [S, B, H, L] contiguous (what
+    attention_fwd(..., lse=) wrote beside each part), out bf16 [B, L, H*hd] view, lse_out f32 [B, H, L] contiguous or None."""
+    assert parts.dim() == 4 and lse.dim() == 4 and out.dim() == 3, (parts.shape, lse.shape, out.shape)
+    S, B, L, D = parts.shape
+    assert 1 <= S <= 8 and D == H * hd and hd % 8 == 0, (parts.shape, H, hd)
+    assert parts.dtype == torch.bfloat16 and out.dtype == torch.bfloat16 and tuple(out.shape) == (B, L, D), (parts.dtype, out.dtype, out.shape)
+    assert lse.dtype == torch.float32 and lse.is_contiguous() and tuple(lse.shape) == (S, B, H, L), (lse.dtype, lse.shape, lse.stride())
+    for t in (parts, out):
+        assert t.stride(-1) == 1 and all(st % 8 == 0 for st in t.stride()[:-1]) and t.data_ptr() % 16 == 0, (t.stride(), t.data_ptr() % 16)
+    if lse_out is not None:
+        assert lse_out.dtype == torch.float32 and lse_out.is_contiguous() and tuple(lse_out.shape) == (B, H, L), (lse_out.dtype, lse_out.shape)
+    _check(lib.osk_attention_merge_bf16(parts.data_ptr(), parts.stride(0), parts.stride(1), parts.stride(2), lse.data_ptr(),
+                                        out.data_ptr(), out.stride(0), out.stride(1), _p(lse_out), S, B, H, L, hd, _stream()),
+           "osk_attention_merge_bf16")
+    return out
 
 
 def attention_short(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, H: int, hd: int, scale: float,

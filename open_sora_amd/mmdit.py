@@ -1028,7 +1028,13 @@ class MMDiTModel(_OskState, nn.Module):
         bounds = [float(p.score_bound) for p in plans]
         bodies = sorted({_OPS.attention_body(hd, n_seg, seg_len, b) for b in bounds}) if hasattr(_OPS, "attention_body") else []
         auto = sum(1 for b in bounds if not (0.0 < b <= SCORE_BOUND_LIMIT)) if AUTO_BOUND and hasattr(_OPS, "attention_fwd_auto") else 0
-        return {"score_bound_min": min(bounds), "score_bound_max": max(bounds), "bound_limit": SCORE_BOUND_LIMIT, "bodies": bodies,
+        # key slices the sequence-parallel K / V^T gather is cut into (seqpar.enable(kv_chunks=...)): 1 without sequence parallelism,
+        # in head-exchange mode and for the fp8 attention; with n_seg > 1 and a seg_len, the count that applies to a rank of seg_len rows
+        sp = getattr(self, "_sp", None)
+        chunks = 1
+        if sp is not None and hasattr(sp, "kv_chunks_applied"):
+            chunks = sp.kv_chunks_applied(self.num_heads, any(p.pv8 for p in plans), seg_len if n_seg > 1 else 0)
+        return {"kv_chunks": chunks, "score_bound_min": min(bounds), "score_bound_max": max(bounds), "bound_limit": SCORE_BOUND_LIMIT, "bodies": bodies,
                 "blocks_on_fast_body": sum(1 for b in bounds if 0.0 < b <= SCORE_BOUND_LIMIT), "blocks": len(bounds),
                 # blocks whose weight-derived bound is too large: FAST / general chosen per (batch, head) on the device from the operands
                 "blocks_auto_dispatched": auto}

@@ -19,6 +19,14 @@ The transport is an object (`all_gather / all_to_all / all_reduce_max`, each ret
 process on ONE GPU with device-copy "collectives" on per-rank communication streams (tests/test_gpu_overlap.py), which
 exercises the same event protocol and the overlap itself where no multi-GPU node is available.
 
+Chunked gather (kv_chunks = S > 1, opt-in; all-gather mode with bf16 attention): the one launch cannot start before the last byte
+of K and V^T has arrived, and only the Q projection (+ MLP-up) hides that.  The reference hides its exchange under attention itself
+(ring: compute on one key block while the next travels, merge by log-sum-exp, distributed.py:223-313).  The xGMI form keeps the full
+mesh: the gather is cut into S gathers over key sub-ranges (rows [s L/(P S), (s + 1) L/(P S)) of every rank), all issued up front on
+the communication stream; attention launch s waits for gather s only and returns (out, lse); osk_attention_merge_bf16 combines the S
+partials in one HBM-bound pass.  The cost side (S launches + the merge) is measured in profiles/sp_chunked.md; the hidden-exchange
+side needs a multi-GPU node, so the default stays S = 1.
+
 Head-parallel exchange ("ulysses", the reference's other mode, distributed.py:473-495): when the head count divides
 by P the block can instead all-to-all q, k, v from "my tokens, all heads" to "all tokens, my H/P heads", run the flash
 kernel on whole sequences of H/P heads and all-to-all the result back.  Per rank and block it moves
@@ -113,7 +121,7 @@ class SeqPar:
     """Per-model sequence-parallel state: process group + the gathered K / V^T buffers (allocated once per
     geometry, reused by all 28/57 blocks: 2 * B * L * D * 2 bytes)."""
 
-    def __init__(self, group=None, mode: str | None = None, transport=None):
+    def __init__(self, group=None, mode: str | None = None, transport=None, kv_chunks: int | None = None):
         self.tp = transport if transport is not None else DistTransport(group)
         self.P, self.rank = self.tp.P, self.tp.rank
         self._bufs = {}
@@ -121,6 +129,11 @@ class SeqPar:
         self.mode = mode or os.environ.get("OSK_SP_MODE", "auto")   # "allgather" | "ulysses" | "auto"
         if self.mode not in ("allgather", "ulysses", "auto"):
             raise ValueError(f"unknown sequence-parallel mode {self.mode!r}")
+        # all-gather mode, bf16 attention: cut the K / V^T gather into up to `kv_chunks` key slices and run the attention slice by
+        # slice behind their arrival (gather_kv_start / attention below).  1 = one gather, one launch, no merge.
+        self.kv_chunks = int(os.environ.get("OSK_SP_KV_CHUNKS", "1") if kv_chunks is None else kv_chunks)
+        if not 1 <= self.kv_chunks <= self.MAX_KV_CHUNKS:
+            raise ValueError(f"kv_chunks must be in 1 .. {self.MAX_KV_CHUNKS}, not {self.kv_chunks}")
 
     # ------------------------------------------------------------------ exposed-communication accounting (bench.py --gpus N)
     def _timed_wait(self, work, what: str):
@@ -168,6 +181,19 @@ class SeqPar:
     # ------------------------------------------------------------------ K/V exchange
     MAX_GEOMETRIES = 4   # exchange-buffer sets kept (least recently used first out)
     kv_qk8 = True        # gather_kv_start takes qk8 (mmdit._sp_qk8 asks before it passes the argument)
+    MAX_KV_CHUNKS = 8    # parts osk_attention_merge_bf16 takes
+
+    def kv_chunks_for(self, Lloc: int) -> int:
+        """key slices S the gather of a rank with Lloc rows is cut into: the largest S <= kv_chunks that divides Lloc -- equal
+        slices keep every collective a plain all_gather_into_tensor (a prime Lloc: 1)"""
+        return max(s for s in range(1, max(1, min(self.kv_chunks, Lloc)) + 1) if Lloc % s == 0)
+
+    def kv_chunks_applied(self, H: int, pv8: bool = False, Lloc: int = 0) -> int:
+        """the S attention() runs with (reporting: MMDiTModel.attention_report): head-exchange mode needs the whole sequence of a
+        head and the fp8 handles the reduced e4m3 scale before the first key is used -- both keep the single gather"""
+        if self.head_parallel(H) or pv8:
+            return 1
+        return self.kv_chunks_for(Lloc) if Lloc else self.kv_chunks
 
     def _cached(self, key, make):
         """exchange buffers of one (kind, geometry, device, stream), least-recently-used eviction: an i2v run that alternates between
@@ -209,11 +235,25 @@ class SeqPar:
 
         return self._cached(("qk8", B, Lloc, H, hd, str(device), mmdit._stream_key(device)), make)
 
+    def _buffers_chunked(self, B: int, Lloc: int, S: int, H: int, hd: int, device):
+        """kv_chunks: the gather buffers cut into S key slices of Lc = Lloc / S rows -- K [S, P, B, Lc, D], V^T
+        [S, P, B, H, hd, round_up(Lc, 64)] (zero-filled: the key padding of a ragged slice) -- and the S partial results the slices'
+        attention launches write: out [S, B, Lloc, D] bf16 and lse [S, B, H, Lloc] f32 (S more images of this rank's rows)"""
+        def make():
+            Lc = Lloc // S
+            Lcp = (Lc + 63) // 64 * 64
+            return (torch.empty(S, self.P, B, Lc, H * hd, dtype=BF16, device=device),
+                    torch.zeros(S, self.P, B, H, hd, Lcp, dtype=BF16, device=device),
+                    torch.empty(S, B, Lloc, H * hd, dtype=BF16, device=device),
+                    torch.empty(S, B, H, Lloc, dtype=torch.float32, device=device))
+
+        return self._cached(("chunks", S, B, Lloc, H, hd, str(device), mmdit._stream_key(device)), make)
+
     def local_vt(self, B: int, Lloc: int, H: int, hd: int, device):
         """this rank's slot [B, H, hd, round_up(L/P, 64)] of the gathered V^T buffer (all-gather mode, bf16), or None: the projection
         may write V straight into it as V^T (osk_gemm_group_bf16's V^T task, round 6) -- gather_kv_start(..., vt_ready=True) then
-        skips the osk_v_transpose_bf16 pass"""
-        if self.head_parallel(H):
+        skips the osk_v_transpose_bf16 pass.  None with kv_chunks too: the V^T task writes ONE contiguous slot, the slices are S."""
+        if self.head_parallel(H) or self.kv_chunks_for(Lloc) > 1:
             return None
         return self._buffers(B, Lloc, H, hd, device)[1][self.rank]
 
@@ -255,6 +295,24 @@ class SeqPar:
             mmdit.ops().v_transpose_fp8(v, sv, vt8_all[self.rank], H, hd)
             wv = self.tp.all_gather(vt8_all.view(-1), vt8_all[self.rank].view(-1))
             return "pv8", k_all, vt8_all, sv, wk, wv
+        S = self.kv_chunks_for(Lloc)
+        if S > 1:
+            # S gathers over key sub-ranges, all issued up front on the communication stream (the full mesh stays: no ring hops);
+            # slice s = rows [s Lc, (s + 1) Lc) of EVERY rank.  The gather of slice s is issued before the copies of slice s + 1 are
+            # queued, so it travels beside them -- and beside the Q projection -- and attention() starts on slice 0 while 1 .. S-1 travel
+            assert not vt_ready, "local_vt() is None with kv_chunks: the projection writes V token-major"
+            ops = mmdit.ops()
+            k_all, vt_all, parts, lses = self._buffers_chunked(B, Lloc, S, H, hd, k.device)
+            Lc = Lloc // S
+            works = []
+            for s in range(S):
+                rows = slice(s * Lc, (s + 1) * Lc)
+                ops.copy_rows(k[:, rows], k_all[s, self.rank])
+                ops.v_transpose(v[:, rows], vt_all[s, self.rank], H, hd)
+                wk = self.tp.all_gather(k_all[s].view(-1), k_all[s, self.rank].view(-1))
+                wv = self.tp.all_gather(vt_all[s].view(-1), vt_all[s, self.rank].view(-1))
+                works.append((wk, wv))
+            return "chunks", k_all, vt_all, parts, lses, works
         k_all, vt_all = self._buffers(B, Lloc, H, hd, k.device)
         mmdit.ops().copy_rows(k, k_all[self.rank])
         if not vt_ready:                       # (vt_ready: the V projection already wrote local_vt())
@@ -278,6 +336,20 @@ class SeqPar:
             ops.attention_fwd_qk8(q, k8_all[0], s2[0], vt8_all, s2[1], out, H, hd, hd ** -0.5, seg_len=Lloc, n_seg=self.P,
                                   k_seg_stride=k8_all.stride(0), vt_seg_stride=vt8_all.stride(0), q_prescaled=True,
                                   workspace=ops.attention_workspace(q.device))
+            return
+        if isinstance(pending[0], str) and pending[0] == "chunks":
+            # slice s: P key segments of Lc keys, its own wait -- the launch on slice s runs while slices s + 1 .. travel -- into
+            # partial s with its log-sum-exp; ONE merge launch combines them (distributed.py:223-313 merges hop by hop)
+            _, k_all, vt_all, parts, lses, works = pending
+            Lc = k_all.shape[3]
+            wsp = ops.attention_workspace(q.device)
+            for s, (wk, wv) in enumerate(works):
+                self._timed_wait(wk, "k")
+                self._timed_wait(wv, "v")
+                ops.attention_fwd(q, k_all[s, 0], vt_all[s], parts[s], H, hd, hd ** -0.5, lse=lses[s], n_seg=self.P, seg_len=Lc,
+                                  k_seg_stride=k_all.stride(1), vt_seg_stride=vt_all.stride(1), q_prescaled=True,
+                                  workspace=wsp, score_bound=score_bound)
+            ops.attention_merge(parts, lses, out, H, hd)
             return
         if isinstance(pending[0], str):   # "pv8"
             _, k_all, vt8_all, sv, wk, wv = pending
@@ -395,11 +467,14 @@ class SeqPar:
         return full.permute(1, 0, 2, 3).reshape(B, self.P * Lloc, C_out)[:, L_txt:].contiguous()
 
 
-def enable(model, group=None, mode: str | None = None, transport=None) -> SeqPar:
+def enable(model, group=None, mode: str | None = None, transport=None, kv_chunks: int | None = None) -> SeqPar:
     """Shard `model`'s denoise step over `group` (default: WORLD).  The counterpart of installing
     MMDiTPolicy / Distributed*Processor through booster.boost (distributed.py:686-760): weights stay replicated,
-    MMDiTModel.forward keeps its signature and returns the full prediction on every rank."""
-    sp = SeqPar(group, mode, transport)
+    MMDiTModel.forward keeps its signature and returns the full prediction on every rank.
+    kv_chunks (default: OSK_SP_KV_CHUNKS, else 1): all-gather mode with bf16 attention cuts the K / V^T gather into that many key
+    slices (the largest count <= kv_chunks that divides a rank's rows) and runs the attention slice by slice behind their arrival,
+    merged by log-sum-exp; 1 = one gather and one launch.  Head-exchange mode and the fp8 attention ignore it."""
+    sp = SeqPar(group, mode, transport, kv_chunks)
     model._sp = sp if sp.P > 1 else None
     return sp
 

@@ -42,6 +42,26 @@ PY
 )" | tee -a "$OUT/summary.txt"
   done
 done
+# 2b. the chunked K / V^T gather (seqpar.enable(kv_chunks=S); all-gather mode, bf16): the same line per S -- what the slices HIDE shows in
+#     `exposed` (the "k" / "v" stalls of the compute stream) against the S = 1 line of the allgather leg above; what they cost on one GPU is
+#     profiles/sp_chunked.md.  Until this sweep has run on a multi-GPU node the default stays S = 1.
+for chunks in 2 4 8; do
+  for n in 2 4 8; do
+    [ "$n" -gt "$NGPU" ] && continue
+    f="$OUT/bench_allgather_chunks${chunks}_n$n"
+    OSK_SP_MODE=allgather OSK_SP_KV_CHUNKS=$chunks timeout 1200 bash -c "$(declare -f run_n port); run_n $n bench.py --full --gpus $n --steps $STEPS --warmup $WARM --no-cpu-baseline --no-extra --no-b1" \
+      > "$f.json" 2> "$f.err"
+    echo "bench mode=allgather kv_chunks=$chunks n=$n rc=$? $(python - "$f.json" <<'PY'
+import json, sys
+try:
+    r = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
+    print(f"ms_per_step={r['ms_per_step']} value={r['value']} exposed={r.get('rccl', {}).get('exposed_comm_ms_per_step_rank0')}")
+except Exception as e:
+    print("no line:", e)
+PY
+)" | tee -a "$OUT/summary.txt"
+  done
+done
 # 3. kernel trace of the widest step (all ranks; rank 0's file is the one to read): RCCL kernels beside the MFMA loops
 N=$NGPU; [ "$N" -gt 8 ] && N=8
 ( cd /tmp && timeout 1500 rocprofv3 --kernel-trace --stats -d "$OLDPWD/$OUT/prof_n$N" -- bash -c "cd $OLDPWD && $(declare -f run_n port); run_n $N bench.py --full --gpus $N --steps 4 --warmup 2 --no-cpu-baseline --no-extra --no-b1" \
