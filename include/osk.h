@@ -26,7 +26,9 @@
 extern "C" {
 #endif
 
-/* (osk_attention_merge_bf16 was added the same way: a new entry, no existing contract changed.)
+/* (osk_attention_fwd_ragged_bf16 / osk_attention_ragged_workspace_bytes / osk_attention_merge_into_bf16 -- sequence parallelism over
+ * token counts the rank count does not divide -- are additive entries too: the version stays 2, as the suite pins it.)
+ * (osk_attention_merge_bf16 was added the same way: a new entry, no existing contract changed.)
  * (round 6 added osk_gemm_group_bf16 without changing any existing contract: the version stays 2.)
  * 2 (round 5): osk_copy_rows_bf16 added; and the contracts that changed under version 1 during round 4 are now versioned -- the
  * key order osk_v_transpose_bf16 bakes into V^T for head_dim 64 (the 16x16x32 order of head_dim 72: attention_fwd.hip), the entry
@@ -389,6 +391,49 @@ int osk_attention_fwd_qk8_bf16(const void* q, int64_t q_batch_stride, int64_t q_
                                float* lse, int B, int H, int Lq, int n_seg, int seg_len, int hd,
                                float scale, int q_prescaled, int kv_batches, void* workspace, int64_t workspace_bytes,
                                void* stream);
+
+/* ---- attention over key segments whose LAST one is shorter (sequence parallelism over a token count L the rank count P does not
+ * divide: ranks 0 .. P-2 own Lc = ceil(L / P) rows, the last one Lt = L - (P-1) Lc; open_sora_amd/seqpar.py).  The reference refuses
+ * such lengths (opensora/models/mmdit/distributed.py:604-608); the arithmetic replaced is that of the entries above.
+ * The hand-scheduled kernels bake one ragged-tile mask per launch, so the call enqueues, on `stream`:
+ *   A  the n_seg - 1 full segments (seg_len keys each) into out / lse, exactly as the entry of that operand kind would,
+ *   B  the last segment alone (n_seg = 1, seg_len = last_seg_len, down to one key) into f32 partials in the workspace,
+ *   M  one in-place merge of B's partial into A's rows by their log-sum-exp (osk_attention_merge_into_bf16's kernel).
+ * Each launch picks its loop body by the normal rules (A with several segments of fewer than 3 tiles: the general body).
+ * mode: which operands k / vt are, shared by both launches --
+ *   OSK_ATTN_BF16  as osk_attention_fwd_bounded_bf16 (score_bound as there; k_scale, v_scale ignored),
+ *   OSK_ATTN_PV8   as osk_attention_fwd_pv8_bf16   (vt = vt8, vt_seg_stride in bytes, v_scale; score_bound must be 0 or is ignored),
+ *   OSK_ATTN_QK8   as osk_attention_fwd_qk8_bf16   (k = k8 with byte strides, k_row_stride = 128, k_scale; vt = vt8, v_scale).
+ * Layout of the last segment: n_seg - 1 segment strides behind the first, written as a tensor of last_seg_len keys OF ITS OWN -- V^T
+ *   rows of round_up(last_seg_len, 64) positions (what osk_v_transpose_bf16 / osk_v_transpose_fp8 write for L = last_seg_len), e4m3 K
+ *   [Bkv, H, round_up(last_seg_len, 64), 128] (osk_k_pack_fp8 for L = last_seg_len); bf16 K keeps k_batch_stride / k_row_stride.
+ * out: 16-byte aligned, strides multiples of 8 (the merge moves 16-byte pieces); lse f32 [B, H, Lq] or NULL.
+ * workspace: required (NULL or fewer bytes than the partials need: OSK_EINVAL); osk_attention_ragged_workspace_bytes(B, H, Lq, hd) is
+ *   always enough and leaves launch A the tail-split room of osk_attention_workspace_bytes().
+ * 2 <= n_seg, 1 <= last_seg_len <= seg_len (else OSK_EINVAL).  No allocation, no memset, no host synchronisation: capturable in a
+ * hipGraph.  Cost over one launch on a divisible length: one more launch (its workgroups walk one segment) + the merge, which
+ * moves 8 bytes per output element. */
+#define OSK_ATTN_BF16 0
+#define OSK_ATTN_PV8 1
+#define OSK_ATTN_QK8 2
+int64_t osk_attention_ragged_workspace_bytes(int B, int H, int Lq, int hd);
+int osk_attention_fwd_ragged_bf16(const void* q, int64_t q_batch_stride, int64_t q_row_stride,
+                                  const void* k, int64_t k_seg_stride, int64_t k_batch_stride, int64_t k_row_stride,
+                                  const float* k_scale, const void* vt, int64_t vt_seg_stride, const float* v_scale,
+                                  void* out, int64_t o_batch_stride, int64_t o_row_stride, float* lse,
+                                  int B, int H, int Lq, int n_seg, int seg_len, int last_seg_len, int hd,
+                                  float scale, int q_prescaled, int kv_batches, float score_bound, int mode,
+                                  void* workspace, int64_t workspace_bytes, void* stream);
+/* The merge on its own: fold the result of a second attention over OTHER keys into a finished (out, lse) pair, in place.
+ * out   bf16 [B, Lq, H*hd] view (16-byte aligned, strides multiples of 8, row stride >= H*hd): read and overwritten
+ * lse   f32 [B, H, Lq] contiguous, natural log: read and overwritten with the merged value
+ * o_b   f32 [B, H, Lqp, hd] contiguous, Lqp = Lq rounded up to 256 (rows >= Lq are never read), 16-byte aligned: normalised partial
+ * lse_b f32 [B, H, Lqp] contiguous, natural log; -inf = a part that saw no key (its o_b row is then not used)
+ * Per (b, l, h) as osk_attention_merge_bf16 with S = 2: f32 sums, ONE rounding; both -inf: out = 0, lse = -inf.
+ * hd in {64, 72, 128} (else OSK_EUNSUPPORTED).  HBM: out read + written (2 + 2 bytes per element) + o_b read (4): no third image
+ * of the rows, where osk_attention_merge_bf16 with S = 2 moves 6 bytes per element and needs two partial images beside out. */
+int osk_attention_merge_into_bf16(void* out, int64_t o_batch_stride, int64_t o_row_stride, float* lse, const float* o_b,
+                                  const float* lse_b, int B, int H, int Lq, int hd, void* stream);
 
 /* ---- short-sequence attention with an optional ALiBi bias (the STDiT-generation block's temporal
  * self-attention over T <= 64 frames, B * H * W independent sequences, "RoPE/ALiBi" in BASELINE.json's north_star).  The mounted

@@ -54,6 +54,10 @@ SIGNATURES = {
     "osk_attention_fwd_auto_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp,
                                     _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _vp, _vp, _vp, _i64, _vp],
     "osk_attention_merge_bf16": [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
+    "osk_attention_ragged_workspace_bytes": [_i32, _i32, _i32, _i32],
+    "osk_attention_fwd_ragged_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp,
+                                      _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _f32, _i32, _vp, _i64, _vp],
+    "osk_attention_merge_into_bf16": [_vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
     "osk_rownorm2_max_bf16": [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp],
     "osk_attention_workspace_bytes": [],
     "osk_v_scale_fp8": [_vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _vp],
@@ -113,7 +117,8 @@ def _load() -> C.CDLL:
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.argtypes = argtypes
         fn.restype = (C.c_char_p if name in ("osk_arch", "osk_attention_kernel_name", "osk_attention_body_name") else
-                      _i64 if name in ("osk_attention_workspace_bytes", "osk_attention_hd512_workspace_bytes") else _i32)
+                      _i64 if name in ("osk_attention_workspace_bytes", "osk_attention_hd512_workspace_bytes",
+                                       "osk_attention_ragged_workspace_bytes") else _i32)
     if lib.osk_abi_version() != 2:
         raise ImportError("libosk_hip.so ABI version mismatch")
     return lib
@@ -563,6 +568,81 @@ def attention_merge(parts: torch.Tensor, lse: torch.Tensor, out: torch.Tensor, H
     _check(lib.osk_attention_merge_bf16(parts.data_ptr(), parts.stride(0), parts.stride(1), parts.stride(2), lse.data_ptr(),
                                         out.data_ptr(), out.stride(0), out.stride(1), _p(lse_out), S, B, H, L, hd, _stream()),
            "osk_attention_merge_bf16")
+    return out
+
+
+def attention_ragged_workspace(B: int, H: int, Lq: int, hd: int, device) -> torch.Tensor:
+    """workspace of attention_fwd_ragged for these query dimensions, one per (device, stream) like attention_workspace(): the f32
+    partials of the last-segment launch, launch A's lse, and the tail-split room of a plain call.  Grows to the largest request."""
+    dev = torch.device(device)
+    key = ("ragged", str(dev), torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0)
+    need = lib.osk_attention_ragged_workspace_bytes(B, H, Lq, hd)
+    ws = _ATTN_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _ATTN_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+    return ws
+
+
+def attention_fwd_ragged(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Tensor, H: int, hd: int, scale: float, *,
+                         n_seg: int, seg_len: int, last_seg_len: int, k_seg_stride: int, vt_seg_stride: int, workspace: torch.Tensor,
+                         lse=None, q_prescaled: bool = False, kv_batches: int = 0, score_bound: float = 0.0,
+                         k_scale: torch.Tensor | None = None, v_scale: torch.Tensor | None = None):
+    """attention over n_seg key segments of seg_len keys whose LAST holds last_seg_len <= seg_len (osk_attention_fwd_ragged_bf16):
+    one launch over the full segments, one over the last, one in-place merge.  Operands by the scales given: neither = bf16 (k, vt,
+    score_bound as attention_fwd), v_scale = pv8 (vt = vt8, byte stride, as attention_fwd_pv8), k_scale too = qk8 (k = segment 0's
+    k8 [Bkv, H, Lp, 128], byte stride, as attention_fwd_qk8).  The last segment lies n_seg - 1 segment strides in, laid out as a
+    tensor of last_seg_len keys of its own (v_transpose / v_transpose_fp8 / k_pack_fp8 of those keys alone).  workspace: from
+    attention_ragged_workspace()."""
+    assert q.dim() == 3 and out.dim() == 3 and q.shape == out.shape and q.shape[2] == H * hd, (q.shape, out.shape, H, hd)
+    assert q.dtype == torch.bfloat16 and out.dtype == torch.bfloat16 and q.stride(2) == 1 and out.stride(2) == 1, (q.dtype, out.dtype)
+    assert n_seg >= 2 and 1 <= last_seg_len <= seg_len, (n_seg, seg_len, last_seg_len)
+    assert q.stride(0) % 8 == 0 and q.stride(1) % 8 == 0 and q.data_ptr() % 16 == 0, (q.stride(), q.data_ptr() % 16)
+    assert out.stride(0) % 8 == 0 and out.stride(1) % 8 == 0 and out.data_ptr() % 16 == 0, (out.stride(), out.data_ptr() % 16)
+    B, Lq, _ = q.shape
+    Bkv = kv_batches or B
+    mode = 0 if v_scale is None else (1 if k_scale is None else 2)
+    assert k_scale is None or v_scale is not None, "qk8 operands come with both scale vectors"
+    for s_ in (k_scale, v_scale):
+        assert s_ is None or (s_.dtype == torch.float32 and s_.is_contiguous() and s_.numel() == Bkv * H), "scales: f32 [Bkv, H]"
+    if mode == 2:
+        assert hd == 128 and k.dtype == torch.uint8 and k.dim() == 4 and k.stride(3) == 1 and k.stride(2) == 128, (hd, k.dtype, k.stride())
+        assert tuple(k.shape) == k8_shape(Bkv, H, seg_len, hd) and k.stride(1) == k.shape[2] * 128, (k.shape, k.stride())
+        assert k.data_ptr() % 16 == 0 and k.stride(0) % 16 == 0 and k_seg_stride % 16 == 0, (k.stride(), k_seg_stride)
+        kbs, krs = k.stride(0), 128
+    else:
+        assert k.dtype == torch.bfloat16 and k.dim() == 3 and k.stride(2) == 1 and k.shape[2] == H * hd, (k.dtype, k.shape, k.stride())
+        assert k.stride(0) % 8 == 0 and k.stride(1) % 8 == 0 and k_seg_stride % 8 == 0 and k.data_ptr() % 16 == 0, (k.stride(), k_seg_stride)
+        kbs, krs = k.stride(0), k.stride(1)
+    assert vt.dtype == (torch.bfloat16 if mode == 0 else torch.uint8) and vt.data_ptr() % 16 == 0, (vt.dtype, vt.data_ptr() % 16)
+    assert vt_seg_stride % (8 if mode == 0 else 16) == 0, vt_seg_stride
+    if lse is not None:
+        assert lse.dtype == torch.float32 and lse.is_contiguous() and tuple(lse.shape) == (B, H, Lq), (lse.dtype, lse.shape)
+    assert workspace is not None and workspace.dtype == torch.uint8 and workspace.data_ptr() % 16 == 0
+    if CHECK_SCORE_BOUND and mode == 0 and score_bound > 0 and not torch.cuda.is_current_stream_capturing():
+        _assert_score_bound(q, k, H, hd, scale, n_seg - 1, seg_len, k_seg_stride, q_prescaled, kv_batches, score_bound)
+        k_last = torch.as_strided(k, (Bkv, last_seg_len, H * hd), k.stride(), k.storage_offset() + (n_seg - 1) * k_seg_stride)
+        _assert_score_bound(q, k_last, H, hd, scale, 1, last_seg_len, 0, q_prescaled, kv_batches, score_bound)   # launch B's keys
+    with _attn_prof():
+        _check(lib.osk_attention_fwd_ragged_bf16(q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k_seg_stride, kbs, krs, _p(k_scale),
+                                                 vt.data_ptr(), vt_seg_stride, _p(v_scale), out.data_ptr(), out.stride(0), out.stride(1),
+                                                 _p(lse), B, H, Lq, n_seg, seg_len, last_seg_len, hd, scale, int(q_prescaled), kv_batches,
+                                                 float(score_bound), mode, workspace.data_ptr(), workspace.numel(), _stream()),
+               "osk_attention_fwd_ragged_bf16")
+    return out
+
+
+def attention_merge_into(out: torch.Tensor, lse: torch.Tensor, o_b: torch.Tensor, lse_b: torch.Tensor, H: int, hd: int) -> torch.Tensor:
+    """fold a second attention result over other keys into (out, lse) in place (osk_attention_merge_into_bf16): out bf16 [B, Lq, H*hd]
+    view, lse f32 [B, H, Lq]; o_b f32 [B, H, Lqp, hd] and lse_b f32 [B, H, Lqp] contiguous, Lqp = Lq rounded up to 256."""
+    assert out.dim() == 3 and out.dtype == torch.bfloat16 and out.shape[2] == H * hd and out.stride(2) == 1, (out.shape, out.dtype, out.stride())
+    B, Lq, _ = out.shape
+    Lqp = (Lq + 255) // 256 * 256
+    assert out.stride(0) % 8 == 0 and out.stride(1) % 8 == 0 and out.data_ptr() % 16 == 0, (out.stride(), out.data_ptr() % 16)
+    assert lse.dtype == torch.float32 and lse.is_contiguous() and tuple(lse.shape) == (B, H, Lq), (lse.dtype, lse.shape)
+    assert o_b.dtype == torch.float32 and o_b.is_contiguous() and tuple(o_b.shape) == (B, H, Lqp, hd) and o_b.data_ptr() % 16 == 0, (o_b.dtype, o_b.shape)
+    assert lse_b.dtype == torch.float32 and lse_b.is_contiguous() and tuple(lse_b.shape) == (B, H, Lqp), (lse_b.dtype, lse_b.shape)
+    _check(lib.osk_attention_merge_into_bf16(out.data_ptr(), out.stride(0), out.stride(1), lse.data_ptr(), o_b.data_ptr(), lse_b.data_ptr(),
+                                             B, H, Lq, hd, _stream()), "osk_attention_merge_into_bf16")
     return out
 
 

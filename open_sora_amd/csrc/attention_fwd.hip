@@ -202,6 +202,20 @@ static int then_merge(int rc, const AttnParams& p, int hd, hipStream_t st) {
   return rc != 0 || p.tail_split == 1 ? rc : osk_attn::launch_merge(p, hd, st);
 }
 
+// The kernel family of a filled parameter block (OSK_ATTN_* of include/osk.h): bf16 operands (p.bound set), e4m3 V^T, e4m3 K and V^T
+static int run_mode(const AttnParams& p, int hd, int mode, hipStream_t st) {
+  if (mode == OSK_ATTN_BF16) return run(p, hd, st);
+  if (mode == OSK_ATTN_QK8) return osk_attn::launch_asm128q8(p, st);
+  return hd == 128 ? osk_attn::launch_asm128p8(p, st) : osk_attn::launch_asm72p8(p, st);
+}
+
+// One call of an entry point on a filled parameter block: launch shape, kernel, merge of the split tail units
+static int dispatch(AttnParams& p, int hd, int mode, void* workspace, int64_t workspace_bytes, hipStream_t st) {
+  if (mode == OSK_ATTN_BF16) launch_shape(p, hd, workspace, workspace_bytes);
+  else osk_attn::split_tail(p, osk_attn::attn_units(p), hd, workspace, workspace_bytes);
+  return then_merge(run_mode(p, hd, mode, st), p, hd, st);
+}
+
 extern "C" int osk_attention_fwd_bounded_bf16(const void* q, int64_t q_batch_stride, int64_t q_row_stride,
                                          const void* k, int64_t k_seg_stride, int64_t k_batch_stride,
                                          int64_t k_row_stride, const void* vt, int64_t vt_seg_stride,
@@ -216,9 +230,7 @@ extern "C" int osk_attention_fwd_bounded_bf16(const void* q, int64_t q_batch_str
                              kv_batches, workspace, workspace_bytes);
   if (rc != OSK_OK) return rc;
   p.bound = bound_to_bf16_up(score_bound);
-  launch_shape(p, hd, workspace, workspace_bytes);
-  hipStream_t st = (hipStream_t)stream;
-  return then_merge(run(p, hd, st), p, hd, st);
+  return dispatch(p, hd, OSK_ATTN_BF16, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // ---- auto-dispatched pair (round 6): the bound comes from the operands themselves, per (batch, head), on the device
@@ -580,10 +592,7 @@ extern "C" int osk_attention_fwd_pv8_bf16(const void* q, int64_t q_batch_stride,
                        kv_batches, workspace, workspace_bytes);
   if (rc != OSK_OK) return rc;
   p.vt = nullptr; p.vt8 = (const unsigned char*)vt8; p.v_scale = v_scale;
-  osk_attn::split_tail(p, osk_attn::attn_units(p), hd, workspace, workspace_bytes);
-  hipStream_t st = (hipStream_t)stream;
-  rc = hd == 128 ? osk_attn::launch_asm128p8(p, st) : osk_attn::launch_asm72p8(p, st);
-  return then_merge(rc, p, hd, st);
+  return dispatch(p, hd, OSK_ATTN_PV8, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // =============================================================================================
@@ -663,7 +672,84 @@ extern "C" int osk_attention_fwd_qk8_bf16(const void* q, int64_t q_batch_stride,
   if (k8_row_stride != 128) return OSK_EUNSUPPORTED;   // the packed layout: rows of 128 bytes, heads seg_lp rows apart
   p.k = nullptr; p.k8 = (const unsigned char*)k8; p.k_scale = k_scale;
   p.vt = nullptr; p.vt8 = (const unsigned char*)vt8; p.v_scale = v_scale;
-  osk_attn::split_tail(p, osk_attn::attn_units(p), hd, workspace, workspace_bytes);
+  return dispatch(p, hd, OSK_ATTN_QK8, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// =============================================================================================
+// Ragged last key segment (sequence parallelism over a token count the rank count does not divide): two launches + one merge
+// =============================================================================================
+// The kernels bake ONE ragged-tile mask per launch (seg_len is uniform), so the n_seg - 1 full segments and the shorter last one
+// are two launches of the normal selector; the second writes f32 partials (the split-tail epilogue, every unit, one part) that
+// attn_merge_into_kernel folds into the first launch's rows in place.
+static int64_t ragged_partial_bytes(int B, int H, int Lq, int hd) {
+  return ((int64_t)((Lq + 255) / 256) * B * H * 256 * (hd + 1) * 4 + 15) & ~(int64_t)15;
+}
+static int64_t ragged_lse_bytes(int B, int H, int Lq) { return ((int64_t)B * H * Lq * 4 + 15) & ~(int64_t)15; }
+
+extern "C" int64_t osk_attention_ragged_workspace_bytes(int B, int H, int Lq, int hd) {
+  if (B <= 0 || H <= 0 || Lq <= 0 || hd <= 0) return 0;
+  return ragged_partial_bytes(B, H, Lq, hd) + ragged_lse_bytes(B, H, Lq) + osk_attention_workspace_bytes();
+}
+
+extern "C" int osk_attention_fwd_ragged_bf16(const void* q, int64_t q_batch_stride, int64_t q_row_stride,
+                                             const void* k, int64_t k_seg_stride, int64_t k_batch_stride, int64_t k_row_stride,
+                                             const float* k_scale, const void* vt, int64_t vt_seg_stride, const float* v_scale,
+                                             void* out, int64_t o_batch_stride, int64_t o_row_stride, float* lse,
+                                             int B, int H, int Lq, int n_seg, int seg_len, int last_seg_len, int hd,
+                                             float scale, int q_prescaled, int kv_batches, float score_bound, int mode,
+                                             void* workspace, int64_t workspace_bytes, void* stream) {
+  if (mode != OSK_ATTN_BF16 && mode != OSK_ATTN_PV8 && mode != OSK_ATTN_QK8) return OSK_EINVAL;
+  if (!(score_bound >= 0.f) || n_seg < 2 || last_seg_len < 1 || last_seg_len > seg_len) return OSK_EINVAL;
+  if (mode != OSK_ATTN_BF16 && (!v_scale || ((uintptr_t)v_scale & 3))) return OSK_EINVAL;
+  if (mode == OSK_ATTN_QK8 && (!k_scale || ((uintptr_t)k_scale & 3) || (k_seg_stride & 15) || (k_batch_stride & 15) || k_seg_stride < 0 ||
+                               k_batch_stride < 0))
+    return OSK_EINVAL;
+  // the merge reads and writes `out` in 16-byte pieces; the partials are not optional, so neither is the workspace
+  if (((uintptr_t)out & 15) || (o_batch_stride & 7) || (o_row_stride & 7) || !workspace) return OSK_EINVAL;
+  // (with the other OSK_EINVAL checks, in front of attn_params' head-dim OSK_EUNSUPPORTED: a malformed call is reported as malformed)
+  if (B > 0 && H > 0 && Lq > 0 && hd > 0 && workspace_bytes < ragged_partial_bytes(B, H, Lq, hd) + (lse ? 0 : ragged_lse_bytes(B, H, Lq)))
+    return OSK_EINVAL;
+  AttnParams a;
+  int rc = mode == OSK_ATTN_BF16
+               ? attn_params(a, q, q_batch_stride, q_row_stride, k, k_seg_stride, k_batch_stride, k_row_stride, vt, vt_seg_stride, 7, out,
+                             o_batch_stride, o_row_stride, lse, B, H, Lq, n_seg - 1, seg_len, hd, {64, 72, 128}, scale, q_prescaled,
+                             kv_batches, workspace, workspace_bytes)
+               : attn_params(a, q, q_batch_stride, q_row_stride, k, k_seg_stride, k_batch_stride, k_row_stride, vt, vt_seg_stride, 15, out,
+                             o_batch_stride, o_row_stride, lse, B, H, Lq, n_seg - 1, seg_len, hd,
+                             mode == OSK_ATTN_QK8 ? std::initializer_list<int>{128} : std::initializer_list<int>{72, 128}, scale,
+                             q_prescaled, kv_batches, workspace, workspace_bytes);
+  if (rc != OSK_OK) return rc;
+  if (mode == OSK_ATTN_QK8 && k_row_stride != 128) return OSK_EUNSUPPORTED;
+  const int64_t part_bytes = ragged_partial_bytes(B, H, Lq, hd), lse_bytes = lse ? 0 : ragged_lse_bytes(B, H, Lq);
+  // workspace: [f32 partials of launch B | lse of launch A when the caller keeps none | the rest: launch A's own tail split]
+  char* wsb = (char*)workspace;
+  if (!lse) a.lse = (float*)(wsb + part_bytes);
+  void* ws_a = wsb + part_bytes + lse_bytes;
+  const int64_t ws_a_bytes = workspace_bytes - part_bytes - lse_bytes;
+  if (mode == OSK_ATTN_BF16) {
+    a.bound = bound_to_bf16_up(score_bound);
+  } else {
+    a.vt = nullptr; a.vt8 = (const unsigned char*)vt; a.v_scale = v_scale;
+    if (mode == OSK_ATTN_QK8) { a.k = nullptr; a.k8 = (const unsigned char*)k; a.k_scale = k_scale; }
+  }
+  // launch B: the last segment alone, laid out as a tensor of last_seg_len keys of its own (V^T rows of round_up(last_seg_len, 64)
+  // positions; e4m3 K [Bkv, H, that many rows, 128]) n_seg - 1 segment strides in; same queries, scales, bound
+  AttnParams b = a;
+  set_segments(b, 1, last_seg_len);
+  const int64_t skip = n_seg - 1;
+  if (b.k) b.k += skip * a.kss;
+  if (b.k8) { b.k8 += skip * a.kss; b.kbs = (int64_t)H * b.seg_lp * 128; }
+  if (b.vt) b.vt += skip * a.vtss;
+  if (b.vt8) b.vt8 += skip * a.vtss;
+  b.rows = 256;
+  b.tail_first = 0; b.tail_split = 1;          // every unit: f32 partial O + log2-domain lse of its whole key range
+  b.ws_o = (float*)workspace;
+  b.ws_lse = b.ws_o + (int64_t)osk_attn::attn_units(b) * 256 * hd;
   hipStream_t st = (hipStream_t)stream;
-  return then_merge(osk_attn::launch_asm128q8(p, st), p, hd, st);
+  rc = dispatch(a, hd, mode, ws_a_bytes > 0 ? ws_a : nullptr, ws_a_bytes, st);
+  if (rc != 0) return rc;
+  rc = run_mode(b, hd, mode, st);
+  if (rc != 0) return rc;
+  b.out = a.out; b.lse = a.lse;
+  return osk_attn::launch_merge_into(b, hd, 0.6931471805599453f, st);
 }

@@ -28,6 +28,10 @@ struct AttnParams {
   // tail split (hand-scheduled kernels only; see split_tail()): the workgroups of the last, partial round of the grid
   // -- work units >= tail_first in launch order -- are cut into tail_split parts along the key axis; a part writes its
   // normalised partial O (f32) and its log2-domain LSE into the workspace and attn_merge_kernel combines them
+  // INVARIANT: tail_first ALONE decides which epilogue a unit runs (block_to_work_split: unit >= tail_first writes f32 partials);
+  // tail_split only says how many key parts such a unit has (attn_grid, key_part).  Every launch without partial results keeps
+  // tail_first = 0x7fffffff -- split_tail() and the general twin of an auto-dispatched pair reset it -- and tail_first = 0 with
+  // tail_split = 1 is the last-segment launch of osk_attention_fwd_ragged_bf16: every unit, one part, its whole key range.
   int tail_first = 0x7fffffff, tail_split = 1;
   float* ws_o = nullptr;
   float* ws_lse = nullptr;
@@ -102,7 +106,9 @@ OSK_DEV bool block_to_work_split(const AttnParams& p, int nqb, int& bh, int& qb,
   int unit = blockIdx.x;
   part = 0;
   tail_unit = 0;
-  const bool tail = p.tail_split > 1 && unit >= p.tail_first;
+  // (tail_first is 0x7fffffff in every launch without partial results; tail_split == 1 with tail_first == 0 is the last-segment launch of
+  //  osk_attention_fwd_ragged_bf16: every unit writes its f32 partial over its whole key range)
+  const bool tail = unit >= p.tail_first;
   if (tail) {
     const int j = unit - p.tail_first;
     tail_unit = j / p.tail_split;
@@ -149,6 +155,11 @@ static inline int attn_grid(const AttnParams& p) {
 // host: decide the tail split of a launch of `units` work units given the workspace (attention_fwd.hip)
 void split_tail(AttnParams& p, int units, int hd, void* workspace, int64_t workspace_bytes);
 int launch_merge(const AttnParams& p, int hd, hipStream_t st);
+// attention_merge.hip: fold the f32 partials (p.ws_o, p.ws_lse x lse_b_mult = natural log) of a launch whose every unit wrote one
+// (tail_first == 0, tail_split == 1) into the finished rows p.out / p.lse of another launch over other keys, in place.
+// unit_order: p.map's (the launch order of the attention kernels), or OSK_ATTN_ORDER_PLAIN = unit (b * H + h) * nqb + qb
+#define OSK_ATTN_ORDER_PLAIN 2
+int launch_merge_into(const AttnParams& p, int hd, float lse_b_mult, hipStream_t st);
 
 // attention_asm72.hip: head_dim 72, 4 waves x 64 query rows, hand-scheduled (generated) main loop
 int launch_asm72(const AttnParams& p, hipStream_t st);

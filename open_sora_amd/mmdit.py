@@ -1020,9 +1020,12 @@ class MMDiTModel(_OskState, nn.Module):
         return self
 
     # ------------------------------------------------------------------ planning
-    def attention_report(self, n_seg: int = 1, seg_len: int = 0) -> dict:
+    def attention_report(self, n_seg: int = 1, seg_len: int = 0, last_seg_len: int = 0) -> dict:
         """Which attention loop body the blocks' plans select, and from which score bounds (the choice is data-dependent:
-        _score_bound() reads the QK-norm scale vectors).  Blocks without a plan yet (no forward so far) are planned here."""
+        _score_bound() reads the QK-norm scale vectors).  Blocks without a plan yet (no forward so far) are planned here.
+        last_seg_len (0 or seg_len: an equal split): the rows of the last sequence-parallel rank where the rank count does not divide
+        the sequence (seqpar.SeqPar.split) -- the report then carries a "ragged" entry: the bodies of the two launches, the
+        launches of the attention entry (two + the merge) and of the extra layout calls per block, and kv_chunks = 1 (a ragged split keeps the single gather)."""
         hd = self.hidden_size // self.num_heads
         plans = [plan_double(b) for b in self.double_blocks] + [plan_single(b) for b in self.single_blocks]
         bounds = [float(p.score_bound) for p in plans]
@@ -1034,7 +1037,18 @@ class MMDiTModel(_OskState, nn.Module):
         chunks = 1
         if sp is not None and hasattr(sp, "kv_chunks_applied"):
             chunks = sp.kv_chunks_applied(self.num_heads, any(p.pv8 for p in plans), seg_len if n_seg > 1 else 0)
-        return {"kv_chunks": chunks, "score_bound_min": min(bounds), "score_bound_max": max(bounds), "bound_limit": SCORE_BOUND_LIMIT, "bodies": bodies,
+        ragged = {}
+        if n_seg > 1 and 0 < last_seg_len < seg_len:
+            # osk_attention_fwd_ragged_bf16: launch A over the n_seg - 1 full segments, launch B over the last alone, one in-place merge
+            body = lambda n, l: sorted({_OPS.attention_body(hd, n, l, b) for b in bounds}) if hasattr(_OPS, "attention_body") else []
+            # extra_prep_launches: head-exchange mode lays the last segment out by calls of its own -- one more V^T transpose, with qk8
+            # one more K pack as well; all-gather mode writes each rank's slot once either way
+            heads = sp is not None and sp.head_parallel(self.num_heads)
+            prep = (1 + int(any(p.qk8 for p in plans))) if heads else 0
+            ragged = {"ragged": {"last_seg_len": last_seg_len, "attention_entry_launches": 3, "extra_prep_launches": prep, "bodies_full_segments": body(n_seg - 1, seg_len),
+                                 "bodies_last_segment": body(1, last_seg_len), "kv_chunks_requested": getattr(sp, "kv_chunks", 1)}}
+            chunks = 1
+        return {**ragged, "kv_chunks": chunks, "score_bound_min": min(bounds), "score_bound_max": max(bounds), "bound_limit": SCORE_BOUND_LIMIT, "bodies": bodies,
                 "blocks_on_fast_body": sum(1 for b in bounds if 0.0 < b <= SCORE_BOUND_LIMIT), "blocks": len(bounds),
                 # blocks whose weight-derived bound is too large: FAST / general chosen per (batch, head) on the device from the operands
                 "blocks_auto_dispatched": auto}

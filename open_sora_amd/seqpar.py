@@ -39,6 +39,12 @@ lands directly in the layout the return all-to-all sends — no re-layout pass o
 Equal chunks keep every collective a plain `all_gather_into_tensor` / `all_to_all_single`; the final prediction is gathered as
 [P, B, L/P, C] (rank 0 also projects its text rows, which are dropped after the gather) instead of the
 reference's var-len gather (:39-112).
+
+Token counts P does not divide (the reference asserts them away, :604-608): ranks 0 .. P-2 own Lc = ceil(L / P) rows, the last rank the
+Ltail = L - (P - 1) Lc that remain (SeqPar.split).  Every buffer above keeps P slots of Lc rows -- zero-filled once, the last rank writes
+only its Ltail rows -- so the collectives do not change; token-wise work runs on the true row count; attention sees P - 1 key segments of
+Lc keys and one of Ltail, which the kernels take as two launches and an in-place merge (osk_attention_fwd_ragged_bf16, bf16 / pv8 / qk8);
+the gathered prediction [P, B, Lc, C] is cut to L rows.  P | L never takes that path.  kv_chunks is ignored on a ragged split.
 """
 from __future__ import annotations
 
@@ -125,6 +131,7 @@ class SeqPar:
         self.tp = transport if transport is not None else DistTransport(group)
         self.P, self.rank = self.tp.P, self.tp.rank
         self._bufs = {}
+        self.geom = None      # (Lc, Ltail) of the split shard_range() last made
         self.exposed = None   # a list while bench.py measures exposed communication (see _timed_wait)
         self.mode = mode or os.environ.get("OSK_SP_MODE", "auto")   # "allgather" | "ulysses" | "auto"
         if self.mode not in ("allgather", "ulysses", "auto"):
@@ -169,14 +176,29 @@ class SeqPar:
         """Token range [lo, hi) of the joint sequence owned by this rank, or None when sharding must be
         skipped because some rank would hold no image tokens (the reference then disables SP for the call,
         distributed.py:617-619)."""
+        self.geom = None
         if self.P == 1:
             return None
-        if L % self.P != 0:
-            raise AssertionError(f"Expected {L} % {self.P} == 0")  # distributed.py:604-608
-        Lloc = L // self.P
-        if Lloc <= L_txt:  # rank 0 would be text-only (`0 in img_splits`)
+        Lc, Ltail = self.split(L)
+        if Ltail < 1 or Lc <= L_txt:  # a rank without rows, or rank 0 text-only (`0 in img_splits`)
             return None
-        return self.rank * Lloc, (self.rank + 1) * Lloc
+        self.geom = (Lc, Ltail)
+        return self.rank * Lc, min((self.rank + 1) * Lc, L)
+
+    def split(self, L: int):
+        """(Lc, Ltail): ranks 0 .. P-2 own Lc = ceil(L / P) rows of the joint sequence, the last rank the Ltail = L - (P - 1) Lc that
+        remain (Ltail == Lc when P divides L: the reference's equal split, the only one it accepts, distributed.py:604-608).  The
+        padding sits on the last rank alone: every exchange buffer holds P slots of Lc rows, so the collectives stay equal-sized."""
+        Lc = -(-L // self.P)
+        return Lc, L - (self.P - 1) * Lc
+
+    def _geom(self, Lloc: int):
+        """(slot rows Lc, rows of the last rank) for a call on Lloc local rows: the split shard_range() last made when Lloc is this
+        rank's share of it, else the equal split of a direct call"""
+        g = self.geom
+        if g is not None and Lloc == (g[1] if self.rank == self.P - 1 else g[0]):
+            return g
+        return Lloc, Lloc
 
     # ------------------------------------------------------------------ K/V exchange
     MAX_GEOMETRIES = 4   # exchange-buffer sets kept (least recently used first out)
@@ -186,12 +208,16 @@ class SeqPar:
     def kv_chunks_for(self, Lloc: int) -> int:
         """key slices S the gather of a rank with Lloc rows is cut into: the largest S <= kv_chunks that divides Lloc -- equal
         slices keep every collective a plain all_gather_into_tensor (a prime Lloc: 1)"""
+        Lc, Ltail = self._geom(Lloc)
+        if Ltail != Lc:        # a ragged split keeps the single gather (its attention is two launches + a merge already)
+            return 1
         return max(s for s in range(1, max(1, min(self.kv_chunks, Lloc)) + 1) if Lloc % s == 0)
 
-    def kv_chunks_applied(self, H: int, pv8: bool = False, Lloc: int = 0) -> int:
+    def kv_chunks_applied(self, H: int, pv8: bool = False, Lloc: int = 0, Ltail: int = 0) -> int:
         """the S attention() runs with (reporting: MMDiTModel.attention_report): head-exchange mode needs the whole sequence of a
-        head and the fp8 handles the reduced e4m3 scale before the first key is used -- both keep the single gather"""
-        if self.head_parallel(H) or pv8:
+        head and the fp8 handles the reduced e4m3 scale before the first key is used -- both keep the single gather, and so does a
+        ragged split (Ltail: the last rank's rows, where they differ from Lloc)"""
+        if self.head_parallel(H) or pv8 or (Ltail and Ltail != Lloc):
             return 1
         return self.kv_chunks_for(Lloc) if Lloc else self.kv_chunks
 
@@ -207,33 +233,58 @@ class SeqPar:
         self._bufs[key] = b
         return b
 
-    def _buffers(self, B: int, Lloc: int, H: int, hd: int, device):
+    # Every exchange buffer holds P slots of Lloc = Lc rows.  Ltail (the last rank's rows; Lloc when P divides the sequence) is part
+    # of the cache key: with Ltail < Lloc the buffers are zero-filled at allocation and the last rank writes only its Ltail rows, so
+    # the pad rows stay zero for as long as the set lives -- which holds for ONE (Lc, Ltail) geometry only.
+    def _buffers(self, B: int, Lloc: int, H: int, hd: int, device, Ltail: int | None = None):
+        Ltail = Lloc if Ltail is None else Ltail
+
         def make():
             Lp = (Lloc + 63) // 64 * 64
-            return (torch.empty(self.P, B, Lloc, H * hd, dtype=BF16, device=device),
+            return ((torch.zeros if Ltail != Lloc else torch.empty)(self.P, B, Lloc, H * hd, dtype=BF16, device=device),
                     torch.zeros(self.P, B, H, hd, Lp, dtype=BF16, device=device))
 
-        return self._cached((B, Lloc, H, hd, str(device), mmdit._stream_key(device)), make)
+        return self._cached((B, Lloc, Ltail, H, hd, str(device), mmdit._stream_key(device)), make)
 
-    def _buffers8(self, B: int, Lloc: int, H: int, hd: int, device):
+    def _buffers8(self, B: int, Lloc: int, H: int, hd: int, device, Ltail: int | None = None):
+        Ltail = Lloc if Ltail is None else Ltail
+
         def make():
             Lp = (Lloc + 63) // 64 * 64
-            return (torch.empty(self.P, B, Lloc, H * hd, dtype=BF16, device=device),
+            return ((torch.zeros if Ltail != Lloc else torch.empty)(self.P, B, Lloc, H * hd, dtype=BF16, device=device),
                     torch.zeros(self.P, B, H, mmdit.ops().vt8_rows(hd), Lp, dtype=torch.uint8, device=device))
 
-        return self._cached(("pv8", B, Lloc, H, hd, str(device), mmdit._stream_key(device)), make)
+        return self._cached(("pv8", B, Lloc, Ltail, H, hd, str(device), mmdit._stream_key(device)), make)
 
-    def _buffers_qk8(self, B: int, Lloc: int, H: int, hd: int, device):
+    def _buffers_qk8(self, B: int, Lloc: int, H: int, hd: int, device, Ltail: int | None = None):
         """qk8 (head_dim 128): K travels packed as e4m3 too -- [P, B, H, Lp, 128] bytes, no bf16 K buffer -- plus the [2, B, H]
         scale buffer (K's scales, then V's) that the one reducing collective of the block works on"""
+        Ltail = Lloc if Ltail is None else Ltail
+
         def make():
             ops = mmdit.ops()
             Lp = (Lloc + 63) // 64 * 64
-            return (torch.empty(self.P, *ops.k8_shape(B, H, Lloc, hd), dtype=torch.uint8, device=device),
+            return ((torch.zeros if Ltail != Lloc else torch.empty)(self.P, *ops.k8_shape(B, H, Lloc, hd), dtype=torch.uint8, device=device),
                     torch.zeros(self.P, B, H, ops.vt8_rows(hd), Lp, dtype=torch.uint8, device=device),
                     torch.empty(2, B, H, dtype=torch.float32, device=device))
 
-        return self._cached(("qk8", B, Lloc, H, hd, str(device), mmdit._stream_key(device)), make)
+        return self._cached(("qk8", B, Lloc, Ltail, H, hd, str(device), mmdit._stream_key(device)), make)
+
+    @staticmethod
+    def _own_layout(slot: Tensor, rows: int, key_axis: int = 3) -> Tensor:
+        """a slot [B, H, R, Lp(Lc)] (V^T; key_axis 3) or [B, H, Lp(Lc), 128] (e4m3 K; key_axis 2) of the gathered buffers as the
+        tensor the transposing / packing kernels write for `rows` keys: the same memory, round_up(rows, 64) key positions.  The slot
+        itself unless the last rank's shorter chunk ends in an earlier 64-key tile (osk_attention_fwd_ragged_bf16 reads the last
+        segment in this layout)."""
+        Lp = (rows + 63) // 64 * 64
+        if slot.shape[key_axis] == Lp:
+            return slot
+        shape = list(slot.shape)
+        shape[key_axis] = Lp
+        n = 1
+        for d in shape:
+            n *= d
+        return slot.reshape(-1)[:n].view(shape)
 
     def _buffers_chunked(self, B: int, Lloc: int, S: int, H: int, hd: int, device):
         """kv_chunks: the gather buffers cut into S key slices of Lc = Lloc / S rows -- K [S, P, B, Lc, D], V^T
@@ -255,7 +306,57 @@ class SeqPar:
         skips the osk_v_transpose_bf16 pass.  None with kv_chunks too: the V^T task writes ONE contiguous slot, the slices are S."""
         if self.head_parallel(H) or self.kv_chunks_for(Lloc) > 1:
             return None
+        Lc, Ltail = self._geom(Lloc)
+        if Ltail != Lc:   # ragged split: the slot in the layout of THIS rank's rows (columns past them stay zero: written by nobody)
+            return self._own_layout(self._buffers(B, Lc, H, hd, device, Ltail)[1][self.rank], Lloc)
         return self._buffers(B, Lloc, H, hd, device)[1][self.rank]
+
+    def _ragged_kv_start(self, k: Tensor, v: Tensor, H: int, hd: int, pv8: bool, vt_ready: bool, qk8: bool, Lc: int, Ltail: int):
+        """gather_kv_start (all-gather mode) on a ragged split: the same exchanges over slots of Lc rows.  This rank writes its
+        Lloc <= Lc rows; the last rank's slot keeps the layout of a tensor of Ltail keys (_own_layout) in front of its zero padding.
+        One gather whatever kv_chunks says.  The handle carries Ltail for attention()."""
+        ops = mmdit.ops()
+        B, Lloc, _ = k.shape
+        r = self.rank
+        if qk8:
+            k8_all, vt8_all, s2 = self._buffers_qk8(B, Lc, H, hd, k.device, Ltail)
+            ops.kv_scale_fp8(k, v, H, hd, out=s2)
+            self._timed_wait(self.tp.all_reduce_max(s2), "kvmax")
+            ops.k_pack_fp8(k, s2[0], self._own_layout(k8_all[r], Lloc, 2), H, hd)
+            wk = self.tp.all_gather(k8_all.view(-1), k8_all[r].view(-1))
+            ops.v_transpose_fp8(v, s2[1], self._own_layout(vt8_all[r], Lloc), H, hd)
+            wv = self.tp.all_gather(vt8_all.view(-1), vt8_all[r].view(-1))
+            return "ragged", "qk8", (Lc, Ltail), k8_all, vt8_all, s2[0], s2[1], wk, wv
+        if pv8:
+            sv = mmdit.v_scale_fp8(v, H, hd)
+            wmax = self.tp.all_reduce_max(sv)
+            k_all, vt8_all = self._buffers8(B, Lc, H, hd, k.device, Ltail)
+            ops.copy_rows(k, k_all[r][:, :Lloc])
+            wk = self.tp.all_gather(k_all.view(-1), k_all[r].view(-1))
+            self._timed_wait(wmax, "vmax")
+            ops.v_transpose_fp8(v, sv, self._own_layout(vt8_all[r], Lloc), H, hd)
+            wv = self.tp.all_gather(vt8_all.view(-1), vt8_all[r].view(-1))
+            return "ragged", "pv8", (Lc, Ltail), k_all, vt8_all, None, sv, wk, wv
+        k_all, vt_all = self._buffers(B, Lc, H, hd, k.device, Ltail)
+        ops.copy_rows(k, k_all[r][:, :Lloc])
+        if not vt_ready:
+            ops.v_transpose(v, self._own_layout(vt_all[r], Lloc), H, hd)
+        wk = self.tp.all_gather(k_all.view(-1), k_all[r].view(-1))
+        wv = self.tp.all_gather(vt_all.view(-1), vt_all[r].view(-1))
+        return "ragged", "bf16", (Lc, Ltail), k_all, vt_all, None, None, wk, wv
+
+    def _ragged_attention(self, pending, q: Tensor, out: Tensor, H: int, hd: int, score_bound: float):
+        """P - 1 key segments of Lc keys and a last one of Ltail: osk_attention_fwd_ragged_bf16 -- one launch over the full
+        segments, one over the last, one in-place merge; the divisible case never comes here"""
+        _, kind, (Lc, Ltail), k_all, vt_all, k_scale, v_scale, wk, wv = pending
+        self._timed_wait(wk, "k")
+        self._timed_wait(wv, "v")
+        ops = mmdit.ops()
+        B, Lloc, _ = q.shape
+        ops.attention_fwd_ragged(q, k_all[0], vt_all, out, H, hd, hd ** -0.5, n_seg=self.P, seg_len=Lc, last_seg_len=Ltail,
+                                 k_seg_stride=k_all.stride(0), vt_seg_stride=vt_all.stride(0), q_prescaled=True,
+                                 workspace=ops.attention_ragged_workspace(B, H, Lloc, hd, q.device),
+                                 score_bound=score_bound if kind == "bf16" else 0.0, k_scale=k_scale, v_scale=v_scale)
 
     def gather_kv_start(self, ws, k: Tensor, v: Tensor, H: int, hd: int, pv8: bool = False, vt_ready: bool = False,
                         qk8: bool = False):
@@ -271,6 +372,9 @@ class SeqPar:
         if self.head_parallel(H):
             return self._heads_kv_start(k, v, H, hd, pv8, qk8)
         B, Lloc, _ = k.shape
+        Lc, Ltail = self._geom(Lloc)
+        if Ltail != Lc:
+            return self._ragged_kv_start(k, v, H, hd, pv8, vt_ready, qk8, Lc, Ltail)
         if qk8:
             ops = mmdit.ops()
             k8_all, vt8_all, s2 = self._buffers_qk8(B, Lloc, H, hd, k.device)
@@ -327,6 +431,8 @@ class SeqPar:
         FAST body takes segmented / ragged key layouts since round 4, so sequence-parallel calls run it too."""
         if isinstance(pending[0], str) and pending[0] == "heads":
             return self._heads_attention(pending, q, out, H, hd, score_bound)
+        if isinstance(pending[0], str) and pending[0] == "ragged":
+            return self._ragged_attention(pending, q, out, H, hd, score_bound)
         B, Lloc, D = q.shape
         ops = mmdit.ops()
         if isinstance(pending[0], str) and pending[0] == "qk8":
@@ -367,38 +473,47 @@ class SeqPar:
                           workspace=ops.attention_workspace(q.device), score_bound=score_bound)
 
     # ------------------------------------------------------------------ head-parallel exchange (all-to-all)
-    def _heads_buffers(self, B: int, Lloc: int, H: int, hd: int, device):
+    def _heads_buffers(self, B: int, Lloc: int, H: int, hd: int, device, Ltail: int | None = None):
+        """send / receive chunks of Lloc = Lc rows.  Ragged split (Ltail < Lloc): zero-filled, and the last rank only ever writes its
+        Ltail rows of a send chunk, so every received chunk of the last source rank ends in zero rows (finite scores and outputs)"""
+        Ltail = Lloc if Ltail is None else Ltail
+
         def make():
             Hg, Lp = H // self.P, (Lloc + 63) // 64 * 64
-            mk = lambda: torch.empty(self.P, B, Lloc, Hg * hd, dtype=BF16, device=device)
-            b = dict(ks=mk(), kr=mk(), vs=mk(), vr=mk(), qs=mk(), qr=mk(), os=mk(), orr=mk(),
+            mk = lambda: (torch.zeros if Ltail != Lloc else torch.empty)(self.P, B, Lloc, Hg * hd, dtype=BF16, device=device)
+            b = dict(ks=mk(), kr=mk(), vs=mk(), vr=mk(), qs=mk(), qr=mk(), os=mk(), orr=mk(), geom=(Lloc, Ltail),
                      vt=torch.zeros(self.P, B, Hg, hd, Lp, dtype=BF16, device=device))
             if hd in (72, 128):   # fp8 mode: e4m3 V^T of the received chunks
                 b["vt8"] = torch.zeros(self.P, B, Hg, mmdit.ops().vt8_rows(hd), Lp, dtype=torch.uint8, device=device)
             return b
 
-        return self._cached(("heads", B, Lloc, H, hd, str(device), mmdit._stream_key(device)), make)
+        return self._cached(("heads", B, Lloc, Ltail, H, hd, str(device), mmdit._stream_key(device)), make)
 
     def _to_head_chunks(self, dst: Tensor, x: Tensor):
         """[B, L/P, H*hd] (all heads of my tokens) -> dst [P, B, L/P, (H/P)*hd]: chunk j = head group j, for rank j.
         ONE osk_copy_rows_bf16 launch (chunk j of the source = columns j Dg ..): round 4 ran a torch permute-copy here, four per block."""
         B, Lloc, D = x.shape
+        if dst.shape[2] != Lloc:      # the last rank of a ragged split: its rows lead the chunk, the rest stays zero
+            dst = dst[:, :, :Lloc]
         mmdit.ops().copy_rows(x.view(B, Lloc, self.P, D // self.P).permute(2, 0, 1, 3), dst)
 
     def _from_head_chunks(self, out: Tensor, src: Tensor):
         """the way back: src [P, B, L/P, Dg] (head group j of my tokens, from rank j) -> out [B, L/P, P x Dg], head groups side by side"""
         B, Lloc, D = out.shape
+        if src.shape[2] != Lloc:      # (the rows behind them were computed from zero queries: dropped here)
+            src = src[:, :, :Lloc]
         mmdit.ops().copy_rows(src, out.view(B, Lloc, self.P, D // self.P).permute(2, 0, 1, 3))
 
     def _heads_kv_start(self, k: Tensor, v: Tensor, H: int, hd: int, pv8: bool = False, qk8: bool = False):
         """K and V travel in bf16 whatever the fp8 mode (packing K before the all-to-all would need per-segment K scales in the
         kernel); the handle's last element says what _heads_attention does with them: False, True (pv8) or "qk8" """
         B, Lloc, _ = k.shape
-        bufs = self._heads_buffers(B, Lloc, H, hd, k.device)
+        Lc, Ltail = self._geom(Lloc)
+        bufs = self._heads_buffers(B, Lc, H, hd, k.device, Ltail)
         if qk8:
             pv8 = "qk8"
             if "k8" not in bufs:    # e4m3 K of the received chunks: only a model that asked for qk8 pays for it
-                bufs["k8"] = torch.empty(self.P, *mmdit.ops().k8_shape(B, H // self.P, Lloc, hd), dtype=torch.uint8, device=k.device)
+                bufs["k8"] = torch.empty(self.P, *mmdit.ops().k8_shape(B, H // self.P, Lc, hd), dtype=torch.uint8, device=k.device)
         self._to_head_chunks(bufs["ks"], k)
         wk = self.tp.all_to_all(bufs["kr"].view(-1), bufs["ks"].view(-1))
         self._to_head_chunks(bufs["vs"], v)
@@ -419,7 +534,10 @@ class SeqPar:
     def _heads_attention(self, pending, q: Tensor, out: Tensor, H: int, hd: int, score_bound: float = 0.0):
         pending = self.q_exchange_start(pending, q, H, hd)     # (a caller that did not start it earlier)
         _, bufs, wk, wv, pv8, wq = pending
-        B, Lloc, D = q.shape
+        B, D = q.shape[0], q.shape[2]
+        Lloc, Ltail = bufs["geom"]     # rows of a chunk (Lc), valid rows of the last source rank's
+        if Ltail != Lloc:
+            return self._heads_attention_ragged(pending, out, H, hd, score_bound)
         P, Hg = self.P, H // self.P
         self._timed_wait(wq, "q")
         self._timed_wait(wk, "k")
@@ -456,15 +574,59 @@ class SeqPar:
         self._timed_wait(self.tp.all_to_all(bufs["orr"].view(-1), bufs["os"].view(-1)), "o")
         self._from_head_chunks(out, bufs["orr"])
 
+    def _heads_attention_ragged(self, pending, out: Tensor, H: int, hd: int, score_bound: float):
+        """_heads_attention on a ragged split: P key segments of Lc rows of which the last holds Ltail, P * B query batches of Lc
+        rows.  The last segment's V^T (and e4m3 K) is written by a call of its own over its Ltail keys -- the layout
+        osk_attention_fwd_ragged_bf16 reads, and what keeps the zero pad rows out of the e4m3 validity row.  The pad queries of the
+        last source rank's batches are zero rows: their outputs are finite and the return exchange's receiver drops them."""
+        _, bufs, wk, wv, pv8, wq = pending
+        Lc, Ltail = bufs["geom"]
+        P, Hg = self.P, H // self.P
+        B = bufs["qr"].shape[1]
+        Dg = Hg * hd
+        self._timed_wait(wq, "q")
+        self._timed_wait(wk, "k")
+        self._timed_wait(wv, "v")
+        ops = mmdit.ops()
+        qr, kr, vr, os_ = bufs["qr"].view(P * B, Lc, Dg), bufs["kr"], bufs["vr"], bufs["os"].view(P * B, Lc, Dg)
+        full = lambda t: t[:P - 1].reshape((P - 1) * t.shape[1], *t.shape[2:])     # the P - 1 full segments as one batch axis (a view)
+        k_last, v_last = kr[P - 1][:, :Ltail], vr[P - 1][:, :Ltail]
+        k_op, k_scale, v_scale = kr, None, None
+        if pv8:
+            vt = bufs["vt8"]
+            if pv8 == "qk8":
+                s2 = ops.kv_scale_fp8(kr.view(P * B, Lc, Dg), vr.view(P * B, Lc, Dg), Hg, hd).view(2, P, B, Hg).amax(1).contiguous()   # [2, B, Hg]
+                k_scale, v_scale = s2[0], s2[1]
+                k_op = bufs["k8"]
+                ops.k_pack_fp8(full(kr), k_scale.repeat(P - 1, 1).contiguous(), full(k_op), Hg, hd)
+                ops.k_pack_fp8(k_last, k_scale, self._own_layout(k_op[P - 1], Ltail, 2), Hg, hd)
+            else:
+                v_scale = ops.v_scale_fp8(vr.view(P * B, Lc, Dg), Hg, hd).view(P, B, Hg).amax(0).contiguous()                         # [B, Hg]
+            ops.v_transpose_fp8(full(vr), v_scale.repeat(P - 1, 1).contiguous(), full(vt), Hg, hd)
+            ops.v_transpose_fp8(v_last, v_scale, self._own_layout(vt[P - 1], Ltail), Hg, hd)
+        else:
+            vt = bufs["vt"]
+            ops.v_transpose(full(vr), full(vt), Hg, hd)
+            ops.v_transpose(v_last, self._own_layout(vt[P - 1], Ltail), Hg, hd)
+        ops.attention_fwd_ragged(qr, k_op[0], vt, os_, Hg, hd, hd ** -0.5, n_seg=P, seg_len=Lc, last_seg_len=Ltail,
+                                 k_seg_stride=k_op.stride(0), vt_seg_stride=vt.stride(0), q_prescaled=True, kv_batches=B,
+                                 workspace=ops.attention_ragged_workspace(P * B, Hg, Lc, hd, qr.device),
+                                 score_bound=0.0 if pv8 else score_bound, k_scale=k_scale, v_scale=v_scale)
+        self._timed_wait(self.tp.all_to_all(bufs["orr"].view(-1), bufs["os"].view(-1)), "o")
+        self._from_head_chunks(out, bufs["orr"])
+
     # ------------------------------------------------------------------ output
     def gather_output(self, ws, project, C_out: int, L_txt: int) -> Tensor:
         """project(dst) writes this rank's [B, L/P, C_out] rows; returns the full image prediction
         [B, L_img, C_out] on every rank (gather_forward_split_backward_var_len, distributed.py:678-679)."""
         B, Lloc = ws.B, ws.L
-        full = torch.empty(self.P, B, Lloc, C_out, dtype=BF16, device=ws.x.device)
-        project(full[self.rank])
+        Lc, Ltail = self._geom(Lloc)
+        # (ragged split: an exchange buffer like the others -- zero-filled, the last rank writes its Ltail rows only)
+        full = (torch.zeros if Ltail != Lc else torch.empty)(self.P, B, Lc, C_out, dtype=BF16, device=ws.x.device)
+        project(full[self.rank][:, :Lloc])
         self._timed_wait(self.tp.all_gather(full.view(-1), full[self.rank].view(-1)), "out")
-        return full.permute(1, 0, 2, 3).reshape(B, self.P * Lloc, C_out)[:, L_txt:].contiguous()
+        # (ragged split: the last slot's zero rows behind Ltail end behind row L, where the cut drops them)
+        return full.permute(1, 0, 2, 3).reshape(B, self.P * Lc, C_out)[:, L_txt: (self.P - 1) * Lc + Ltail].contiguous()
 
 
 def enable(model, group=None, mode: str | None = None, transport=None, kv_chunks: int | None = None) -> SeqPar:
