@@ -37,13 +37,40 @@ FAST bodies (`generate(..., fast=True)`, attention_asm*_n2_f0.inc): the loop the
 Body t (starts right after barrier t-1): the last 2 fragment pairs' P.V MFMAs of tile t-1 | QK^T of tile t+1 |
 P.V of tile t (first 10 of 12 fragment pairs); beside them: K / V^T fragment reads (4-deep rings), LDS-DMA of
 K(t+2), V(t+1), exp2 + pack of tile t, max of tile t+1.
+What a call emits is a function of its arguments alone: generate(L, fast, knobs) / generate_wide(L, knobs).  Knobs() is the production
+schedule; every other value is an experiment that only MOVES instructions (`--set name=value`, into a scratch --out only).
 """
 import argparse
+import copy
+import dataclasses
 import os
+import re
 
 from asm_emit import ar, clobbers, header, vr, write_body
 
 THR_BITS = "0x41000000"                    # 8.0: move M when a score exceeds the reference by > 2^8
+
+
+@dataclasses.dataclass(frozen=True)
+class Knobs:
+    """every tunable of the schedules; the defaults are what is shipped"""
+    safe: bool = False         # hazard-padded debug schedule: s_nop 7 behind every MFMA of the loop bodies
+    dma_gap: int = 1           # 256-row bodies: one LDS-DMA item per dma_gap MFMA shadows ...
+    dma_cost: int = 12         # ... and the issue cycles a shadow's filler budget is charged for it
+    # filler cycles per MFMA shadow of the 256-row bodies (round 5: 24 / 9 instead of 30 / 13, as in the wide body -- the MFMA's own
+    # issue takes 4.4 cycles of its shadow): 32x32x16 bf16 shadows, 16x16x32 P.V shadows, fp8 P.V shadows, every shadow of the qk8 body
+    m32: int = 24
+    pv16: int = 9
+    pv8: int = 60
+    qk8: int = 96
+    fast_windows: tuple = ()   # ((hd, (a0, a1, b0, b1)), ...): filler windows of the 256-row FAST body (NU = 2) of head_dim hd
+    wide_gap: int = 1          # wide body: one LDS-DMA piece per wide_gap trailing P.V shadows
+    # wide body: filler cycles per 16 / 32-cycle shadow (round 5: 9 / 24 -- an MFMA's own issue takes 4.4 cycles and v_exp_f32 8.5, not
+    # 8: with round 4's 13 / 30 the shadows were over-subscribed; in-step A/B -0.8 % per launch on two boxes,
+    # profiles/r05n_attn_filler_budget_ab.jsonl)
+    wide_budget: tuple = (9, 24)
+    wide_pretrail: int = 0     # wide body: exponentials of the body's own phase-0 scores per trailing P.V shadow (0: none)
+    wide_windows: tuple = ()   # (a0, a1, b0, b1): filler windows of the wide body
 
 
 class Geometry:
@@ -161,16 +188,12 @@ def operand_names(geo, nslot_k, nslot_v):
     return names
 
 
-N2_BUDGET = {"m32": 24, "pv16": 9, "pv8": 60, "qk8": 96}   # filler cycles per MFMA shadow of the 256-row bodies (round 5: 24 / 9 instead of 30 / 13, as in
-# the wide body -- the MFMA's own issue takes 4.4 cycles of its shadow; --n2-budget: experiments)
-FAST_WINDOWS_OVERRIDE = {}   # (hd, nu) -> [a0, a1, b0, b1, c0, c1]; set by --fast-windows (experiments) or below (production)
-
-
 class Layout:
     """register file and schedule geometry for NU query blocks per wave"""
 
     def __init__(self, nu, hd=72, pv8=False, pv16=False, nom=False, qk8=False):
         self.NU = nu
+        self.FAST = False                      # the bounded body (see the header): generate(L, fast=True) works on a copy that says so
         self.G = G = Geometry(hd, pv8, pv16, nom, qk8)
         self.PV8 = pv8
         self.QK8 = qk8
@@ -229,15 +252,13 @@ class Layout:
             self.WINDOWS = [1, 26, 20, 46, 29, last]
             self.C_T2_RELEASE = 31
         elif hd == 72:
-            self.WINDOWS = [4, 25, 24, 40, 26, 43] if nu == 2 else [2, 13, 12, 19, 14, 21]
-            self.C_T2_RELEASE = 28 if nu == 2 else 15   # chains over keys 32..63: their last QK^T MFMAs come last
+            assert nu == 1, "head_dim 72 with NU = 2 runs P.V on the 16x16x32 MFMAs (pv16)"
+            self.WINDOWS = [2, 13, 12, 19, 14, 21]
+            self.C_T2_RELEASE = 15             # chains over keys 32..63: their last QK^T MFMAs come last
         else:
             self.WINDOWS = [self.I_QK0, self.I_PV0 + 1, self.I_PV0, self.I_PV0 + 3 * NDT * nu - 2, self.I_PV0 + 2, last]
             self.C_T2_RELEASE = self.I_PV0 + 2 * nu
         self.S_ONESMASK = S_HIM if G.M_HI else S_HI2   # lanes 32..63
-        # FAST bodies carry no class C: exp2 + pack paced evenly over the whole iteration (deadlines: group g before the P.V
-        # pairs of group g, which start at shadow I_PV0 + g NDT NU)
-        self.FAST_WINDOWS = FAST_WINDOWS_OVERRIDE.get((hd, nu)) or self.WINDOWS
 
     def S(self, setbase, u, t2, r=0):
         return setbase + (u * 2 + t2) * 16 + r
@@ -261,20 +282,11 @@ class Layout:
 class Stream:
     """instruction list with in-order LDS-read bookkeeping (lgkmcnt)"""
 
-    def __init__(self, ablate=frozenset()):
+    def __init__(self):
         self.lines, self.pending, self.table = [], [], []
-        self.ablate, self.in_body = ablate, False
         self.events = []   # FAST bodies: (which, uid, ring slot, V^T step) of every advance site, for fast_events()
 
     def emit(self, text, kind="x"):
-        ab = self.ablate if self.in_body else frozenset()
-        if ("noexp" in ab and text.startswith("v_exp")) or ("nobar" in ab and text.startswith("s_barrier")) or \
-           ("nodma" in ab and text.startswith("global_load_lds")) or \
-           ("nolds" in ab and (text.startswith("ds_read") or "lgkmcnt" in text)) or \
-           ("novalu" in ab and kind in ("e", "v") and not text.startswith("v_mfma") and not text.startswith("v_cmp")) or \
-           ("nomfma" in ab and text.startswith("v_mfma")) or ("norare" in ab and text.startswith("s_cbranch_vccnz")) or \
-           ("nocvt" in ab and text.startswith("v_cvt_pk")) or ("nomax" in ab and (text.startswith("v_max") or text.startswith("v_cmp"))):
-            return
         self.lines.append("  " + text)
         self.table.append((kind, text))
 
@@ -358,8 +370,6 @@ def pv_mfma(st, L, b):
         st.emit("v_mfma_f32_32x32x64_f8f6f4 %s, %s, %s, %s" % (dst, vr(L.VR0 + (r % 2) * 8, 8), vr(L.PB(u, 0), 8), dst), "F")
         return
     g, d = r // L.G.NDT, r % L.G.NDT
-    if "pv80" in st.ablate and st.in_body and L.G.HD == 72 and d == 2 and g % 2 == 1:
-        return   # timing ablation: the matrix time of an 80-row P.V product (5 x 16 rows) instead of 96 (3 x 32)
     dst = ar(L.AO(u, d), 16)
     st.emit("v_mfma_f32_32x32x16_bf16 %s, %s, %s, %s" % (dst, vr(L.VR0 + (r % 4) * 4, 4), vr(L.PB(u, g), 4), dst), "M")
 
@@ -393,35 +403,31 @@ def swap_group(L, u, t2, guard=True):
     permlane write -> MFMA operand read."""
     # guard = False (the wide body): no nops -- the order of the fillers keeps the packs >= 3 instructions in front of the swap and
     # the swap >= 3 in front of its MFMA, which _check_swap_distance() verifies on the emitted stream (in-step A/B: -1.5 .. -2.6 % per launch)
-    nop = [] if (NO_SWAP_NOPS or not guard) else [("n", "s_nop 1")]
+    nop = [("n", "s_nop 1")] if guard else []
     ops = list(nop)
     for i in range(4):
         ops.append(("v", "v_permlane16_swap_b32 %s, %s" % (vr(L.PB(u, 2 * t2, i)), vr(L.PB(u, 2 * t2 + 1, i)))))
     return ops + nop
 
 
-NO_SWAP_NOPS = False   # experiment (--wide-exp noswapnop): rely on the distance the filler order gives (checked by _check_swap_distance)
-
-
 def _check_swap_distance(st):
     """without the guard nops: >= 2 instructions between the v_cvt_pk that writes a P register and the lane-row swap that reads it,
     and between a swap and the MFMA that reads its registers"""
-    import re as _re
     last_write, last_swap = {}, {}
     n = 0
     for kind, text in st.table:
         if kind == "L":
             continue
         n += 1
-        m = _re.match(r"v_cvt_pk_\w+ v(\d+),", text)
+        m = re.match(r"v_cvt_pk_\w+ v(\d+),", text)
         if m:
             last_write[int(m.group(1))] = n
-        m = _re.match(r"v_permlane16_swap_b32 v(\d+), v(\d+)", text)
+        m = re.match(r"v_permlane16_swap_b32 v(\d+), v(\d+)", text)
         if m:
             for r in (int(m.group(1)), int(m.group(2))):
                 assert n - last_write.get(r, -99) > 2, "swap too close behind the pack of v%d" % r
                 last_swap[r] = n
-        m = _re.match(r"v_mfma_f32_16x16x32_bf16 a\[\d+:\d+\], v\[\d+:\d+\], v\[(\d+):(\d+)\]", text)
+        m = re.match(r"v_mfma_f32_16x16x32_bf16 a\[\d+:\d+\], v\[\d+:\d+\], v\[(\d+):(\d+)\]", text)
         if m:
             for r in range(int(m.group(1)), int(m.group(2)) + 1):
                 assert n - last_swap.get(r, -99) > 2, "MFMA too close behind the swap of v%d" % r
@@ -471,9 +477,6 @@ def rowmax_from_chains(st, L):
         st.emit("v_max_f32 %s, %s, %s" % (vr(L.MT[u]), vr(ta), vr(tb)))
 
 
-FAST = False   # set by generate(): the body being emitted is the bounded / single-segment / whole-tile variant
-
-
 def k_dma(st, L, slot, i, part=3):
     """K loader slot i of this wave -> ring slot `slot` (instruction j = wave + NW i).  part 1 = M0 write only,
     2 = the DMA only (one other instruction must sit between them), 3 = both with an s_nop.  On the ragged last tile
@@ -483,12 +486,12 @@ def k_dma(st, L, slot, i, part=3):
         if L.QK8:     # the packed K tensor repeats a segment's last key up to the tile boundary: one set of offsets
             if part == 3:
                 st.emit("s_nop 0", "n")
-        elif not FAST:
+        elif not L.FAST:
             st.emit("v_cndmask_b32_e64 %s, %s, %s, s[%d:%d]" % (vr(L.TX[3]), L.OP["koff%d" % i], L.OP["koffL%d" % i], S_KRG, S_KRG + 1), "v")
         elif part == 3:
             st.emit("s_nop 0", "n")
     if part & 2:   # FAST: the offsets in force (koff, or koffL while the loader sits on a ragged tile) live in KCUR registers
-        st.emit("global_load_lds_dwordx4 %s, s[%d:%d]" % (L.OP["koff%d" % i] if L.QK8 else (vr(L.KCUR + i) if FAST else vr(L.TX[3])), S_KB, S_KB + 1), "g")
+        st.emit("global_load_lds_dwordx4 %s, s[%d:%d]" % (L.OP["koff%d" % i] if L.QK8 else (vr(L.KCUR + i) if L.FAST else vr(L.TX[3])), S_KB, S_KB + 1), "g")
 
 
 def v_dma(st, L, slot, i, part=3):
@@ -517,9 +520,11 @@ def dma_last(st, L, which, slot, uid):
     st.label(lab)
 
 
-def advance(st, which, uid, vstep=128, L=None, slot=0):
-    """point the loader at its next tile; past the last tile it stays (harmless re-fetch of the last tile)"""
-    if FAST:   # branch-free, six SALU instructions, behind the event check (slow path: fast_events())
+def advance(st, L, which, uid, slot):
+    """point the loader at its next tile; past the last tile it stays (harmless re-fetch of the last tile).  `slot`: the ring slot
+    that received the tile the loader leaves (FAST: what its event code needs)"""
+    vstep = L.G.VSTEP
+    if L.FAST:   # branch-free, six SALU instructions, behind the event check (slow path: fast_events())
         sl, sb = (S_KL, S_KB) if which == "k" else (S_VL, S_VB)
         st.emit("s_cmp_eq_u32 s%d, s%d" % (sl, S_KNEXT if which == "k" else S_VNEXT), "s")
         st.emit("s_cbranch_scc1 .L@@_ev%s%s" % (which, uid), "s")
@@ -556,9 +561,9 @@ def advance(st, which, uid, vstep=128, L=None, slot=0):
     st.label(lab)
 
 
-def ragged_masks(st):
+def ragged_masks(st, L):
     """refresh both loaders' ragged-tile lane masks; skipped entirely when the launch has no ragged tile"""
-    if FAST:
+    if L.FAST:
         return
     lab = ".L@@_rg%d" % len(st.lines)
     st.emit("s_cmp_lg_u32 s%d, 0" % S_NRG, "s")
@@ -598,8 +603,8 @@ def dma_group(st, L, which, slot, uid):
     for i in range(nslot(L, which) - 1):
         (k_dma if which == "k" else v_dma)(st, L, slot, i)
     dma_last(st, L, which, slot, uid)
-    advance(st, which, uid, L.G.VSTEP, L, slot)
-    ragged_masks(st)
+    advance(st, L, which, uid, slot)
+    ragged_masks(st, L)
 
 
 def row_write(st, L, slot, mask, uid):
@@ -777,35 +782,74 @@ def fixup(st, L, sx, init):
 
 
 # ------------------------------------------------------------------------------------------ body
-DMAGAP = 1     # LDS-DMA items: one per DMAGAP MFMA shadows (set by --exp dmagapN for the experimental variant)
-DMACOST = 12   # issue cycles a shadow's filler budget is charged for an LDS-DMA item
-
-
-def _check_p_ready(st, L, k):
-    """every P.V MFMA of this body's own tile must come AFTER the v_cvt_pk instructions that write its P operand registers
-    (the filler windows are hand-set: this is what keeps an edited window honest).  The trailing MFMAs at the top of the body
-    consume the PREVIOUS tile's last fragments and are exempt."""
-    import re as _re
-    start = max(i for i, (kind, text) in enumerate(st.table) if kind == "L" and text.endswith("_entry%d" % k))
+def _check_p_ready(st, L, entry_label):
+    """every P.V MFMA of the body's own tile (wide body: half) must come AFTER the v_cvt_pk instructions that write its P operand
+    registers and, with the P.V product on 16x16x32 MFMAs, after their lane-row swap (the filler windows are hand-set: this is what
+    keeps an edited window honest).  The trailing MFMAs at the top of the body, in front of the entry label, consume the PREVIOUS
+    tile's last fragments and are exempt; the s_waitcnt that covers an MFMA's LDS operand is Stream.need's bookkeeping."""
+    start = max(i for i, (kind, text) in enumerate(st.table) if kind == "L" and text == entry_label)
     written, swapped = set(), set()
     for kind, text in st.table[start:]:
         if text.startswith("v_cvt_pk"):
-            written.add(int(_re.match(r"v_cvt_pk_\w+ v(\d+),", text).group(1)))
+            written.add(int(re.match(r"v_cvt_pk_\w+ v(\d+),", text).group(1)))
         elif text.startswith("v_permlane16_swap"):
-            a_, b_ = (int(x) for x in _re.match(r"v_permlane16_swap_b32 v(\d+), v(\d+)", text).groups())
+            a_, b_ = (int(x) for x in re.match(r"v_permlane16_swap_b32 v(\d+), v(\d+)", text).groups())
             assert {a_, b_} <= written, "lane-row swap before its registers are packed: " + text
             swapped |= {a_, b_}
-        elif text.startswith("v_mfma") and kind in ("M", "F") and ", a[" in text.split(",", 1)[0] + ",":   # accumulating into O^T (AGPRs)
-            m = _re.match(r"v_mfma_\w+ a\[\d+:\d+\], v\[\d+:\d+\], v\[(\d+):(\d+)\]", text)
+        else:
+            m = re.match(r"v_mfma_\w+ a\[\d+:\d+\], v\[\d+:\d+\], v\[(\d+):(\d+)\]", text)   # accumulating into O^T (AGPRs)
             if m:
                 need = set(range(int(m.group(1)), int(m.group(2)) + 1))
                 assert need <= written, "P.V MFMA reads P registers %s before their v_cvt_pk: %s" % (sorted(need - written), text)
                 assert not L.PV16 or need <= swapped, "P.V MFMA reads P registers before their lane-row swap: " + text
 
 
-def body(st, L, k, safe):
+# fillers are paced in CYCLES: v_exp 8, s_nop 2, other VALU 4
+cost = lambda kind: 8.0 if kind == "e" else (2.0 if kind == "n" else 4.0)
+
+
+class Fillers:
+    """one class of filler instructions, spread uniformly (in cycles) over the MFMA shadows first .. last; the items from index
+    `held` on are not issued before shadow `release`.  `done` of them are already issued when the pacing starts."""
+
+    def __init__(self, items, first, last, done=0, held=None, release=0):
+        self.items, self.first, self.last, self.done, self.held, self.release = items, first, last, done, held, release
+        self.total = sum(cost(o[0]) for o in items)
+        self.spent = sum(cost(o[0]) for o in items[:done])
+
+
+def fill_shadow(st, i, used, budget, classes, later, after=None):
+    """what a body puts behind the MFMA of shadow i: the next item of `later` (LDS-DMA pieces, loader advances: (emitter, cycles)),
+    then of every class whose window is open as many fillers as bring it up to its share of the window, until the shadow's cycle
+    budget is spent (`used`: what the caller has put there already).  The last shadow of a window takes all that is left of its class.
+    after(): called behind every filler (the wide body puts the second half of an LDS-DMA piece there)."""
+    if later:
+        fn, cyc = later.pop(0)
+        fn()
+        used += cyc
+    for c in classes:
+        if i < c.first:
+            continue
+        frac = min(1.0, (i - c.first + 1) / float(c.last - c.first + 1))
+        while c.done < len(c.items):
+            kind, text = c.items[c.done]
+            if c.held is not None and c.done >= c.held and i < c.release:
+                break
+            if c.total * frac - c.spent <= 0 and i < c.last:
+                break
+            if used >= budget and i < c.last:
+                break
+            st.emit(text, kind)
+            used += cost(kind)
+            c.spent += cost(kind)
+            c.done += 1
+            if after:
+                after()
+
+
+def body(st, L, k, knobs):
     """iteration with ring slot parity k: SC = scores of tile t (k == 0: set A), SN receives tile t+1"""
-    NU = L.NU
+    NU, FAST, DMAGAP, DMACOST = L.NU, L.FAST, knobs.dma_gap, knobs.dma_cost
     sc, sn = (L.SA0, L.SB0) if k == 0 else (L.SB0, L.SA0)
     cur = k
     uid = "b%d" % k
@@ -844,11 +888,10 @@ def body(st, L, k, safe):
     later.append((lambda: dma_last(st, L, "v", cur ^ 1, uid), DMACOST))
     if not L.PV8 and not FAST:   # pv8: the ones / key-validity row arrives with the V^T tile itself; fast: whole tiles only
         later.append((lambda: ones_row(st, L, cur ^ 1), 8))   # before the V^T loader moves on: S_VRG is tile t+1's
-    later.append((lambda: advance(st, "k", uid, 128, L, cur), 20 if FAST else 28))
-    later.append((lambda: (advance(st, "v", uid, L.G.VSTEP, L, cur ^ 1), ragged_masks(st)), 20 if FAST else 32))
+    later.append((lambda: advance(st, L, "k", uid, cur), 20 if FAST else 28))
+    later.append((lambda: (advance(st, L, "v", uid, cur ^ 1), ragged_masks(st, L)), 20 if FAST else 32))
 
-    # -- fillers paced in CYCLES (v_exp 8, other VALU 4): three classes, each spread uniformly over its window
-    cost = lambda kind_: 8.0 if kind_ == "e" else (2.0 if kind_ == "n" else 4.0)
+    # -- fillers (fill_shadow): three classes, each spread uniformly over its window
     clsA, clsB, clsC = [], [], []
     for g in range(4):
         for u in range(NU):
@@ -859,18 +902,21 @@ def body(st, L, k, safe):
         if L.PV16 and g % 2 == 1:
             for u in range(NU):
                 (clsA if g < 2 else clsB).extend(swap_group(L, u, g // 2))
-    dq = (lambda u, t2: dequant(L, sn, u, t2)) if L.QK8 else (lambda u, t2: [])
-    ca = [dq(u, 0) + max_chain(L, sn, u, 0, chain_tmp(L, u, 0)) for u in range(NU)]
-    cb = [dq(u, 1) + max_chain(L, sn, u, 1, chain_tmp(L, u, 1)) for u in range(NU)]
-    clsC.extend([o for grp in zip(*ca) for o in grp])
-    n_first_b = len(clsC)
-    clsC.extend([o for grp in zip(*cb) for o in grp])
-    clsC.extend(lanemax_final(L))
-    if FAST:   # no reference max to maintain
-        clsC, n_first_b = [], 0
-    W = L.FAST_WINDOWS if FAST else L.WINDOWS
-    classes = [[clsA, W[0], W[1], 0, 0.0], [clsB, W[2], W[3], 0, 0.0], [clsC, W[4], W[5], 0, 0.0]]
-    totals = [sum(cost(o[0]) for o in c[0]) for c in classes]
+    # FAST bodies carry no class C (no reference max to maintain): exp2 + pack paced evenly over the whole iteration (deadlines: group
+    # g before the P.V pairs of group g, which start at shadow I_PV0 + g NDT NU)
+    W = (dict(knobs.fast_windows).get(L.G.HD) if FAST and NU == 2 else None) or L.WINDOWS
+    classes = [Fillers(clsA, W[0], W[1]), Fillers(clsB, W[2], W[3])]
+    if not FAST:
+        dq = (lambda u, t2: dequant(L, sn, u, t2)) if L.QK8 else (lambda u, t2: [])
+        ca = [dq(u, 0) + max_chain(L, sn, u, 0, chain_tmp(L, u, 0)) for u in range(NU)]
+        cb = [dq(u, 1) + max_chain(L, sn, u, 1, chain_tmp(L, u, 1)) for u in range(NU)]
+        clsC.extend([o for grp in zip(*ca) for o in grp])
+        n_first_b = len(clsC)   # the chains over keys 32..63 wait for shadow C_T2_RELEASE
+        clsC.extend([o for grp in zip(*cb) for o in grp])
+        clsC.extend(lanemax_final(L))
+        classes.append(Fillers(clsC, W[4], W[5], held=n_first_b, release=L.C_T2_RELEASE))
+    qk_budget = knobs.qk8 if L.QK8 else knobs.m32
+    budget = {"qk": qk_budget, "pv": knobs.pv8 if L.PV8 else (knobs.pv16 if L.PV16 else qk_budget)}
     mf = [("qk", a) for a in range(L.NQK)] + [("pv", b) for b in range(L.NPVB)]
     for n, (kind, idx) in enumerate(mf):
         i = L.I_QK0 + n
@@ -888,7 +934,7 @@ def body(st, L, k, safe):
             qk_mfma(st, L, sn, idx)
         else:
             pv_mfma(st, L, idx)
-        if safe:
+        if knobs.safe:
             st.emit("s_nop 7", "n")
         used = 0.0
         # ring reads: after the last MFMA of pair x its ring slot is free -> read pair x + 4
@@ -904,32 +950,10 @@ def body(st, L, k, safe):
             elif pair + L.RD < L.G.NPV:
                 v_read(st, L, cur, pair + L.RD, ("v", pair + L.RD))
                 used += 8 if L.PV8 else 4
-        if later and n % DMAGAP == 0:
-            fn, cyc = later.pop(0)
-            fn()
-            used += cyc
-        for ci, c in enumerate(classes):
-            items, first, last = c[0], c[1], c[2]
-            if i < first:
-                continue
-            frac = min(1.0, (i - first + 1) / float(last - first + 1))
-            while c[3] < len(items):
-                kind_, text = items[c[3]]
-                if ci == 2 and c[3] >= n_first_b and i < L.C_T2_RELEASE:
-                    break
-                if totals[ci] * frac - c[4] <= 0 and i < last:
-                    break
-                if used >= (N2_BUDGET["pv8"] if kind == "pv" and L.PV8 else (N2_BUDGET["pv16"] if kind == "pv" and L.PV16 else
-                                                                              (N2_BUDGET["qk8"] if L.QK8 else N2_BUDGET["m32"]))) and i < last:
-                    break
-                st.emit(text, kind_)
-                used += cost(kind_)
-                c[4] += cost(kind_)
-                c[3] += 1
-    for c in classes:
-        assert c[3] == len(c[0]), "unscheduled filler work"
+        fill_shadow(st, i, used, budget[kind], classes, later if n % DMAGAP == 0 else None)
+    assert all(c.done == len(c.items) for c in classes), "unscheduled filler work"
     assert not later
-    _check_p_ready(st, L, k)
+    _check_p_ready(st, L, ".L@@_entry%d" % k)
     # -- end of body: DMA landed + every fragment read retired, then the tile barrier
     st.emit("s_waitcnt vmcnt(0) lgkmcnt(0)", "w")
     st.pending = []
@@ -942,23 +966,10 @@ def body(st, L, k, safe):
     return pieces
 
 
-def generate(L, safe=False, ablate=frozenset(), fast=False):
-    assert not L.G.NOM or fast, "the padding k-step may only be dropped in the bounded (FAST) body"
-    """fast: the bounded / single-segment / whole-tile variant (see the header); not for the fp8 P.V kernels, whose e4m3 P
-    needs the reference max within 2^8 of the true one"""
-    global FAST
-    assert not (fast and L.PV8)
-    FAST = fast
-    try:
-        return _generate(L, safe, ablate)
-    finally:
-        FAST = False
-
-
-def _generate(L, safe, ablate):
-    st = Stream(ablate)
+def preamble(st, L, zeroed):
+    """copy the mutable scalars into asm-owned SGPRs (`zeroed`: the counters that start at 0), lane masks and flags, the loaders'
+    initial state, M = 0, O^T = 0"""
     e = st.emit
-    # ---- copy the mutable scalars into asm-owned SGPRs
     e("s_mov_b64 s[%d:%d], %s" % (S_KB, S_KB + 1, L.OP["kbase"]))
     e("s_mov_b64 s[%d:%d], %s" % (S_VB, S_VB + 1, L.OP["vbase"]))
     e("s_mov_b32 s%d, %s" % (S_KSTEP, L.OP["kstep"]))
@@ -972,7 +983,7 @@ def _generate(L, safe, ablate):
         e("s_lshr_b32 s%d, %s, 16" % (S_NT, L.OP["tpsnt"]))
         e("s_lshr_b32 s%d, %s, 16" % (S_NKW, L.OP["nkvw"]))
         e("s_and_b32 s%d, %s, 0xffff" % (S_NVW, L.OP["nkvw"]))
-    for sreg in (S_T, S_KTT, S_VTT, S_KL, S_VL):
+    for sreg in zeroed:
         e("s_mov_b32 s%d, 0" % sreg)
     if L.G.M_HI:       # S_HIM = the half-wave whose lanes hold Q's M-carrying padding dim
         e("s_mov_b32 s%d, 0" % S_HIM)
@@ -990,7 +1001,7 @@ def _generate(L, safe, ablate):
     e("s_lshr_b32 s%d, s%d, 8" % (S_FLG, S_NVW))
     e("s_and_b32 s%d, s%d, 1" % (S_NRG, S_FLG))
     e("s_and_b32 s%d, s%d, 0xff" % (S_NVW, S_NVW))
-    if not FAST:
+    if not L.FAST:
         ragged_mask(st, "k")
         ragged_mask(st, "v")
     else:
@@ -999,12 +1010,40 @@ def _generate(L, safe, ablate):
         e("v_mov_b32 %s, 0" % vr(L.MM[u]))
     for r in range(L.A_O0, L.A_Q0):
         e("v_accvgpr_write_b32 %s, 0" % ar(r))
-    # ---- prologue: K0, V0 -> slot 0, K1 -> slot 1
+
+
+def prologue_loads(st, L):
+    """K0, V0 -> slot 0, K1 -> slot 1, landed and visible to every wave"""
     dma_group(st, L, "k", 0, "p0")
     dma_group(st, L, "v", 0, "p1")
     dma_group(st, L, "k", 1, "p2")
-    e("s_waitcnt vmcnt(0)")
-    e("s_barrier")
+    st.emit("s_waitcnt vmcnt(0)")
+    st.emit("s_barrier")
+
+
+def exit_sequence(st, L, pv):
+    """the trailing P.V MFMAs of the last tile (pv: the layout's P.V MFMA emitter), then M for the wrapper's epilogue"""
+    st.label(".L@@_exit")
+    for n in range(L.NTRAIL):
+        pv(st, L, (L.G.NPV - L.NTP) * L.MPP + n)
+    st.emit("s_nop 15")
+    st.emit("s_nop 15")
+    st.emit("v_mov_b32 %s, %s" % (L.OP["m0out"], vr(L.MM[0])))
+    st.emit("v_mov_b32 %s, %s" % (L.OP["m1out"], vr(L.MM[1])))
+
+
+def generate(L, fast=False, knobs=Knobs()):
+    """fast: the bounded / single-segment / whole-tile variant (see the header); not for the fp8 P.V kernels, whose e4m3 P
+    needs the reference max within 2^8 of the true one"""
+    assert not L.G.NOM or fast, "the padding k-step may only be dropped in the bounded (FAST) body"
+    assert not (fast and L.PV8)
+    L = copy.copy(L)
+    L.FAST = fast
+    st = Stream()
+    e = st.emit
+    # (FAST: S_KTT / S_VTT are the loaders' next-event indices, which fast_preamble() sets right behind)
+    preamble(st, L, (S_T, S_KTT, S_VTT, S_KL, S_VL))
+    prologue_loads(st, L)
     # scores of tile 0 -> set A (Q's padding dim is 0: raw scores)
     for p in range(L.G.NPK):
         if p < L.G.NPK_READ:
@@ -1015,7 +1054,7 @@ def _generate(L, safe, ablate):
     e("s_barrier")                      # every wave has read K0: slot 0 may be refilled
     e("s_nop 15")
     e("s_nop 15")
-    if not FAST:   # (fast: Q's padding dim already carries the bound, the scores above are final)
+    if not fast:   # (fast: Q's padding dim already carries the bound, the scores above are final)
         for t2 in range(2):
             for u in range(L.NU):
                 for op in (dequant(L, L.SA0, u, t2) if L.QK8 else []) + max_chain(L, L.SA0, u, t2, chain_tmp(L, u, t2)):
@@ -1023,34 +1062,25 @@ def _generate(L, safe, ablate):
         fixup(st, L, L.SA0, init=True)
     # what body 0 does before its entry point: the first LDS-DMA pieces of K(2) -> slot 0 and V(1) -> slot 1 (the
     # same ones body() puts into the trailing shadows), the first K fragment reads of tile 1
-    pieces = body(Stream(), L, 0, False)
+    pieces = body(Stream(), L, 0, knobs)
     for w, i in pieces:
         (k_dma if w == "k" else v_dma)(st, L, 0 if w == "k" else 1, i)
     for p in range(L.KRD):
         k_read(st, L, 1, p, ("k", p))
     e("s_branch .L@@_entry0")
     # ---- the two loop bodies
-    st.in_body = True
     for k in range(2):
         st.pending = []
-        body(st, L, k, safe)
-    st.in_body = False
+        body(st, L, k, knobs)
     # ---- rare paths
-    for k in range(0 if FAST else 2):
+    for k in range(0 if fast else 2):
         st.label(".L@@_rare%d" % k)
         fixup(st, L, L.SA0 if k == 0 else L.SB0, init=False)
         e("s_branch .L@@_entry%d" % k)
-    if FAST:
+    if fast:
         e("s_branch .L@@_exit")   # (never reached: both bodies end in branches)
         fast_events(st, L)
-    # ---- exit: the trailing P.V MFMAs of the last tile
-    st.label(".L@@_exit")
-    for n in range(L.NTRAIL):
-        pv_mfma(st, L, (L.G.NPV - L.NTP) * L.MPP + n)
-    e("s_nop 15")
-    e("s_nop 15")
-    e("v_mov_b32 %s, %s" % (L.OP["m0out"], vr(L.MM[0])))
-    e("v_mov_b32 %s, %s" % (L.OP["m1out"], vr(L.MM[1])))
+    exit_sequence(st, L, pv_mfma)
     return st
 
 
@@ -1072,7 +1102,7 @@ class LayoutW(Layout):
     def __init__(self):
         Layout.__init__(self, 2, 72, pv16=True)
         G = self.G
-        self.WIDE = True
+        self.FAST = True
         self.NUW = 4                                   # query blocks per wave
         self.A_O0 = 0
         self.A_Q0 = 4 * G.NDB * 2 * self.NUW           # 160
@@ -1084,13 +1114,7 @@ class LayoutW(Layout):
         self.MT = [self.TMP0 + 6, self.TMP0 + 7]
         self.TX = [self.TMP0 + 8 + i for i in range(4)]
         self.V_END = self.TMP0 + 12
-        assert self.V_END <= 256 and self.A_END <= 256
-
-    def AO16W(self, u2, qb, db):
-        return self.A_O0 + ((u2 * 2 + qb) * self.G.NDB + db) * 4
-
-    def AQW(self, u2, ks):
-        return self.A_Q0 + (u2 * self.G.NKS + ks) * 4
+        assert self.V_END <= 256 and self.A_END <= 256   # (AO16 / AQ: indexed by u'' here)
 
 
 def kw_read(st, L, slot, half, ks, tag):
@@ -1106,7 +1130,7 @@ def qkw_mfma(st, L, sn, a):
     p, u = a // 2, a % 2
     ks, ph = p // 2, p % 2
     dst = vr(L.S(sn, u, ph), 16)
-    st.emit("v_mfma_f32_32x32x16_bf16 %s, %s, %s, %s" % (dst, vr(L.KR0 + (ks % 4) * 4, 4), ar(L.AQW(2 * ph + u, ks), 4),
+    st.emit("v_mfma_f32_32x32x16_bf16 %s, %s, %s, %s" % (dst, vr(L.KR0 + (ks % 4) * 4, 4), ar(L.AQ(2 * ph + u, ks), 4),
                                                        "0" if ks == 0 else dst), "M")
 
 
@@ -1114,14 +1138,11 @@ def pvw_mfma(st, L, b):
     r, sub = b // 4, b % 4
     u, qb = sub // 2, sub % 2
     ph, db = r // L.G.NDB, r % L.G.NDB
-    dst = ar(L.AO16W(2 * ph + u, qb, db), 4)
+    dst = ar(L.AO16(2 * ph + u, qb, db), 4)
     st.emit("v_mfma_f32_16x16x32_bf16 %s, %s, %s, %s" % (dst, vr(L.VR0 + db * 4, 4), vr(L.PB(u, 2 * ph + qb), 4), dst), "X")
 
 
-WIDE_EXP = {"gap": 1, "win": None, "vm": 0, "swapnop": False, "kwait2": True, "dmafill": True, "budget": (9, 24), "pretrail": 0}   # production values; --wide-exp flips them   # --wide-exp (experiments): DMA piece spacing in the trailing shadows, filler windows, swap placement
-
-
-def body_wide(st, L, k, h, safe=False):
+def body_wide(st, L, k, h, knobs):
     """body (k, h): P.V of key half h of the tile in ring slot k (its scores: set A when h == 0, set B when h == 1) beside QK^T
     of the next half into the other set"""
     G = L.G
@@ -1134,16 +1155,15 @@ def body_wide(st, L, k, h, safe=False):
     for ks in range(4):
         kw_read(st, L, nslot_, nhalf, ks, ("k", ks))
     dma = k_dma if which == "k" else v_dma
-    gap = WIDE_EXP["gap"]
+    gap = knobs.wide_gap
     pieces = list(range(nslot(L, which) - 1))[:(L.NTRAIL + gap - 1) // gap]
-    cost = lambda kind_: 8.0 if kind_ == "e" else (2.0 if kind_ == "n" else 4.0)
     clsA, clsB = [], []
     for g in range(4):
         for u in range(2):
             (clsA if g < 2 else clsB).extend(exp_group(L, sc, u, g))
         if g % 2 == 1:
             for u in range(2):
-                (clsA if g < 2 else clsB).extend(swap_group(L, u, g // 2, guard=WIDE_EXP["swapnop"]))
+                (clsA if g < 2 else clsB).extend(swap_group(L, u, g // 2, guard=False))
     # round 5: the trailing P.V shadows of the PREVIOUS half (8 x 16 cycles that carried only LDS-DMA M0 writes) take the first
     # exponentials of THIS half's phase-0 scores -- complete since the previous body's QK^T, touched by nobody else: exp2 in place --
     # one per shadow, out of the QK^T shadows that were the body's fullest.  A body entered at its entry label (the prologue's jump into
@@ -1156,23 +1176,20 @@ def body_wide(st, L, k, h, safe=False):
         pvw_mfma(st, L, 32 + n)                    # pairs 8, 9 = (phase 1, row blocks 3, 4) of the previous body
         if pn < len(pieces):
             dma(st, L, dslot, pieces[pn], 2)
-        for _ in range(WIDE_EXP["pretrail"]):
+        for _ in range(knobs.wide_pretrail):
             if len(pre) < len(clsA) and clsA[len(pre)][0] == "e":
                 st.emit(clsA[len(pre)][1], "e")
                 pre.append(clsA[len(pre)])
     st.label(".L@@_entry%d%d" % (k, h))
-    later = []
+    later = []         # (12: the issue cycles a shadow's filler budget is charged for an LDS-DMA item)
     deferred = []      # the LDS-DMA instruction of a piece whose M0 write was just emitted: goes behind the next filler instruction
     for i in range(len(pieces), nslot(L, which) - 1):
-        if WIDE_EXP["dmafill"]:
-            later.append((lambda i=i: (dma(st, L, dslot, i, 1), deferred.append(lambda i=i: dma(st, L, dslot, i, 2))), DMACOST))
-        else:
-            later.append((lambda i=i: dma(st, L, dslot, i), DMACOST))
-    later.append((lambda: dma_last(st, L, which, dslot, uid), DMACOST))
-    later.append((lambda: advance(st, which, uid, G.VSTEP, L, dslot), 20))
-    W = WIDE_EXP["win"] or L.FAST_WINDOWS
-    classes = [[clsA, W[0], W[1], len(pre), sum(cost(o[0]) for o in pre)], [clsB, W[2], W[3], 0, 0.0]]
-    totals = [sum(cost(o[0]) for o in c[0]) for c in classes]
+        later.append((lambda i=i: (dma(st, L, dslot, i, 1), deferred.append(lambda i=i: dma(st, L, dslot, i, 2))), 12))
+    later.append((lambda: dma_last(st, L, which, dslot, uid), 12))
+    later.append((lambda: advance(st, L, which, uid, dslot), 20))
+    W = knobs.wide_windows or L.WINDOWS
+    classes = [Fillers(clsA, W[0], W[1], done=len(pre)), Fillers(clsB, W[2], W[3])]
+    budget = {"pv": knobs.wide_budget[0], "qk": knobs.wide_budget[1]}
     mf = [("qk", a) for a in range(20)] + [("pv", b) for b in range(32)]
     for n, (kind, idx) in enumerate(mf):
         i = L.I_QK0 + n
@@ -1180,14 +1197,8 @@ def body_wide(st, L, k, h, safe=False):
         if kind == "qk":
             p, u = idx // 2, idx % 2
             ks, ph = p // 2, p % 2
-            if u == 0 and ph == 0:
-                if not WIDE_EXP["kwait2"]:
-                    st.need(("k", ks))
-                elif WIDE_EXP["kwait2"] == 4:
-                    if ks in (0, 4):       # experiment: one wait for the four fragments read at the top, one for the fifth
-                        st.need(("k", 3 if ks == 0 else 4))
-                elif ks % 2 == 0:          # one wait per two k-steps (the fragments of both were issued long before)
-                    st.need(("k", min(ks + 1, G.NKS - 1)))
+            if u == 0 and ph == 0 and ks % 2 == 0:   # one wait per two k-steps (the fragments of both were issued long before)
+                st.need(("k", min(ks + 1, G.NKS - 1)))
             qkw_mfma(st, L, sn, idx)
             if u == 1 and ph == 1:                 # both phases of this k-step issued: its K ring slot is free
                 if ks + 4 < G.NKS:
@@ -1204,39 +1215,18 @@ def body_wide(st, L, k, h, safe=False):
             if r == 0 and sub == 3:                # the fifth V^T fragment (row block 4: dims 64..71, ones row)
                 st.ds_read(L.VR0 + 4 * 4, L.OP["vo%d" % h], G.VOFF[k] + 4 * 2048, ("v", 4))
                 used += 4
-        if safe:
+        if knobs.safe:
             st.emit("s_nop 7", "n")
-        if later:
-            fn, cyc = later.pop(0)
-            fn()
-            used += cyc
-        for ci, c in enumerate(classes):
-            items, first, last = c[0], c[1], c[2]
-            if i < first:
-                continue
-            frac = min(1.0, (i - first + 1) / float(last - first + 1))
-            while c[3] < len(items):
-                kind_, text = items[c[3]]
-                if totals[ci] * frac - c[4] <= 0 and i < last:
-                    break
-                if used >= (WIDE_EXP["budget"][0] if kind == "pv" else WIDE_EXP["budget"][1]) and i < last:   # filler cycles per 16 / 32-cycle shadow (round 5: 9 / 24 -- an MFMA's own issue takes 4.4 cycles and v_exp_f32 8.5, not 8: with round 4's 13 / 30 the shadows were over-subscribed; in-step A/B -0.8 % per launch on two boxes, profiles/r05n_attn_filler_budget_ab.jsonl)
-                    break
-                st.emit(text, kind_)
-                used += cost(kind_)
-                c[4] += cost(kind_)
-                c[3] += 1
-                if deferred:               # one instruction now sits between the M0 write and its LDS-DMA
-                    deferred.pop(0)()
+        # behind a filler, one instruction sits between the M0 write and its LDS-DMA
+        fill_shadow(st, i, used, budget[kind], classes, later, after=lambda: deferred and deferred.pop(0)())
         if deferred:                       # no filler in this shadow: the wait state the hardware needs
             st.emit("s_nop 0", "n")
             deferred.pop(0)()
-    for c in classes:
-        assert c[3] == len(c[0]), "unscheduled filler work"
+    assert all(c.done == len(c.items) for c in classes), "unscheduled filler work"
     assert not later and not deferred
-    _check_p_ready_wide(st, k, h)
-    # the pieces this body issued are not needed before the body after next (K(t + 2) from (t, 1): read from (t + 1, 1) on; V^T(t + 1)
-    # from (t, 0): read from (t + 1, 0) on): the wait in front of the barrier only has to retire the PREVIOUS body's pieces
-    st.emit("s_waitcnt vmcnt(%d) lgkmcnt(0)" % WIDE_EXP["vm"], "w")
+    _check_p_ready(st, L, ".L@@_entry%d%d" % (k, h))
+    # every LDS-DMA piece has landed and every fragment read has retired in front of the barrier
+    st.emit("s_waitcnt vmcnt(0) lgkmcnt(0)", "w")
     st.pending = []
     st.emit("s_barrier", "B")
     if h == 1:
@@ -1248,66 +1238,12 @@ def body_wide(st, L, k, h, safe=False):
     return which, dslot, pieces, pre
 
 
-def _check_p_ready_wide(st, k, h):
-    """body_wide's filler windows are hand-set: every P.V MFMA of the body's own half comes after the packs and the lane-row swap of
-    its P operand; every MFMA after the s_waitcnt that covers its LDS operand is checked by Stream.need's bookkeeping"""
-    import re as _re
-    start = max(i for i, (kind, text) in enumerate(st.table) if kind == "L" and text.endswith("_entry%d%d" % (k, h)))
-    written, swapped = set(), set()
-    for kind, text in st.table[start:]:
-        if text.startswith("v_cvt_pk"):
-            written.add(int(_re.match(r"v_cvt_pk_\w+ v(\d+),", text).group(1)))
-        elif text.startswith("v_permlane16_swap"):
-            a_, b_ = (int(x) for x in _re.match(r"v_permlane16_swap_b32 v(\d+), v(\d+)", text).groups())
-            assert {a_, b_} <= written, "lane-row swap before its registers are packed: " + text
-            swapped |= {a_, b_}
-        elif text.startswith("v_mfma_f32_16x16x32"):
-            m = _re.match(r"v_mfma_\w+ a\[\d+:\d+\], v\[\d+:\d+\], v\[(\d+):(\d+)\]", text)
-            need = set(range(int(m.group(1)), int(m.group(2)) + 1))
-            assert need <= written and need <= swapped, "P.V MFMA before its P operand is ready: " + text
-
-
-def generate_wide(L, safe=False):
-    global FAST
-    FAST = True
-    try:
-        return _generate_wide(L, safe)
-    finally:
-        FAST = False
-
-
-def _generate_wide(L, safe):
+def generate_wide(L, knobs=Knobs()):
     st = Stream()
     e = st.emit
     G = L.G
-    e("s_mov_b64 s[%d:%d], %s" % (S_KB, S_KB + 1, L.OP["kbase"]))
-    e("s_mov_b64 s[%d:%d], %s" % (S_VB, S_VB + 1, L.OP["vbase"]))
-    e("s_mov_b32 s%d, %s" % (S_KSTEP, L.OP["kstep"]))
-    e("s_mov_b64 s[%d:%d], %s" % (S_KJ, S_KJ + 1, L.OP["kjump"]))
-    e("s_mov_b64 s[%d:%d], %s" % (S_VJ, S_VJ + 1, L.OP["vjump"]))
-    e("s_mov_b32 s%d, %s" % (S_KDST, L.OP["kdst"]))
-    e("s_mov_b32 s%d, %s" % (S_VDST, L.OP["vdst"]))
-    e("s_and_b32 s%d, %s, 0xffff" % (S_TPS, L.OP["tpsnt"]))
-    e("s_lshr_b32 s%d, %s, 16" % (S_NT, L.OP["tpsnt"]))
-    e("s_lshr_b32 s%d, %s, 16" % (S_NKW, L.OP["nkvw"]))
-    e("s_and_b32 s%d, %s, 0xffff" % (S_NVW, L.OP["nkvw"]))
-    for sreg in (S_T, S_KL, S_VL):
-        e("s_mov_b32 s%d, 0" % sreg)
-    e("s_mov_b32 s%d, 0" % S_HIM)
-    e("s_mov_b32 s%d, -1" % (S_HIM + 1))
-    e("s_lshr_b32 s%d, s%d, 8" % (S_FLG, S_NVW))
-    e("s_and_b32 s%d, s%d, 1" % (S_NRG, S_FLG))
-    e("s_and_b32 s%d, s%d, 0xff" % (S_NVW, S_NVW))
-    fast_preamble(st, L)
-    for u in range(2):
-        e("v_mov_b32 %s, 0" % vr(L.MM[u]))
-    for r in range(L.A_O0, L.A_Q0):
-        e("v_accvgpr_write_b32 %s, 0" % ar(r))
-    dma_group(st, L, "k", 0, "p0")
-    dma_group(st, L, "v", 0, "p1")
-    dma_group(st, L, "k", 1, "p2")
-    e("s_waitcnt vmcnt(0)")
-    e("s_barrier")
+    preamble(st, L, (S_T, S_KL, S_VL))
+    prologue_loads(st, L)
     for ks in range(G.NKS):                     # scores of (tile 0, half 0) -> set A
         kw_read(st, L, 0, 0, ks, ("k", ks))
         st.need(("k", ks))
@@ -1316,31 +1252,130 @@ def _generate_wide(L, safe):
                 qkw_mfma(st, L, L.SA0, (ks * 2 + ph) * 2 + u)
     e("s_nop 15")
     e("s_nop 15")
-    which, dslot, pieces, pre = body_wide(Stream(), L, 0, 0)
-    for i in pieces:                            # what body (0, 0) does before its entry point
+    which, dslot, pieces, pre = body_wide(Stream(), L, 0, 0, knobs)
+    for i in pieces:                          # what body (0, 0) does before its entry point
         (k_dma if which == "k" else v_dma)(st, L, dslot, i)
     for kind_, text in pre:                     # (incl. the exponentials its trailing shadows carry: the two s_nop 15 above cover the QK^T latency)
         e(text)
     for ks in range(4):
         kw_read(st, L, 0, 1, ks, ("k", ks))
     e("s_branch .L@@_entry00")
-    st.in_body = True
     for k in range(2):
         for h in range(2):
             st.pending = []
-            body_wide(st, L, k, h, safe)
-    st.in_body = False
+            body_wide(st, L, k, h, knobs)
     fast_events(st, L)
-    if not WIDE_EXP["swapnop"]:
-        _check_swap_distance(st)
-    st.label(".L@@_exit")
-    for n in range(L.NTRAIL):
-        pvw_mfma(st, L, 32 + n)
-    e("s_nop 15")
-    e("s_nop 15")
-    e("v_mov_b32 %s, %s" % (L.OP["m0out"], vr(L.MM[0])))
-    e("v_mov_b32 %s, %s" % (L.OP["m1out"], vr(L.MM[1])))
+    _check_swap_distance(st)
+    exit_sequence(st, L, pvw_mfma)             # pairs 8, 9 of the last body
     return st
+
+
+CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "open_sora_amd", "csrc")
+
+
+def tagof(L):
+    return "%d%s" % (L.G.HD, "q8" if L.QK8 else ("p8" if L.PV8 else ""))
+
+
+def shipped():
+    """(file name, note, label prefix, layout, fast) of every body the library includes: the 4 waves x 64 rows layout (NU = 2) of both
+    head dims, bf16 and fp8, and the wide layout.  The 8 waves x 32 rows layout (NU = 1, head_dim 72) tied NU = 2 in rounds 1-2 and
+    stays a generator option (--table 1) without a shipped body.  "@@" in a label of the stream -> the prefix, unique per body and
+    per emitted copy of it."""
+    rows = []
+    for hd, pv8, qk8 in ((72, False, False), (128, False, False), (72, True, False), (128, True, False), (128, True, True)):
+        L = Layout(2, hd, pv8, pv16=(hd == 72 and not pv8), qk8=qk8)
+        rows.append(("attention_asm%s_n2_v0.inc" % tagof(L), "head_dim %d%s, layout NU=2" %
+                     (hd, ", fp8 QK^T and P.V" if qk8 else (", fp8 P.V" if pv8 else "")), "osk%sn2v0_%%=" % tagof(L), L, False))
+        if not pv8:   # the bounded body of the same layout (hd 128: the padding k-step is dropped too)
+            rows.append(("attention_asm%s_n2_f0.inc" % tagof(L), "head_dim %d, layout NU=2, FAST body (score bound, one segment of whole tiles)" % hd,
+                         "osk%sn2f0_%%=" % tagof(L), Layout(2, hd, pv16=L.PV16, nom=(hd == 128)), True))
+    rows.append(("attention_asm72w_f0.inc", "head_dim 72, WIDE layout (4 waves x 128 query rows, one 32-key half per body), FAST body",
+                 "osk72wf0_%=", LayoutW(), True))
+    return rows
+
+
+def variant_note(knobs, wide):
+    """how a generated file's first line names its schedule (the spellings the A/B records under profiles/ were taken with)"""
+    dma = "" if (knobs.dma_gap, knobs.dma_cost) == (1, 12) else "dmagap%d" % knobs.dma_gap + ("c%d" % knobs.dma_cost if knobs.dma_cost != 12 else "")
+    if not (knobs.safe or dma):
+        return "production"
+    if wide:
+        return "experiment " + ("safe" if knobs.safe else dma)
+    return "hazard-padded (debug)" if knobs.safe else "schedule experiment " + dma
+
+
+def write_regs(out, rows):
+    """attention_asm_regs.inc: the register / operand contract the wrappers static_assert and bind their asm operands by"""
+    LW = next(L for _, _, _, L, _ in rows if isinstance(L, LayoutW))
+    general = [L for _, _, _, L, fast in rows if not fast]
+    with open(os.path.join(out, "attention_asm_regs.inc"), "w") as f:
+        def layout_regs(P, L, nu):   # nu: query blocks per wave
+            G = L.G
+            f.write("#define %sCLOBBERS %s\n" % (P, clobbers(L.V_FIRST, L.V_END - L.V_FIRST, L.A_END, S_FIRST, S_LAST)))
+            f.write("#define %sA_CLOBBERS %s\n" % (P, ", ".join('"a%d"' % i for i in range(0, L.A_END))))
+            f.write("#define %sNSLOT %d\n" % (P, L.NSLOT))
+            if L.PV8:
+                f.write("#define %sNSLOT_V %d\n" % (P, L.NSLOT_V))
+            # register map the wrapper binds as asm operands (acc_quads.h): Q fragment words of block u = AGPRs AQ(u) .. + 4 NKS
+            for u in range(nu):
+                f.write("#define %sAQ%d %d\n" % (P, u, L.AQ(u, 0)))
+            if L.QK8:
+                f.write("#define %sA_END %d\n" % (P, L.A_END))
+            if L.PV16:   # O^T of (u, 16-query block qb) = AGPRs 4 NDB (2 u + qb) .. (row block db, register i at + 4 db + i)
+                assert all(L.AO16(u, qb, db) == 4 * G.NDB * (2 * u + qb) + 4 * db for u in range(nu) for qb in range(2) for db in range(G.NDB))
+                f.write("#define %sAO_REGS %d\n" % (P, 4 * G.NDB * 2 * nu))
+            else:
+                assert all(L.AO(u, d) == 16 * (u * G.NDT + d) for u in range(nu) for d in range(G.NDT))   # O^T row tile (u, d): 16 registers
+                f.write("#define %sAO_REGS %d\n" % (P, 16 * G.NDT * nu))
+
+        f.write(header("gen_attn_asm.py"))
+        layout_regs("OSK72W_", LW, LW.NUW)
+        for L in sorted(general, key=lambda L: (L.G.HD, L.PV8, L.QK8)):
+            G = L.G
+            P = "OSK%s_" % tagof(L).upper()
+            f.write("#define %sSMEM %d\n#define %sCONST_OFF %d\n" % (P, G.SMEM, P, G.CONST_OFF))
+            f.write("#define %sKTILE %d\n#define %sVTILE %d\n#define %sVOFF0 %d\n#define %sKOFF0 %d\n" % (P, G.KTILE, P, G.VTILE, P, G.VOFF[0], P, G.KOFF[0]))
+            f.write("#define %sNKS %d\n#define %sNDT %d\n#define %sNKD %d\n#define %sKIMG %d\n" % (P, G.NKS, P, G.NDT, P, G.NKD, P, G.KIMG))
+            if L.PV8:
+                f.write("#define %sRP %d\n#define %sNVD %d\n" % (P, G.RP, P, G.NVD))
+        for L in general:
+            P = "OSK%sN%d_" % (tagof(L).upper(), L.NU)
+            if L.PV16:
+                f.write("#define %sPV16 1\n#define OSK%s_NDB %d\n" % (P, tagof(L).upper(), L.G.NDB))
+            layout_regs(P, L, L.NU)
+
+
+def print_table(st):
+    """the schedule shadow by shadow: one row per MFMA, the kinds of what sits in its shadow behind it"""
+    row = []
+    for kind, text in st.table:
+        if kind in ("M", "F", "X", "Q"):
+            print("".join(row)); row = [kind + " "]
+        elif kind == "L":
+            print("".join(row)); row = []; print(text + ":")
+        else:
+            row.append({"x": "v"}.get(kind, kind))
+    print("".join(row))
+
+
+def parse_knobs(settings):
+    """--set name=value ... -> Knobs.  A bool: `name` alone, or name=0 / 1; several numbers: comma-separated; fast_windows=hd:a0,a1,b0,b1"""
+    types = {f.name: f.type for f in dataclasses.fields(Knobs)}
+    ints = lambda text: tuple(int(x) for x in text.split(","))
+    values = {}
+    for s in settings:
+        name, _, text = s.partition("=")
+        if name not in types:
+            raise SystemExit("--set %s: no such knob (there are: %s)" % (name, ", ".join(types)))
+        if name == "fast_windows":
+            hd, _, w = text.partition(":")
+            values[name] = values.get(name, ()) + ((int(hd), ints(w)),)
+        elif types[name] is bool:
+            values[name] = text in ("", "1")
+        else:
+            values[name] = int(text) if types[name] is int else ints(text)
+    return Knobs(**values)
 
 
 def main():
@@ -1349,141 +1384,25 @@ def main():
     ap.add_argument("--hd", type=int, default=72, help="head dim of the schedule --table prints")
     ap.add_argument("--pv8", action="store_true", help="--table: the fp8 P.V variant")
     ap.add_argument("--qk8", action="store_true", help="--table: the fp8 QK^T + fp8 P.V variant (head_dim 128, layout 2; implies --pv8)")
-    ap.add_argument("--exp", default="", help="emit an EXPERIMENTAL body in place of the production one (never into the shipped tree: "
-                    "point --out at a scratch copy of csrc, see tools/make_ablated_libs.sh): safe = hazard-padded debug schedule | "
-                    "dmagapN[cC] = LDS-DMA items every N shadows | timing ablations joined by + (noexp nobar nodma nolds novalu "
-                    "nomfma norare nocvt nomax pv80: WRONG RESULTS)")
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "open_sora_amd", "csrc"))
-    ap.add_argument("--no-pv16", action="store_true", help="experiment: head_dim 72 with the P.V product on 32x32x16 MFMAs (96 padded rows) as in "
-                    "rounds 1-2; changes the V^T key order the kernel expects, so only for timing runs with matching wrappers")
-    ap.add_argument("--fast-windows", default="", help="experiment: hd:a0,a1,b0,b1 filler windows of the FAST body (layout NU = 2), e.g. 72:1,33,30,42")
-    ap.add_argument("--fast-exp", default="", help="experiment: like --exp, applied to the FAST bodies only")
-    ap.add_argument("--n2-budget", default="", help="experiment: m32,pv16,pv8 filler-cycle budgets of the 256-row bodies' MFMA shadows (production 24,9,60)")
-    ap.add_argument("--wide-exp", default="", help="experiment on the WIDE head_dim-72 body: gapN (LDS-DMA pieces every N trailing shadows) and / or "
-                    "win:a0,a1,b0,b1 (filler windows), joined by +")
+    ap.add_argument("--out", default=CSRC)
+    ap.add_argument("--set", action="append", default=[], metavar="NAME=VALUE", help="an EXPERIMENTAL schedule in place of the production "
+                    "one (never into the shipped tree: point --out at a scratch copy of csrc, see tools/make_attn_variants.sh): a field of "
+                    "Knobs, e.g. safe, dma_gap=2, pv16=13, wide_budget=13,30, fast_windows=128:2,40,38,56; repeatable")
     args = ap.parse_args()
-    if args.n2_budget:
-        N2_BUDGET.update(zip(("m32", "pv16", "pv8"), (int(x) for x in args.n2_budget.split(","))))
-    for tok in [t for t in args.wide_exp.split("+") if t]:
-        if tok.startswith("gap"):
-            WIDE_EXP["gap"] = int(tok[3:])
-        elif tok == "kwait4":
-            WIDE_EXP["kwait2"] = 4
-        elif tok in ("swapnop", "kwait1", "nodmafill"):
-            WIDE_EXP[{"swapnop": "swapnop", "kwait1": "kwait2", "nodmafill": "dmafill"}[tok]] = tok == "swapnop"
-        elif tok.startswith("vm"):
-            WIDE_EXP["vm"] = int(tok[2:])
-        elif tok.startswith("pretrail"):    # exponentials of the body's own phase-0 scores per trailing P.V shadow (0: none)
-            WIDE_EXP["pretrail"] = int(tok[8:])
-        elif tok.startswith("budget:"):     # filler-cycle budget of a P.V / QK^T shadow (round 5: the MFMA's own issue takes 4.4 cycles)
-            WIDE_EXP["budget"] = tuple(int(x) for x in tok[7:].split(","))
-        elif tok.startswith("win:"):
-            w_ = [int(x) for x in tok[4:].split(",")]
-            WIDE_EXP["win"] = w_ + [w_[3], w_[3]]
-    if args.fast_windows:
-        for spec_ in args.fast_windows.split(";"):
-            hd_, w_ = spec_.split(":")
-            w_ = [int(x) for x in w_.split(",")]
-            FAST_WINDOWS_OVERRIDE[(int(hd_), 2)] = w_ + [w_[3], w_[3]]
-    # shipped: the 4 waves x 64 rows layout (NU = 2) of both head dims, bf16 and fp8 P.V.  The 8 waves x 32 rows layout
-    # (NU = 1, head_dim 72) tied it in rounds 1-2 and stays a generator option (--table 1) without a shipped body.
-    layouts = [(72, 2, False, False), (128, 2, False, False), (72, 2, True, False), (128, 2, True, False), (128, 2, True, True)]
-    mk = lambda nu, hd, pv8, qk8=False: Layout(nu, hd, pv8, pv16=(hd == 72 and not pv8 and not args.no_pv16), qk8=qk8)
-    tagof = lambda hd, pv8, qk8=False: "%d%s" % (hd, "q8" if qk8 else ("p8" if pv8 else ""))
-    global DMAGAP, DMACOST
-    safe = args.exp == "safe"
-    gap = args.exp.startswith("dmagap")
-    ablate = frozenset() if (safe or gap or not args.exp) else frozenset(args.exp.split("+"))
-    if (args.exp or args.fast_windows or args.fast_exp or args.no_pv16 or args.wide_exp or args.n2_budget) and os.path.realpath(args.out) == os.path.realpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "open_sora_amd", "csrc")):
-        raise SystemExit("--exp bodies are experiments: give --out a scratch directory, not the shipped csrc")
+    knobs = parse_knobs(args.set)
     if args.table:
-        L = mk(args.table, args.hd, args.pv8 or args.qk8, args.qk8) if args.table == 2 else Layout(args.table, args.hd, args.pv8)
-        st = generate(L, False, frozenset())
-        row = []
-        for kind, text in st.table:
-            if kind in ("M", "F", "X", "Q"):
-                print("".join(row)); row = [kind + " "]
-            elif kind == "L":
-                print("".join(row)); row = []; print(text + ":")
-            else:
-                row.append({"x": "v"}.get(kind, kind))
-        print("".join(row))
+        pv8 = args.pv8 or args.qk8
+        L = Layout(args.table, args.hd, pv8, pv16=(args.table == 2 and args.hd == 72 and not pv8), qk8=args.qk8)
+        print_table(generate(L, knobs=knobs))
         return
-
-    def body(name, note, lines, labels):         # "@@" in a label -> a prefix that is unique per body and per emitted copy of it
-        write_body(os.path.join(args.out, name), "gen_attn_asm.py", note, [ln.replace("@@", labels) for ln in lines])
-
-    for hd, nu, pv8, qk8 in layouts:
-        L = mk(nu, hd, pv8, qk8)
-        DMAGAP, DMACOST = 1, 12
-        if gap:
-            spec = args.exp[len("dmagap"):].split("c")
-            DMAGAP, DMACOST = int(spec[0]), int(spec[1]) if len(spec) > 1 else 12
-        st = generate(L, safe, ablate)
-        DMAGAP, DMACOST = 1, 12
-        what = "production" if not args.exp else ("hazard-padded (debug)" if safe else ("schedule experiment " + args.exp if gap else
-                                                                                         "timing ablation " + "+".join(sorted(ablate))))
-        body("attention_asm%s_n%d_v0.inc" % (tagof(hd, pv8, qk8), nu), "head_dim %d%s, layout NU=%d: %s" %
-             (hd, ", fp8 QK^T and P.V" if qk8 else (", fp8 P.V" if pv8 else ""), nu, what), st.lines, "osk%sn%dv0_%%=" % (tagof(hd, pv8, qk8), nu))
-        if not pv8:   # the bounded / single-segment / whole-tile body of the same layout
-            fexp = args.fast_exp or args.exp
-            if fexp.startswith("dmagap"):
-                spec = fexp[len("dmagap"):].split("c")
-                DMAGAP, DMACOST = int(spec[0]), int(spec[1]) if len(spec) > 1 else 12
-            Lf = Layout(nu, hd, pv8, pv16=L.PV16, nom=(hd == 128))   # hd 128: the padding k-step is dropped too
-            stf = generate(Lf, safe, ablate, fast=True)
-            DMAGAP, DMACOST = 1, 12
-            body("attention_asm%s_n%d_f0.inc" % (tagof(hd, pv8), nu), "head_dim %d, layout NU=%d, FAST body (score bound, one "
-                 "segment of whole tiles): %s" % (hd, nu, what), stf.lines, "osk%sn%df0_%%=" % (tagof(hd, pv8), nu))
-    # the wide layout of head_dim 72 (4 query blocks per wave, 32-key sub-tiles): FAST body only
-    LW = LayoutW()
-    stw = generate_wide(LW, safe)
-    body("attention_asm72w_f0.inc", "head_dim 72, WIDE layout (4 waves x 128 query rows, one 32-key half per "
-         "body), FAST body: %s" % ("production" if not args.exp else "experiment " + args.exp), stw.lines, "osk72wf0_%=")
-    # register / operand contract for the wrapper
-    with open(os.path.join(args.out, "attention_asm_regs.inc"), "w") as f:
-        f.write(header("gen_attn_asm.py"))
-        f.write("#define OSK72W_CLOBBERS %s\n" % clobbers(LW.V_FIRST, LW.V_END - LW.V_FIRST, LW.A_END, S_FIRST, S_LAST))
-        f.write("#define OSK72W_A_CLOBBERS %s\n" % ", ".join('"a%d"' % i for i in range(0, LW.A_END)))
-        f.write("#define OSK72W_NSLOT %d\n" % LW.NSLOT)
-        # register map the wrapper binds as asm operands (acc_quads.h): Q fragment words of block u = AGPRs AQ(u) .. + 4 NKS,
-        # O^T of (u, 16-query block qb) = AGPRs 4 NDB (2 u + qb) .. (row block db, register i at + 4 db + i)
-        for u in range(LW.NUW):
-            f.write("#define OSK72W_AQ%d %d\n" % (u, LW.AQW(u, 0)))
-            for qb in range(2):
-                assert all(LW.AO16W(u, qb, db) == 4 * LW.G.NDB * (2 * u + qb) + 4 * db for db in range(LW.G.NDB))
-        f.write("#define OSK72W_AO_REGS %d\n" % (4 * LW.G.NDB * 2 * LW.NUW))
-        for hd, pv8, qk8 in sorted({(h, p8, q8) for h, _, p8, q8 in layouts}):
-            G = mk(2, hd, pv8, qk8).G
-            P = "OSK%s_" % tagof(hd, pv8, qk8).upper()
-            f.write("#define %sSMEM %d\n#define %sCONST_OFF %d\n" % (P, G.SMEM, P, G.CONST_OFF))
-            f.write("#define %sKTILE %d\n#define %sVTILE %d\n#define %sVOFF0 %d\n#define %sKOFF0 %d\n" % (P, G.KTILE, P, G.VTILE, P, G.VOFF[0], P, G.KOFF[0]))
-            f.write("#define %sNKS %d\n#define %sNDT %d\n#define %sNKD %d\n#define %sKIMG %d\n" % (P, G.NKS, P, G.NDT, P, G.NKD, P, G.KIMG))
-            if pv8:
-                f.write("#define %sRP %d\n#define %sNVD %d\n" % (P, G.RP, P, G.NVD))
-        for hd, nu, pv8, qk8 in layouts:
-            L = mk(nu, hd, pv8, qk8)
-            G = L.G
-            P = "OSK%sN%d_" % (tagof(hd, pv8, qk8).upper(), nu)
-            if L.PV16:
-                f.write("#define %sPV16 1\n#define OSK%s_NDB %d\n" % (P, tagof(hd, pv8).upper(), G.NDB))
-            f.write("#define %sCLOBBERS %s\n" % (P, clobbers(L.V_FIRST, L.V_END - L.V_FIRST, L.A_END, S_FIRST, S_LAST)))
-            f.write("#define %sA_CLOBBERS %s\n" % (P, ", ".join('"a%d"' % i for i in range(0, L.A_END))))
-            f.write("#define %sNSLOT %d\n" % (P, L.NSLOT))
-            if pv8:
-                f.write("#define %sNSLOT_V %d\n" % (P, L.NSLOT_V))
-            # register map the wrapper binds as asm operands (acc_quads.h): Q fragment words of block u = AGPRs AQ(u) .. + 4 NKS
-            for u in range(nu):
-                f.write("#define %sAQ%d %d\n" % (P, u, L.AQ(u, 0)))
-            if qk8:
-                f.write("#define %sA_END %d\n" % (P, L.A_END))
-            if L.PV16:   # O^T of (u, 16-query block qb) = AGPRs 4 NDB (2 u + qb) .. (row block db, register i at + 4 db + i)
-                assert all(L.AO16(u, qb, db) == 4 * G.NDB * (2 * u + qb) + 4 * db for u in range(nu) for qb in range(2) for db in range(G.NDB))
-                f.write("#define %sAO_REGS %d\n" % (P, 4 * G.NDB * 2 * nu))
-                continue
-            assert all(L.AO(u, d) == 16 * (u * G.NDT + d) for u in range(nu) for d in range(G.NDT))   # O^T row tile (u, d): 16 registers
-            f.write("#define %sAO_REGS %d\n" % (P, 16 * G.NDT * nu))
-
-
+    if knobs != Knobs() and os.path.realpath(args.out) == os.path.realpath(CSRC):
+        raise SystemExit("--set bodies are experiments: give --out a scratch directory, not the shipped csrc")
+    rows = shipped()
+    for name, note, labels, L, fast in rows:
+        wide = isinstance(L, LayoutW)
+        st = generate_wide(L, knobs) if wide else generate(L, fast, knobs)
+        write_body(os.path.join(args.out, name), "gen_attn_asm.py", "%s: %s" % (note, variant_note(knobs, wide)),
+                   [ln.replace("@@", labels) for ln in st.lines])
+    write_regs(args.out, rows)
 if __name__ == "__main__":
     main()

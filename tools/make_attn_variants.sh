@@ -1,6 +1,6 @@
 #!/bin/bash
-# A/B libraries for attention schedule experiments: scratch copy of csrc, generator options, only the attention objects rebuilt.
-#   VARIANTS="name|generator args;name2|args2" bash tools/make_attn_variants.sh   -> tools/lib/libosk_attn_<name>.so
+# A/B libraries for attention schedule experiments: scratch copy of csrc, generator knobs (--set name=value), only the attention objects rebuilt.
+#   VARIANTS="gap2|--set dma_gap=2;budget|--set m32=30 --set pv16=13" bash tools/make_attn_variants.sh   -> tools/lib/libosk_attn_<name>.so
 set -e
 cd "$(dirname "$0")/.."
 OBJ=open_sora_amd/lib/obj
