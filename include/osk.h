@@ -481,6 +481,16 @@ const char* osk_attention_body_name(int hd, int n_seg, int seg_len, float score_
 int osk_cfg_euler_bf16(const void* pred, int64_t n, const void* x, void* x_out,
                        float g_txt, float g_img, const float* g_img_vec, float dt, void* stream);
 
+/* ---- the same combine + Euler step over the nb leading branches of the triple, for sampler steps that did not run the
+ * branches their guidance cancels (replaces opensora/utils/sampling.py:208-222, which always combines three):
+ *   nb 3:  v = u2 + g_img*(u - u2) + g_txt*(c - u)     the arithmetic of osk_cfg_euler_bf16, same operation order, same bits
+ *   nb 2:  v = u + g_txt*(c - u)                        branches 2 and 3 identical (u2 == u); g_img, g_img_vec ignored
+ *   nb 1:  v = c                                        both guidances 1.0; g_txt, g_img, g_img_vec ignored
+ *   x_out = x + dt * v                                  f32 math, one rounding; x_out == x (in place) is allowed
+ * pred bf16 [nb, n]: exactly nb * n elements are read.  Another nb, a NULL pred / x / x_out or n % 8 != 0: OSK_EINVAL, no launch. */
+int osk_cfg_euler_nb_bf16(const void* pred, int nb, int64_t n, const void* x, void* x_out,
+                          float g_txt, float g_img, const float* g_img_vec, float dt, void* stream);
+
 /* ---- strided row copy: dst[j, b, l, 0:C] = src[j, b, l, 0:C] (bf16; element strides; src_batch_stride 0 broadcasts one item).
  * replaces the host-side tensor glue of a denoise step: `torch.cat([img, img, img])` of the CFG triple
  * (opensora/utils/sampling.py:196-201), the operand assembly in front of img_in / cond_in (opensora/models/mmdit/model.py:170-176),

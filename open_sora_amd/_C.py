@@ -72,6 +72,7 @@ SIGNATURES = {
     "osk_attention_launch_shape": [_i32, _i32, _i32, _i32, _i32, _i32, _f32, _i64, C.POINTER(_i32)],
     "osk_attention_rows_override": [_i32],
     "osk_cfg_euler_bf16": [_vp, _i64, _vp, _vp, _f32, _f32, _vp, _f32, _vp],
+    "osk_cfg_euler_nb_bf16": [_vp, _i32, _i64, _vp, _vp, _f32, _f32, _vp, _f32, _vp],
     "osk_copy_rows_bf16": [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp],
     "osk_causal_conv3d_ndhwc_bf16": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32,
                                      _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp],
@@ -851,6 +852,20 @@ def cfg_euler(pred: torch.Tensor, x: torch.Tensor, x_out: torch.Tensor, g_txt: f
         f"osk_cfg_euler_bf16 reads and writes bf16; got {pred.dtype}, {x.dtype}, {x_out.dtype}"
     _check(lib.osk_cfg_euler_bf16(pred.data_ptr(), n, x.data_ptr(), x_out.data_ptr(), g_txt, g_img,
                                   _p(g_img_vec), dt, _stream()), "osk_cfg_euler_bf16")
+    return x_out
+
+
+def cfg_euler_nb(pred: torch.Tensor, nb: int, x: torch.Tensor, x_out: torch.Tensor, g_txt: float, g_img: float, dt: float,
+                 g_img_vec=None):
+    """pred bf16 contiguous, its first nb chunks of x.numel() elements = the branches that ran (cond[, uncond[, uncond_2]]);
+    x, x_out bf16 [...] contiguous.  nb outside 1..3 is refused by the library (RuntimeError), nothing is launched."""
+    n = x.numel()
+    assert pred.numel() >= max(nb, 1) * n and pred.is_contiguous() and x.is_contiguous() and x_out.is_contiguous()
+    assert pred.dtype == x.dtype == x_out.dtype == torch.bfloat16, \
+        f"osk_cfg_euler_nb_bf16 reads and writes bf16; got {pred.dtype}, {x.dtype}, {x_out.dtype}"
+    assert g_img_vec is None or (g_img_vec.dtype == torch.float32 and g_img_vec.numel() == n and g_img_vec.is_contiguous())
+    _check(lib.osk_cfg_euler_nb_bf16(pred.data_ptr(), nb, n, x.data_ptr(), x_out.data_ptr(), g_txt, g_img,
+                                     _p(g_img_vec), dt, _stream()), "osk_cfg_euler_nb_bf16")
     return x_out
 
 

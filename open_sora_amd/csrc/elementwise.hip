@@ -794,6 +794,52 @@ extern "C" int osk_cfg_euler_bf16(const void* pred, int64_t n, const void* x, vo
 }
 
 // =============================================================================================
+// CFG combine + Euler update over the NB leading branches of the triple (the sampler's pruned steps: a step whose guidance
+// cancels a branch does not run it).  NB 3: the arithmetic of cfg_euler_kernel in its operation order; NB 2 (branches 2 and 3
+// identical): v = u + g_txt (c - u); NB 1 (both guidances 1.0): v = c.  Bytes: NB pred reads + x read + x write = 2 NB + 4 B per
+// element; nothing behind pred[NB n) is read.
+// =============================================================================================
+template <int NB>
+__global__ void __launch_bounds__(256) cfg_euler_nb_kernel(const unsigned short* __restrict__ pred, int64_t n,
+                                                           const unsigned short* __restrict__ x,
+                                                           unsigned short* __restrict__ xo, float g_txt, float g_img,
+                                                           const float* __restrict__ g_img_vec, float dt) {
+  const int64_t nchunk = n >> 3;
+  for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < nchunk; c += (int64_t)gridDim.x * 256) {
+    float pc[8], pu[8], p2[8], xv[8], o[8];
+    unpack8(*reinterpret_cast<const uint4*>(pred + c * 8), pc);
+    if (NB >= 2) unpack8(*reinterpret_cast<const uint4*>(pred + n + c * 8), pu);
+    if (NB >= 3) unpack8(*reinterpret_cast<const uint4*>(pred + 2 * n + c * 8), p2);
+    unpack8(*reinterpret_cast<const uint4*>(x + c * 8), xv);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float v;
+      if (NB == 3) {
+        const float gi = g_img_vec ? g_img_vec[c * 8 + j] : g_img;
+        v = p2[j] + gi * (pu[j] - p2[j]) + g_txt * (pc[j] - pu[j]);
+      } else if (NB == 2) {
+        v = pu[j] + g_txt * (pc[j] - pu[j]);
+      } else {
+        v = pc[j];
+      }
+      o[j] = xv[j] + dt * v;
+    }
+    *reinterpret_cast<uint4*>(xo + c * 8) = pack8(o);
+  }
+}
+
+extern "C" int osk_cfg_euler_nb_bf16(const void* pred, int nb, int64_t n, const void* x, void* x_out, float g_txt,
+                                     float g_img, const float* g_img_vec, float dt, void* stream) {
+  if (!pred || !x || !x_out || nb < 1 || nb > 3 || n <= 0 || (n & 7)) return OSK_EINVAL;
+  int64_t blocks = (n / 8 + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  auto* kern = nb == 3 ? cfg_euler_nb_kernel<3> : nb == 2 ? cfg_euler_nb_kernel<2> : cfg_euler_nb_kernel<1>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)pred, n,
+                     (const unsigned short*)x, (unsigned short*)x_out, g_txt, g_img, g_img_vec, dt);
+  return (int)hipGetLastError();
+}
+
+// =============================================================================================
 // Strided row copy (bf16): dst[j, b, l, 0:C] = src[j, b, l, 0:C] with independent chunk / batch / row strides on both sides; a
 // source batch stride of 0 broadcasts one item over the batch.  The host glue of the denoise step without a torch kernel:
 // sampler: latents -> the CFG triple's input; model: img / cond -> the K-padded img_in operand (sampling.py:196-201,

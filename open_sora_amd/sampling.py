@@ -94,6 +94,42 @@ def prepare_ids(bs: int, t: int, h: int, w: int, n_txt: int, device, dtype, patc
 _SIDE_STREAMS: dict = {}   # device -> the capture stream of denoise(hip_graph=True)
 
 
+def cfg_branch_counts(n_steps: int, guidance: float, guidance_img: float, text_osci: bool, image_osci: bool,
+                      scale_temporal_osci: bool, dup23: bool) -> list[int]:
+    """How many leading branches of the CFG triple (cond | uncond | uncond_2) each step of I2VDenoiser's loop needs for
+    v = u2 + g_img (u - u2) + g_txt (c - u) (sampling.py:216), per step:
+        g_img == 1.0 without a temporal ramp, or u2 == u (dup23: branches 2 and 3 get identical inputs)  ->  v = u + g_txt (c - u): 2
+        ... and g_txt == 1.0 as well                                                                     ->  v = c:                 1
+    The guidances are the loop's own per-step values, compared with 1.0 exactly (get_oscillation_gs returns the literal)."""
+    counts = []
+    for i in range(n_steps):
+        text_gs = get_oscillation_gs(guidance, i) if text_osci else guidance
+        image_gs = get_oscillation_gs(guidance_img, i) if image_osci else guidance_img
+        ramp = image_gs > 1.0 and scale_temporal_osci
+        img_one = not ramp and image_gs == 1.0
+        if img_one or dup23:
+            counts.append(1 if text_gs == 1.0 else 2)
+        else:
+            counts.append(3)
+    return counts
+
+
+def _branches_2_and_3_identical(masks: Tensor, masked_ref: Tensor, kwargs: dict, n: int) -> bool:
+    """dup23 of cfg_branch_counts, from the tensors themselves (never from the prompts): no image condition at all -- cond3's
+    third block, zeros, then equals its second -- and every tripled model input equal between blocks 2 and 3.  All comparisons
+    reduce on the device into one flag: ONE host synchronisation, before step 0."""
+    flags = [~masks.any(), ~masked_ref.any()]
+    for v in kwargs.values():
+        if torch.is_tensor(v) and v.ndim >= 1 and v.shape[0] == 3 * n:
+            flags.append((v[n:2 * n] == v[2 * n:]).all())
+    return bool(torch.stack(flags).all())
+
+
+def _prune_default() -> bool:
+    """OSK_CFG_PRUNE, read at call time (the reference's prepare_api / api_fn reach denoise() without a keyword for it)"""
+    return os.environ.get("OSK_CFG_PRUNE", "") not in ("", "0")
+
+
 class I2VDenoiser:
     """sampling.py:158-245.  `denoise(model, img=..., timesteps=[...], guidance=..., guidance_img=..., masks=...,
     masked_ref=..., img_ids=..., txt=..., txt_ids=..., y_vec=..., [text_osci, image_osci, scale_temporal_osci,
@@ -104,7 +140,15 @@ class I2VDenoiser:
     latent triple and the timestep vector -- live in fixed buffers).  Same results bit for bit.  Measured on this host:
     no gain at either end -- the XL step's ~540 launches hide behind 150 ms of kernels, and even the S model's 2.6 ms
     forward replays in the same 2.6 ms (`bench.py`: cpu_baseline.cfg1.gpu_hipgraph_ms) -- so it is off by default and
-    meant for hosts whose Python dispatch is slower than the GPU."""
+    meant for hosts whose Python dispatch is slower than the GPU.
+
+    Not in the reference either: `cfg_prune=True` (default: the environment variable OSK_CFG_PRUNE, read at call time) runs at every
+    step only the branches of the triple that step's guidance uses (cfg_branch_counts): one where both guidances are 1.0 -- 20 of
+    the 50 steps of the shipped oscillating schedule -- and two throughout when there is no image condition and the two negative
+    prompts are the same tensor rows (text-to-video).  The skipped branches cancel in sampling.py:216 exactly in real arithmetic; in
+    bf16 the result differs from the triple's by rounding only (tests/test_gpu_cfg_prune.py holds it to the project's parity rule).
+    Off, the loop is the one above, launch for launch.  With hip_graph, one graph per branch count in use.  `last_branch_counts`
+    holds the counts of the last run.  Cost: one activation workspace set per batch size in use instead of one."""
 
     def denoise(self, model, **kwargs) -> Tensor:
         img = kwargs.pop("img")
@@ -119,9 +163,18 @@ class I2VDenoiser:
         scale_temporal_osci = kwargs.pop("scale_temporal_osci", False)
         patch_size = kwargs.pop("patch_size", 2)
         hip_graph = bool(kwargs.pop("hip_graph", False))
+        cfg_prune = kwargs.pop("cfg_prune", None)
+        cfg_prune = _prune_default() if cfg_prune is None else bool(cfg_prune)
 
         n3 = img.shape[0]
         n = n3 // 3
+        counts = [3] * (len(timesteps) - 1)
+        if cfg_prune:
+            counts = cfg_branch_counts(len(timesteps) - 1, guidance, guidance_img, text_osci, image_osci, scale_temporal_osci,
+                                       _branches_2_and_3_identical(masks, masked_ref, kwargs, n))
+        self.last_branch_counts = counts
+        loop = self._loop_pruned if cfg_prune else self._loop
+        tail = (counts,) if cfg_prune else ()
         dev, dt = img.device, img.dtype
         guidance_vec = torch.full((n3,), guidance, device=dev, dtype=dt)
         b, c, t, w_, h_ = masked_ref.size()
@@ -146,12 +199,12 @@ class I2VDenoiser:
                 side = _SIDE_STREAMS[str(dev)] = torch.cuda.Stream(dev)
             side.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(side):
-                out = self._loop(model, kwargs, x, x_next, img3, t_vec, cond3, guidance_vec, timesteps, guidance, guidance_img,
-                                 text_osci, image_osci, scale_temporal_osci, patch_size, b, c, t, h_, w_, dev, True, side)
+                out = loop(model, kwargs, x, x_next, img3, t_vec, cond3, guidance_vec, timesteps, guidance, guidance_img,
+                           text_osci, image_osci, scale_temporal_osci, patch_size, b, c, t, h_, w_, dev, True, side, *tail)
             torch.cuda.current_stream(dev).wait_stream(side)
             return out.to(dt)
-        return self._loop(model, kwargs, x, x_next, img3, t_vec, cond3, guidance_vec, timesteps, guidance, guidance_img, text_osci,
-                          image_osci, scale_temporal_osci, patch_size, b, c, t, h_, w_, dev, False, None).to(dt)
+        return loop(model, kwargs, x, x_next, img3, t_vec, cond3, guidance_vec, timesteps, guidance, guidance_img, text_osci,
+                    image_osci, scale_temporal_osci, patch_size, b, c, t, h_, w_, dev, False, None, *tail).to(dt)
 
     @staticmethod
     def _loop(model, kwargs, x, x_next, img3, t_vec, cond3, guidance_vec, timesteps, guidance, guidance_img, text_osci, image_osci,
@@ -187,6 +240,59 @@ class I2VDenoiser:
             x, x_next = x_next, x
             if graph is not None:
                 pred = pred_g                     # from now on the forward's output is the captured tensor
+        return x
+
+    @staticmethod
+    def _loop_pruned(model, kwargs, x, x_next, img3, t_vec, cond3, guidance_vec, timesteps, guidance, guidance_img, text_osci,
+                     image_osci, scale_temporal_osci, patch_size, b, c, t, h_, w_, dev, hip_graph, side, counts):
+        """_loop with cfg_prune: step i runs the model on the counts[i] leading branches only (cfg_branch_counts) and combines them
+        with osk_cfg_euler_nb_bf16.  The kept branches are a prefix of every tripled tensor, so a branch count's inputs are views of
+        the triple's buffers made ONCE: the same tensor objects every step (the model's position-embedding memo keeps hitting), at
+        fixed addresses (a captured graph reads them)."""
+        n = x.shape[0]
+        inputs = {}    # branch count -> the model's keyword arguments for it
+        graphs = {}    # branch count -> (hipGraph of the forward at that batch, its output tensor)
+        for i, (t_curr, t_prev) in enumerate(zip(timesteps[:-1], timesteps[1:])):
+            nb = counts[i]
+            kw = inputs.get(nb)
+            if kw is None:
+                m = nb * n
+                kw = inputs[nb] = {k: (v[:m] if torch.is_tensor(v) and v.ndim >= 1 and v.shape[0] == 3 * n else v) for k, v in kwargs.items()}
+                kw.update(img=img3[:m], cond=cond3[:m], timesteps=t_vec[:m], guidance=guidance_vec[:m])
+            t_vec.fill_(t_curr)
+            dst = kw["img"]
+            if _ops().copy_rows_ok(x, dst[:n]):
+                for j in ([None] if n == 1 else range(nb)):
+                    _ops().copy_rows(x, dst if j is None else dst[j * n:(j + 1) * n])
+            else:
+                dst.view(nb, *x.shape).copy_(x.unsqueeze(0).expand(nb, *x.shape))
+            if nb in graphs:
+                graphs[nb][0].replay()            # writes the captured prediction of this branch count
+                pred = graphs[nb][1]
+            else:
+                pred = model(**kw)
+                if hip_graph and nb in counts[i + 1:]:
+                    # as step 0 of _loop: the first step of a branch count ran eagerly (it built that batch size's workspaces), the
+                    # same call is captured for the later ones -- one graph per count in use, all on the one side stream, no
+                    # parallel capture branches.  A loop uses at most three batch sizes and mmdit._workspace keeps four geometries
+                    # per model, least recently INSERTED first out (a replay does not touch the cache): at most two sets are
+                    # inserted behind the first one during a loop, so no set a live graph replays into is evicted.  The same
+                    # count holds for seqpar's exchange buffers (SeqPar.MAX_GEOMETRIES = 4, one set per batch size and forward).
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g, stream=side):
+                        pred_g = model(**kw)
+                    graphs[nb] = (g, pred_g)
+            text_gs = get_oscillation_gs(guidance, i) if text_osci else guidance
+            image_gs = get_oscillation_gs(guidance_img, i) if image_osci else guidance_img
+            gvec = None
+            if nb == 3 and image_gs > 1.0 and scale_temporal_osci:
+                upper = torch.linspace(image_gs, 1.0, len(timesteps))[i]
+                ramp = torch.linspace(1.0, float(upper), t)[None, None, :, None, None].repeat(b, c, 1, h_, w_)
+                gvec = pack(ramp, patch_size=patch_size).to(dev, torch.float32).contiguous()
+                image_gs = 1.0
+            _ops().cfg_euler_nb(pred.to(torch.bfloat16).contiguous(), nb, x, x_next, float(text_gs), float(image_gs),
+                                float(t_prev - t_curr), gvec)
+            x, x_next = x_next, x
         return x
 
     def prepare_guidance(self, text: list, optional_models: dict, device, dtype, **kwargs):

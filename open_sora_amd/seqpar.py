@@ -201,7 +201,9 @@ class SeqPar:
         return Lloc, Lloc
 
     # ------------------------------------------------------------------ K/V exchange
-    MAX_GEOMETRIES = 4   # exchange-buffer sets kept (least recently used first out)
+    # exchange-buffer sets kept (least recently used first out).  A forward uses one set; the sampler's cfg_prune loop alternates
+    # at most three batch sizes = three sets, so none is evicted under it (tests/test_cfg_prune_host.py counts)
+    MAX_GEOMETRIES = 4
     kv_qk8 = True        # gather_kv_start takes qk8 (mmdit._sp_qk8 asks before it passes the argument)
     MAX_KV_CHUNKS = 8    # parts osk_attention_merge_bf16 takes
 
