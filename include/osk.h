@@ -435,6 +435,39 @@ int osk_attention_fwd_ragged_bf16(const void* q, int64_t q_batch_stride, int64_t
 int osk_attention_merge_into_bf16(void* out, int64_t o_batch_stride, int64_t o_row_stride, float* lse, const float* o_b,
                                   const float* lse_b, int B, int H, int Lq, int hd, void* stream);
 
+/* ---- frame-window attention: every 256-row query block sees an always-attended key prefix and ONE run of 64-key tiles of the rest
+ * (opt-in; an additive entry, the version stays 2).  It replaces nothing in the reference: opensora/models/mmdit/math.py:22-36 lets
+ * every query see every key.  It is what a video DiT's sliding-window option computes when text stays global and an image query
+ * keeps the frames around its own, stated as a mask and exact with respect to that mask:
+ *   keys [0, n_prefix)   the prefix (text): seen by every query.  n_prefix % 64 == 0, 0 <= n_prefix < Lk
+ *   keys [n_prefix, Lk)  the body; table tile j = body keys 64 j .. 64 j + 63 (the last tile may be ragged)
+ *   windows              DEVICE int32 [n_windows][2] = (first tile, tile count) per 256-row query block, n_windows = ceil(Lq / 256):
+ *                        rows 256 i .. 256 i + 255 see the prefix and body tiles [first, first + count) and NOTHING else.
+ *                        The kernel clamps a row to 0 <= first < tiles, 1 <= count <= tiles - first: a bad table gives wrong
+ *                        numbers, never an out-of-range address (open_sora_amd/_C.py validates the host copy and raises).
+ * q, k, out, lse, scale, q_prescaled, kv_batches, score_bound: as osk_attention_fwd_bounded_bf16 with ONE key segment of Lk keys
+ * (k bf16 [Bkv, Lk, H*hd] view; vt = osk_v_transpose_bf16 of all Lk keys, [Bkv, H, hd, round_up(Lk, 64)]); the bound covers prefix
+ * and body alike and selects the FAST body of both launches (0: the general body).  The call enqueues, on `stream`:
+ *   A  the body as a key axis of its own (K, V^T advanced by n_prefix keys) with the table, finished rows into out / lse,
+ *   B  the prefix alone into f32 partials in the workspace (every work unit, one part),
+ *   M  one in-place merge of B's partial into A's rows by their log-sum-exp (osk_attention_merge_into_bf16's kernel).
+ * n_prefix == 0: launch A alone, workspace may be NULL; with full windows the result is bit-identical to osk_attention_fwd_bf16.
+ * n_prefix > 0: out 16-byte aligned with strides multiples of 8, workspace required -- osk_attention_window_workspace_bytes(B, H,
+ * Lq, hd) is always enough (f32 partials + launch A's lse when the caller keeps none).
+ * OSK_EINVAL: n_windows != ceil(Lq / 256), NULL / misaligned table, n_prefix not a multiple of 64 or >= Lk, missing / short
+ * workspace with n_prefix > 0, negative or NaN score_bound.  hd in {64, 72, 128} (else OSK_EUNSUPPORTED).  bf16 operands only.
+ * No allocation, no memset, no host synchronisation: capturable in a hipGraph.
+ * Cost: work units are always 256 rows (no wide head_dim-72 layout) and the grid's last round is not split along the keys; a
+ * unit's time follows its tile count, so the launch ends with its longest windows.  On top of launch A: launch B walks n_prefix
+ * keys per unit and the merge moves 8 bytes per output element.  Measured: profiles/attn_window.md. */
+int64_t osk_attention_window_workspace_bytes(int B, int H, int Lq, int hd);
+int osk_attention_fwd_window_bf16(const void* q, int64_t q_batch_stride, int64_t q_row_stride,
+                                  const void* k, int64_t k_batch_stride, int64_t k_row_stride, const void* vt,
+                                  void* out, int64_t o_batch_stride, int64_t o_row_stride, float* lse,
+                                  int B, int H, int Lq, int Lk, int n_prefix, int hd, float scale, int q_prescaled,
+                                  int kv_batches, float score_bound, const int32_t* windows, int n_windows,
+                                  void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- short-sequence attention with an optional ALiBi bias (the STDiT-generation block's temporal
  * self-attention over T <= 64 frames, B * H * W independent sequences, "RoPE/ALiBi" in BASELINE.json's north_star).  The mounted
  * v2.0 reference passes alibi_slopes=None at every flash-attn call site (opensora/models/mmdit/math.py:22-36), so this entry is

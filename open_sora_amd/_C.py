@@ -58,6 +58,9 @@ SIGNATURES = {
     "osk_attention_fwd_ragged_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp,
                                       _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _f32, _i32, _vp, _i64, _vp],
     "osk_attention_merge_into_bf16": [_vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
+    "osk_attention_window_workspace_bytes": [_i32, _i32, _i32, _i32],
+    "osk_attention_fwd_window_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
+                                      _f32, _i32, _i32, _f32, _vp, _i32, _vp, _i64, _vp],
     "osk_rownorm2_max_bf16": [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp],
     "osk_attention_workspace_bytes": [],
     "osk_v_scale_fp8": [_vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _vp],
@@ -119,7 +122,7 @@ def _load() -> C.CDLL:
         fn.argtypes = argtypes
         fn.restype = (C.c_char_p if name in ("osk_arch", "osk_attention_kernel_name", "osk_attention_body_name") else
                       _i64 if name in ("osk_attention_workspace_bytes", "osk_attention_hd512_workspace_bytes",
-                                       "osk_attention_ragged_workspace_bytes") else _i32)
+                                       "osk_attention_ragged_workspace_bytes", "osk_attention_window_workspace_bytes") else _i32)
     if lib.osk_abi_version() != 2:
         raise ImportError("libosk_hip.so ABI version mismatch")
     return lib
@@ -629,6 +632,92 @@ def attention_fwd_ragged(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out
                                                  _p(lse), B, H, Lq, n_seg, seg_len, last_seg_len, hd, scale, int(q_prescaled), kv_batches,
                                                  float(score_bound), mode, workspace.data_ptr(), workspace.numel(), _stream()),
                "osk_attention_fwd_ragged_bf16")
+    return out
+
+
+def attention_window_workspace_bytes(B: int, H: int, Lq: int, hd: int) -> int:
+    """bytes attention_fwd_window needs for these query dimensions (a caller that keeps a buffer of its own: mmdit's workspaces)"""
+    return int(lib.osk_attention_window_workspace_bytes(B, H, Lq, hd))
+
+
+def attention_window_workspace(B: int, H: int, Lq: int, hd: int, device) -> torch.Tensor:
+    """workspace of attention_fwd_window for these query dimensions, one per (device, stream) like attention_workspace(): the f32
+    partials of the prefix launch and launch A's lse.  Grows to the largest request."""
+    dev = torch.device(device)
+    key = ("window", str(dev), torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0)
+    need = lib.osk_attention_window_workspace_bytes(B, H, Lq, hd)
+    ws = _ATTN_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _ATTN_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+    return ws
+
+
+def check_window_table(windows: torch.Tensor, Lq: int, Lk: int, n_prefix: int) -> None:
+    """ValueError unless `windows` is a host int32 [ceil(Lq / 256), 2] table of (first tile, tile count) whose every row lies
+    inside the ceil((Lk - n_prefix) / 64) tiles of the body.  (The kernel clamps what it reads; a table it would have to clamp is a
+    host bug and is refused here.)"""
+    if not (isinstance(windows, torch.Tensor) and windows.device.type == "cpu" and windows.dtype == torch.int32):
+        raise ValueError("windows: a host (CPU) int32 tensor is expected")
+    if n_prefix < 0 or n_prefix % 64 or n_prefix >= Lk:
+        raise ValueError(f"n_prefix = {n_prefix}: a multiple of 64 in [0, Lk = {Lk}) is expected")
+    nqb, tiles = (Lq + 255) // 256, (Lk - n_prefix + 63) // 64
+    if windows.dim() != 2 or tuple(windows.shape) != (nqb, 2):
+        raise ValueError(f"windows: shape {tuple(windows.shape)}, expected ({nqb}, 2) = one row per 256 query rows")
+    first, n = windows[:, 0], windows[:, 1]
+    if bool((first < 0).any()):
+        raise ValueError("windows: a negative first tile")
+    if bool((n < 1).any()):
+        raise ValueError("windows: an empty range (tile count < 1)")
+    if bool((first.long() + n.long() > tiles).any()):
+        raise ValueError(f"windows: a range ends past the body's {tiles} tiles")
+
+
+_WINDOW_DEV: dict = {}
+
+
+def _window_on_device(windows: torch.Tensor, device) -> torch.Tensor:
+    """the device copy of a validated host table, uploaded once per (content, device) and kept: a call inside a captured region
+    finds it here (upload the table by one call outside the capture first -- MMDiTModel does)."""
+    c = windows.contiguous()
+    key = (str(torch.device(device)), tuple(c.shape), c.numpy().tobytes())
+    dev = _WINDOW_DEV.get(key)
+    if dev is None:
+        if torch.device(device).type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("attention_fwd_window: this table was never uploaded; call once outside the captured region first")
+        while len(_WINDOW_DEV) >= 16:
+            _WINDOW_DEV.pop(next(iter(_WINDOW_DEV)))
+        dev = _WINDOW_DEV[key] = c.to(device)
+    return dev
+
+
+def attention_fwd_window(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Tensor, H: int, hd: int, scale: float, *,
+                         n_prefix: int, windows: torch.Tensor, lse=None, q_prescaled: bool = False, kv_batches: int = 0,
+                         score_bound: float = 0.0, workspace: torch.Tensor | None = None):
+    """attention in which the 256-row query block i sees keys [0, n_prefix) and the 64-key tiles windows[i] = (first, count) of the
+    body keys [n_prefix, Lk), nothing else (osk_attention_fwd_window_bf16).  q, k, vt, out, lse, score_bound as attention_fwd with
+    one key segment: k bf16 [Bkv, Lk, H*hd] view, vt = v_transpose of all Lk keys.  windows: HOST int32 [ceil(Lq / 256), 2],
+    validated here (ValueError) and uploaded once per content.  workspace: from attention_window_workspace(); needed when
+    n_prefix > 0 (taken from there when None)."""
+    assert q.dim() == 3 and out.dim() == 3 and q.shape == out.shape and q.shape[2] == H * hd, (q.shape, out.shape, H, hd)
+    assert q.dtype == torch.bfloat16 and k.dtype == torch.bfloat16 and vt.dtype == torch.bfloat16 and out.dtype == torch.bfloat16
+    assert k.dim() == 3 and k.shape[2] == H * hd and q.stride(2) == 1 and k.stride(2) == 1 and out.stride(2) == 1, (k.shape, q.stride(), k.stride())
+    B, Lq, _ = q.shape
+    Lk = k.shape[1]
+    check_window_table(windows, Lq, Lk, n_prefix)
+    assert vt.is_contiguous() and vt.shape[-1] == (Lk + 63) // 64 * 64 and vt.shape[-2] == hd, (vt.shape, Lk, hd)
+    if lse is not None:
+        assert lse.dtype == torch.float32 and lse.is_contiguous() and tuple(lse.shape) == (B, H, Lq), (lse.dtype, lse.shape)
+    if n_prefix > 0 and workspace is None:
+        workspace = attention_window_workspace(B, H, Lq, hd, q.device)
+    win = _window_on_device(windows, q.device)
+    if CHECK_SCORE_BOUND and score_bound > 0 and not torch.cuda.is_current_stream_capturing():
+        _assert_score_bound(q, k, H, hd, scale, 1, Lk, 0, q_prescaled, kv_batches, score_bound)
+    with _attn_prof():
+        _check(lib.osk_attention_fwd_window_bf16(q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1),
+                                                 vt.data_ptr(), out.data_ptr(), out.stride(0), out.stride(1), _p(lse), B, H, Lq, Lk,
+                                                 n_prefix, hd, scale, int(q_prescaled), kv_batches, float(score_bound), win.data_ptr(),
+                                                 win.shape[0], _p(workspace), 0 if workspace is None else workspace.numel(), _stream()),
+               "osk_attention_fwd_window_bf16")
     return out
 
 

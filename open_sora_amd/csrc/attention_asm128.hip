@@ -32,7 +32,7 @@ __global__ void __launch_bounds__(256, 1) attn_asm128_kernel(const AttnParams p)
   lds_ones_rows<OSK128_VOFF0, OSK128_VTILE, HD>(smem, w.tid);
   // ragged last key tile of a segment: see attention_asm72.hip (clamped K rows + validity-mask ones row)
   const int last_valid = p.seg_len - (p.tps - 1) * 64;
-  const KeyPart kp = key_part(p, w.tail, w.part, last_valid < 64);   // the whole key axis, or one part of a split tail unit
+  const KeyPart kp = key_part(p, w.tail, w.part, w.qb, last_valid < 64);   // the whole key axis, or one part of a split tail unit
   const bool ragged = kp.ragged;
   unsigned maskval = 0;
   if (lane < 32) {

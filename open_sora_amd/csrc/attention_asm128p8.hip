@@ -35,7 +35,7 @@ __global__ void __launch_bounds__(256, 1) attn_asm128p8_kernel(const AttnParams 
   // ragged last key tile of a segment: K rows past the segment re-fetch its last key (finite scores); the key-validity
   // row of V^T comes baked from osk_v_transpose_fp8
   const int last_valid = p.seg_len - (p.tps - 1) * 64;
-  const KeyPart kp = key_part(p, w.tail, w.part, last_valid < 64);   // the whole key axis, or one part of a split tail unit
+  const KeyPart kp = key_part(p, w.tail, w.part, w.qb, last_valid < 64);   // the whole key axis, or one part of a split tail unit
   const bool ragged = kp.ragged;
   __syncthreads();
 

@@ -50,7 +50,7 @@ __global__ void __launch_bounds__(256, 1) attn_asm72_kernel(const AttnParams p) 
   // scores), V^T is zero there (osk_v_transpose_bf16 pads), and the tile's ones row becomes a validity mask so the
   // duplicates do not count in the softmax denominator.  The mask is in the V^T tile's baked key order.
   const int last_valid = p.seg_len - (p.tps - 1) * 64;   // keys in the last tile of a segment (1..64)
-  const KeyPart kp = key_part(p, w.tail, w.part, last_valid < 64);   // the whole key axis, or one part of a split tail unit
+  const KeyPart kp = key_part(p, w.tail, w.part, w.qb, last_valid < 64);   // the whole key axis, or one part of a split tail unit
   const bool ragged = kp.ragged;
   const unsigned maskval = ragged_mask72(lane, last_valid);
   lds_mask_first_tile<OSK72_VOFF0, HDL>(smem, w.tid, kp, maskval);

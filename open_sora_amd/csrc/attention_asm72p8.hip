@@ -29,7 +29,7 @@ __global__ void __launch_bounds__(NU == 2 ? 256 : 512, NU == 2 ? 1 : 2) attn_asm
   // ragged last key tile of a segment: K rows past the segment re-fetch its last key (finite scores); the key-validity
   // row of V^T comes baked from osk_v_transpose_fp8
   const int last_valid = p.seg_len - (p.tps - 1) * 64;
-  const KeyPart kp = key_part(p, w.tail, w.part, last_valid < 64);
+  const KeyPart kp = key_part(p, w.tail, w.part, w.qb, last_valid < 64);
   const bool ragged = kp.ragged;
   __syncthreads();
 

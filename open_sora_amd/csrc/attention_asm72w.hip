@@ -36,7 +36,7 @@ __global__ void __launch_bounds__(256, 1) attn_asm72w_kernel(const AttnParams p)
   lds_ones_rows<OSK72_VOFF0, OSK72_VTILE, HDL>(smem, w.tid);
   lds_const_chunk<OSK72_CONST_OFF, OSK72_KTILE>(smem, w.tid);
   const int last_valid = p.seg_len - (p.tps - 1) * 64;   // keys in the last tile of a segment (1..64)
-  const KeyPart kp = key_part(p, w.tail, w.part, last_valid < 64);   // the whole key axis, or one part of a split tail unit
+  const KeyPart kp = key_part(p, w.tail, w.part, w.qb, last_valid < 64);   // the whole key axis, or one part of a split tail unit
   const bool ragged = kp.ragged;
   const unsigned maskval = ragged_mask72(lane, last_valid);
   lds_mask_first_tile<OSK72_VOFF0, HDL>(smem, w.tid, kp, maskval);

@@ -62,7 +62,7 @@ __global__ void __launch_bounds__(256) attn_merge_kernel(const AttnParams p) {
 void split_tail(AttnParams& p, int units, int hd, void* workspace, int64_t workspace_bytes) {
   p.tail_split = 1;
   p.tail_first = 0x7fffffff;
-  if (!workspace) return;
+  if (!workspace || p.win) return;   // (a windowed launch: its units have key runs of their own)
   const int cus = osk_device_cus();
   const int R = units % cus;
   if (R == 0) return;
@@ -749,6 +749,64 @@ extern "C" int osk_attention_fwd_ragged_bf16(const void* q, int64_t q_batch_stri
   rc = dispatch(a, hd, mode, ws_a_bytes > 0 ? ws_a : nullptr, ws_a_bytes, st);
   if (rc != 0) return rc;
   rc = run_mode(b, hd, mode, st);
+  if (rc != 0) return rc;
+  b.out = a.out; b.lse = a.lse;
+  return osk_attn::launch_merge_into(b, hd, 0.6931471805599453f, st);
+}
+
+// =============================================================================================
+// Per query block key windows with an always-attended key prefix (frame-window attention): two launches + one merge
+// =============================================================================================
+// Keys [0, n_prefix) (text) are seen by every query; keys [n_prefix, Lk) are the body, of which 256-row query block qb sees the
+// 64-key tiles [first, first + count) of its table row and nothing else.  Launch A runs over the body as a key axis of its own
+// -- K and V^T advanced by n_prefix keys, V^T's row stride still that of the whole tensor -- with the table (key_part() hands
+// every work unit its run of tiles) and writes finished rows; launch B runs over the prefix in the partial mode of the ragged
+// entry above (tail_first = 0, tail_split = 1) and attn_merge_into_kernel folds it into launch A's rows in place.
+extern "C" int64_t osk_attention_window_workspace_bytes(int B, int H, int Lq, int hd) {
+  if (B <= 0 || H <= 0 || Lq <= 0 || hd <= 0) return 0;
+  return ragged_partial_bytes(B, H, Lq, hd) + ragged_lse_bytes(B, H, Lq);
+}
+
+extern "C" int osk_attention_fwd_window_bf16(const void* q, int64_t q_batch_stride, int64_t q_row_stride,
+                                             const void* k, int64_t k_batch_stride, int64_t k_row_stride, const void* vt,
+                                             void* out, int64_t o_batch_stride, int64_t o_row_stride, float* lse,
+                                             int B, int H, int Lq, int Lk, int n_prefix, int hd, float scale, int q_prescaled,
+                                             int kv_batches, float score_bound, const int32_t* windows, int n_windows,
+                                             void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!(score_bound >= 0.f) || !windows || ((uintptr_t)windows & 3)) return OSK_EINVAL;
+  if (Lq <= 0 || Lk <= 0 || n_windows != (Lq + 255) / 256 || n_prefix < 0 || (n_prefix & 63) || n_prefix >= Lk) return OSK_EINVAL;
+  if (n_prefix > 0) {
+    // the merge reads and writes `out` in 16-byte pieces; the prefix's partials are not optional, so neither is the workspace
+    if (((uintptr_t)out & 15) || (o_batch_stride & 7) || (o_row_stride & 7) || !workspace) return OSK_EINVAL;
+    if (B > 0 && H > 0 && hd > 0 && workspace_bytes < ragged_partial_bytes(B, H, Lq, hd) + (lse ? 0 : ragged_lse_bytes(B, H, Lq)))
+      return OSK_EINVAL;
+  }
+  AttnParams a;
+  int rc = attn_params(a, q, q_batch_stride, q_row_stride, k, 0, k_batch_stride, k_row_stride, vt, 0, 7, out, o_batch_stride,
+                       o_row_stride, lse, B, H, Lq, 1, Lk, hd, {64, 72, 128}, scale, q_prescaled, kv_batches, workspace, workspace_bytes);
+  if (rc != OSK_OK) return rc;
+  a.bound = bound_to_bf16_up(score_bound);
+  a.rows = 256;                                  // the table is per 256-row block: no wide layout; no tail split (tail_first stays off)
+  const int64_t seg_lp = a.seg_lp;               // V^T rows keep the whole tensor's length, whichever keys a launch walks
+  AttnParams b = a;
+  // launch A: the body, windowed
+  a.k += (int64_t)n_prefix * a.krs;
+  a.vt += n_prefix;
+  set_segments(a, 1, Lk - n_prefix);
+  a.seg_lp = (int)seg_lp;
+  a.win = windows;
+  hipStream_t st = (hipStream_t)stream;
+  if (n_prefix == 0) return run(a, hd, st);
+  if (!lse) a.lse = (float*)((char*)workspace + ragged_partial_bytes(B, H, Lq, hd));
+  // launch B: the prefix, every unit an f32 partial O + log2-domain lse of all of it
+  set_segments(b, 1, n_prefix);
+  b.seg_lp = (int)seg_lp;
+  b.tail_first = 0; b.tail_split = 1;
+  b.ws_o = (float*)workspace;
+  b.ws_lse = b.ws_o + (int64_t)osk_attn::attn_units(b) * 256 * hd;
+  rc = run(a, hd, st);
+  if (rc != 0) return rc;
+  rc = run(b, hd, st);
   if (rc != 0) return rc;
   b.out = a.out; b.lse = a.lse;
   return osk_attn::launch_merge_into(b, hd, 0.6931471805599453f, st);

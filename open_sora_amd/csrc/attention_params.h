@@ -50,6 +50,10 @@ struct AttnParams {
   // (attn_auto_bound below) -- no host round trip, no promise from the caller, hipGraph-capturable.
   const float* qn2 = nullptr;
   const float* kn2 = nullptr;
+  // per query block key window (osk_attention_fwd_window_bf16): device table [ceil(Lq / 256)][2] of (first tile, tile count), in
+  // 64-key tiles of the launch's single segment; query block qb visits tiles [first, first + count) only (key_part() below).  Only
+  // launches of 256-row units with n_seg == 1 that write finished rows carry one: no wide layout, no tail split.
+  const int* win = nullptr;
 };
 
 #define OSK_ATTN_MAX_BOUND 56.0f   // P = exp2(s - bound) >= 2^-112 for every admissible score: no underflow to zero
@@ -125,7 +129,7 @@ struct KeyPart {
   int tps, nt;
   bool ragged;
 };
-OSK_DEV KeyPart key_part(const AttnParams& p, bool tail, int part, bool ragged) {
+OSK_DEV KeyPart key_part(const AttnParams& p, bool tail, int part, int qb, bool ragged) {
   KeyPart r{0, 0, p.tps, p.n_seg * p.tps, ragged};
   if (tail) {
     if (p.n_seg > 1) {   // whole key segments per part (tail_split divides n_seg)
@@ -140,6 +144,22 @@ OSK_DEV KeyPart key_part(const AttnParams& p, bool tail, int part, bool ragged) 
       r.tps = r.nt = t1 - t0;
       r.ragged = ragged && part == p.tail_split - 1;
     }
+  } else if (p.win && p.n_seg == 1) {
+    // the query block's window: a run of tiles of the single segment, in the form the single-segment tail branch above hands the
+    // loaders -- offsets of its first tile, tps = nt = its length (so the loaders never take a segment jump), ragged only where it
+    // ends in the segment's last tile.  Runs of 1 and 2 tiles are nothing new to the loops: split tail parts of one tile, full and
+    // ragged, run in both bodies (tests/attention_cases.py: f72_one_tile_per_part, g128_3tiles_plain_merge128), and a 2-tile run
+    // is what a whole 128-key call is (tps = nt = 2).  k_loader / vt_loader take only the offsets (their segment jump is never
+    // taken with tps == nt), lds_mask_first_tile covers the 1-tile ragged run, and loader_slots* see only `ragged`.  qb is
+    // wave-uniform, so the two reads are scalar loads.  The table is clamped here: whatever it holds, the run stays inside the
+    // segment.
+    int t0 = p.win[2 * qb], n = p.win[2 * qb + 1];
+    t0 = t0 < 0 ? 0 : (t0 > p.tps - 1 ? p.tps - 1 : t0);
+    n = n < 1 ? 1 : (n > p.tps - t0 ? p.tps - t0 : n);
+    r.k_off = (int64_t)t0 * 64 * p.krs;
+    r.v_off = (int64_t)t0 * 64;
+    r.tps = r.nt = n;
+    r.ragged = ragged && t0 + n == p.tps;
   }
   return r;
 }
@@ -192,7 +212,7 @@ static inline bool attn_wide_path(const AttnParams& p, int hd, int cus, bool has
   (void)p; (void)hd; (void)cus; (void)has_ws;
   return false;
 #else
-  if (!((hd == 72 || hd == 64) && attn_fast_path(p) && p.Lq >= 1024)) return false;
+  if (!((hd == 72 || hd == 64) && attn_fast_path(p) && p.Lq >= 1024) || p.win) return false;   // (a window table is per 256 rows)
   const int bh = p.B * p.H;
   const double narrow = attn_launch_rounds(p, ((p.Lq + 255) / 256) * bh, cus, has_ws);
   const double wide = 1.852 * attn_launch_rounds(p, ((p.Lq + 511) / 512) * bh, cus, has_ws);

@@ -21,6 +21,7 @@ Two entry levels, same kernels:
 from __future__ import annotations
 
 import math
+import os
 from dataclasses import dataclass, field
 
 import weakref
@@ -536,6 +537,11 @@ class _Workspace:
         self.vt = torch.empty(B, H, hd, Lp, dtype=BF16, device=device)
         # the QKV projection writes V directly as V^T (osk_gemm_group_bf16) until the library declines a group of this geometry
         self.vt_group = hasattr(_OPS, "gemm_group")
+        # frame-window attention (MMDiTModel.set_attention_window): the host table of this forward, or None = every key; set by
+        # forward_ckpt on every call.  win_ws: the entry's workspace, one per geometry like the buffers above (a captured
+        # hipGraph replays into it: it must not move when another batch size asks for more)
+        self.attn_window = None
+        self.win_ws = None
 
     def y_double(self, D):
         return self.y[: self.B * self.L * 3 * D].view(self.B, self.L, 3 * D)
@@ -660,12 +666,62 @@ def _bf16_operands(*xs) -> bool:
     return all(not isinstance(x, (tuple, Fp8Weight)) for x in xs)
 
 
+def attention_window_table(L_txt: int, L_img: int, frame_tokens: int, window_frames: int) -> Tensor:
+    """The key ranges of frame-window attention on the joint [txt; img] sequence, for osk_attention_fwd_window_bf16 with
+    n_prefix = L_txt: host int32 [ceil((L_txt + L_img) / 256), 2] of (first tile, tile count), one row per 256 query rows, in
+    64-key tiles of the image keys.  Frame f is image rows [f N, (f + 1) N), N = frame_tokens, T = L_img / N frames, W =
+    window_frames.  A block that holds any text row gets every tile (text queries see everything).  A block whose image rows lie in
+    frames f0..f1 gets the image keys [max(0, f0 - W) N, min(T, f1 + W + 1) N), rounded OUTWARD to whole tiles.
+    This is a block-granular SUPERSET of each row's own +-W frames: a row also sees the windows of the other rows of its block and
+    the keys that share a tile with the range's ends -- up to 255 rows' worth of frames and 63 keys per side more than its own."""
+    if L_txt < 0 or L_img <= 0 or frame_tokens <= 0 or window_frames < 0:
+        raise ValueError(f"attention_window_table: L_txt >= 0, L_img > 0, frame_tokens > 0, window_frames >= 0 expected; got {(L_txt, L_img, frame_tokens, window_frames)}")
+    if L_img % frame_tokens:
+        raise ValueError(f"attention_window_table: {L_img} image tokens are not whole frames of {frame_tokens}")
+    N, W, T = frame_tokens, window_frames, L_img // frame_tokens
+    L = L_txt + L_img
+    tiles = (L_img + 63) // 64
+    rows = []
+    for r0 in range(0, L, 256):
+        r1 = min(r0 + 256, L) - 1                      # the block's last row
+        if r0 < L_txt:
+            rows.append((0, tiles))
+            continue
+        f0, f1 = (r0 - L_txt) // N, (r1 - L_txt) // N
+        k0, k1 = max(0, f0 - W) * N, min(T, f1 + W + 1) * N
+        rows.append((k0 // 64, (k1 + 63) // 64 - k0 // 64))
+    return torch.tensor(rows, dtype=torch.int32)
+
+
+def window_tile_fraction(table: Tensor, L_txt: int, L_img: int) -> float:
+    """key tiles a windowed forward visits / those a full one does, over the query blocks of the table (text tiles included)"""
+    txt_tiles, tiles = (L_txt + 63) // 64, (L_img + 63) // 64
+    return float((table[:, 1].double() + txt_tiles).sum() / (table.shape[0] * (tiles + txt_tiles)))
+
+
+def _window_env_default():
+    v = os.environ.get("OSK_ATTN_WINDOW_FRAMES", "").strip()
+    return int(v) if v else None
+
+
 def _joint_attention(ws: _Workspace, q: Tensor, k: Tensor, v: Tensor, H: int, hd: int, pv8: bool = False,
                      score_bound: float = 0.0, vt_ready: bool = False, qk8: bool = False):
     """attention() of math.py:22-36 on the joint [txt;img] sequence; the output overwrites the (dead) v slot.
     pv8 (fp8 mode, head_dim 72 / 128): V^T as e4m3 with one scale per (batch, head), P.V on the fp8 MFMA.
     qk8 (with pv8, head_dim 128 only; any other head dim takes the pv8 path): K as e4m3 too, QK^T on the fp8 MFMA.
     vt_ready: ws.vt was already written by the projection (osk_gemm_group_bf16's V^T task) -- v then only names the output slot."""
+    if getattr(ws, "attn_window", None) is not None:
+        # opt-in frame-window attention: the text keys as the always-attended prefix, the image keys by the table.  The FAST body
+        # where the plan's weight-derived bound admits it, else the general body (no auto-dispatched pair for this entry)
+        if pv8:
+            raise ValueError("frame-window attention has no fp8 kernels: disable enable_fp8() or set_attention_window(None)")
+        if not vt_ready:
+            _OPS.v_transpose(v, ws.vt, H, hd)
+        if ws.win_ws is None:
+            ws.win_ws = torch.empty(_OPS.attention_window_workspace_bytes(q.shape[0], H, q.shape[1], hd), dtype=torch.uint8, device=q.device)
+        _OPS.attention_fwd_window(q, k, ws.vt, v, H, hd, hd ** -0.5, n_prefix=ws.L_txt, windows=ws.attn_window, q_prescaled=True,
+                                  score_bound=score_bound if 0.0 < score_bound <= SCORE_BOUND_LIMIT else 0.0, workspace=ws.win_ws)
+        return
     wsp = _OPS.attention_workspace(q.device)
     if pv8 and hd in (72, 128):
         B = v.shape[0]
@@ -998,6 +1054,8 @@ class MMDiTModel(_OskState, nn.Module):
             nn.init.zeros_(self.cond_in.bias)
         self._plan = None
         self._sp = None  # set by open_sora_amd.seqpar.enable
+        self._attn_window = None        # (window_frames, frame_tokens) or None: set_attention_window; a plain attribute, not in state_dict
+        self._attn_window_table = None  # ((L_txt, L_img, window_frames, frame_tokens), host table) of the last windowed forward
         self.forward = self.forward_ckpt  # instance attribute, as the reference does (model.py:143-146)
 
     # ------------------------------------------------------------------ fp8 mode
@@ -1013,11 +1071,50 @@ class MMDiTModel(_OskState, nn.Module):
         K is packed after the all-to-all, with no collective.  Recommended for head_dim 128: the attention launch takes
         0.77 - 0.79 of the pv8 time with the K pack counted (A/B spread under 2 %) at the same model-level error; DESIGN.md
         section 4, profiles/attn_qk8.md, profiles/attn_qk8_sp.md (a rank's launch at the sharded shape)."""
+        if on and getattr(self, "_attn_window", None) is not None:
+            raise ValueError("enable_fp8: frame-window attention (set_attention_window) has no fp8 kernels; turn it off first")
         for b in list(self.double_blocks) + list(self.single_blocks):
             object.__setattr__(b, "_osk_fp8", bool(on))
             object.__setattr__(b, "_osk_qk8", bool(on and qk8))
         self.invalidate_plan()
         return self
+
+    # ------------------------------------------------------------------ frame-window attention
+    def set_attention_window(self, window_frames="env", frame_tokens: int | None = None):
+        """Opt-in frame-window attention, off by default: text keys stay visible to every query, an image query block keeps the
+        image keys of its own frames +- window_frames (attention_window_table: a block-granular superset of each row's window) and
+        the attention runs osk_attention_fwd_window_bf16.  frame_tokens: image tokens per latent frame, (h / patch) * (w / patch).
+        None turns it off; without the argument the environment's OSK_ATTN_WINDOW_FRAMES decides (unset: off).  Exact with respect
+        to the mask it states; the reference attends to every key, so outputs DIFFER from it by what the dropped keys carried, and
+        the quality of that on real checkpoints is not measured.  bf16 attention without sequence parallelism
+        only, L_txt % 64 == 0 (checked when a forward sees the text).  The setting is not part of state_dict."""
+        if isinstance(window_frames, str) and window_frames == "env":
+            window_frames = _window_env_default()
+        if window_frames is None:
+            self._attn_window = None
+            return self
+        if int(window_frames) < 0 or frame_tokens is None or int(frame_tokens) <= 0:
+            raise ValueError(f"set_attention_window: window_frames >= 0 and frame_tokens > 0 expected; got {window_frames}, {frame_tokens}")
+        if any(getattr(b, "_osk_fp8", False) for b in list(self.double_blocks) + list(self.single_blocks)):
+            raise ValueError("set_attention_window: frame-window attention has no fp8 kernels; call enable_fp8(False) first")
+        if getattr(self, "_sp", None) is not None:
+            raise ValueError("set_attention_window: frame-window attention does not run under sequence parallelism yet")
+        self._attn_window = (int(window_frames), int(frame_tokens))
+        return self
+
+    def _window_table(self, L_txt: int, L_img: int, sp):
+        """the host table of this forward's geometry (rebuilt when L_txt, L_img or the setting changed), or None when off"""
+        if getattr(self, "_attn_window", None) is None:
+            return None
+        if sp is not None or getattr(self, "_sp", None) is not None:
+            raise ValueError("frame-window attention does not run under sequence parallelism yet: set_attention_window(None)")
+        if L_txt % 64:
+            raise ValueError(f"frame-window attention needs a text length that is a multiple of 64 (the key prefix of "
+                             f"osk_attention_fwd_window_bf16); got L_txt = {L_txt}")
+        key = (L_txt, L_img) + self._attn_window
+        if self._attn_window_table is None or self._attn_window_table[0] != key:
+            self._attn_window_table = (key, attention_window_table(L_txt, L_img, self._attn_window[1], self._attn_window[0]))
+        return self._attn_window_table[1]
 
     # ------------------------------------------------------------------ planning
     def attention_report(self, n_seg: int = 1, seg_len: int = 0, last_seg_len: int = 0) -> dict:
@@ -1048,7 +1145,13 @@ class MMDiTModel(_OskState, nn.Module):
             ragged = {"ragged": {"last_seg_len": last_seg_len, "attention_entry_launches": 3, "extra_prep_launches": prep, "bodies_full_segments": body(n_seg - 1, seg_len),
                                  "bodies_last_segment": body(1, last_seg_len), "kv_chunks_requested": getattr(sp, "kv_chunks", 1)}}
             chunks = 1
-        return {**ragged, "kv_chunks": chunks, "score_bound_min": min(bounds), "score_bound_max": max(bounds), "bound_limit": SCORE_BOUND_LIMIT, "bodies": bodies,
+        window = {"attention_window": None}
+        if getattr(self, "_attn_window", None) is not None:
+            # visited_tile_fraction: of the last windowed forward's geometry (None before the first one)
+            t = self._attn_window_table
+            window = {"attention_window": {"window_frames": self._attn_window[0], "frame_tokens": self._attn_window[1],
+                                           "visited_tile_fraction": None if t is None else window_tile_fraction(t[1], t[0][0], t[0][1])}}
+        return {**ragged, **window, "kv_chunks": chunks, "score_bound_min": min(bounds), "score_bound_max": max(bounds), "bound_limit": SCORE_BOUND_LIMIT, "bodies": bodies,
                 "blocks_on_fast_body": sum(1 for b in bounds if 0.0 < b <= SCORE_BOUND_LIMIT), "blocks": len(bounds),
                 # blocks whose weight-derived bound is too large: FAST / general chosen per (batch, head) on the device from the operands
                 "blocks_auto_dispatched": auto}
@@ -1227,6 +1330,7 @@ class MMDiTModel(_OskState, nn.Module):
                 sp = None
         ws, vec, rope = self.prepare_block_inputs(img, img_ids, txt, txt_ids, timesteps, y_vec, cond, guidance,
                                                   _shard=shard)
+        ws.attn_window = self._window_table(L_txt, L_img, sp)
         p = self._plan
         D, H = self.hidden_size, self.num_heads
         hd = D // H

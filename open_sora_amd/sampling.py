@@ -130,6 +130,12 @@ def _prune_default() -> bool:
     return os.environ.get("OSK_CFG_PRUNE", "") not in ("", "0")
 
 
+def _window_default():
+    """OSK_ATTN_WINDOW_FRAMES, read at call time like OSK_CFG_PRUNE (unset or empty: off)"""
+    v = os.environ.get("OSK_ATTN_WINDOW_FRAMES", "").strip()
+    return int(v) if v else None
+
+
 class I2VDenoiser:
     """sampling.py:158-245.  `denoise(model, img=..., timesteps=[...], guidance=..., guidance_img=..., masks=...,
     masked_ref=..., img_ids=..., txt=..., txt_ids=..., y_vec=..., [text_osci, image_osci, scale_temporal_osci,
@@ -148,7 +154,12 @@ class I2VDenoiser:
     prompts are the same tensor rows (text-to-video).  The skipped branches cancel in sampling.py:216 exactly in real arithmetic; in
     bf16 the result differs from the triple's by rounding only (tests/test_gpu_cfg_prune.py holds it to the project's parity rule).
     Off, the loop is the one above, launch for launch.  With hip_graph, one graph per branch count in use.  `last_branch_counts`
-    holds the counts of the last run.  Cost: one activation workspace set per batch size in use instead of one."""
+    holds the counts of the last run.  Cost: one activation workspace set per batch size in use instead of one.
+
+    `attn_window_frames=W` (default: OSK_ATTN_WINDOW_FRAMES, read at call time; unset = off): opt-in frame-window attention for
+    this loop -- MMDiTModel.set_attention_window(W, frame_tokens) with frame_tokens from masked_ref's h, w and patch_size, also
+    under hip_graph and cfg_prune; the model's previous setting is restored afterwards.  Results differ from the reference's
+    (every query sees every key) by what the dropped keys carried; output quality on real checkpoints is not measured."""
 
     def denoise(self, model, **kwargs) -> Tensor:
         img = kwargs.pop("img")
@@ -165,6 +176,24 @@ class I2VDenoiser:
         hip_graph = bool(kwargs.pop("hip_graph", False))
         cfg_prune = kwargs.pop("cfg_prune", None)
         cfg_prune = _prune_default() if cfg_prune is None else bool(cfg_prune)
+        attn_window_frames = kwargs.pop("attn_window_frames", "env")
+        if isinstance(attn_window_frames, str) and attn_window_frames == "env":
+            attn_window_frames = _window_default()
+        if attn_window_frames is not None:
+            # opt-in frame-window attention for this loop (MMDiTModel.set_attention_window): a latent frame is (h / patch) * (w / patch)
+            # tokens of the packed sequence; the model's previous setting comes back afterwards, whatever the loop does
+            if not hasattr(model, "set_attention_window"):
+                raise ValueError("attn_window_frames needs a model with set_attention_window (open_sora_amd.mmdit.MMDiTModel)")
+            ps = patch_size
+            previous = getattr(model, "_attn_window", None)
+            model.set_attention_window(int(attn_window_frames), (masked_ref.shape[-2] // ps) * (masked_ref.shape[-1] // ps))
+            try:
+                return self.denoise(model, img=img, timesteps=timesteps, guidance=guidance, guidance_img=guidance_img, masks=masks,
+                                    masked_ref=masked_ref, text_osci=text_osci, image_osci=image_osci,
+                                    scale_temporal_osci=scale_temporal_osci, patch_size=patch_size, hip_graph=hip_graph,
+                                    cfg_prune=cfg_prune, attn_window_frames=None, **kwargs)
+            finally:
+                model.set_attention_window(*(previous if previous is not None else (None,)))
 
         n3 = img.shape[0]
         n = n3 // 3
