@@ -534,6 +534,30 @@ int osk_copy_rows_bf16(const void* src, int64_t src_chunk_stride, int64_t src_ba
                        int64_t dst_chunk_stride, int64_t dst_batch_stride, int64_t dst_row_stride, int n_chunks, int B, int L, int C,
                        void* stream);
 
+/* ---- step cache of the sampler (not in the reference; open_sora_amd/sampling.py, I2VDenoiser.denoise(step_cache=...)).  Additive
+ * under ABI version 2.
+ * Step delta, one pass over two bf16 [B, L, C] tensors:
+ *   sums[0] = sum |cur - prev|,  sums[1] = sum |prev|   (f32 accumulation),  then prev := cur, bit for bit.
+ * cur: a view with element strides cur_batch_stride / cur_row_stride (multiples of 8, unit channel stride); prev: contiguous, must
+ * not overlap cur.  Two stages and no atomics: per-workgroup f32 partials go to `workspace`
+ * (osk_step_delta_workspace_bytes(B, L, C) bytes, 4-byte aligned), a one-workgroup finish adds them in a fixed order -- the same
+ * inputs give the same bits on every call.  The host forms the ratio (one 8-byte read back).  C % 8 == 0, cur / prev 16-byte aligned,
+ * B L C / 8 < 2^31; anything else (a NULL pointer, a workspace too small) is OSK_EINVAL with nothing launched.  No allocation,
+ * memset or synchronisation: capturable. */
+int64_t osk_step_delta_workspace_bytes(int B, int L, int C);
+int osk_step_delta_bf16(const void* cur, int64_t cur_batch_stride, int64_t cur_row_stride, void* prev, float* sums, int B, int L, int C,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Residual store and apply over strided bf16 [B, L, C] views (strides multiples of 8, unit channel stride, 16-byte aligned,
+ * C % 8 == 0):  out = bf16(f32(a) - f32(b))  /  out = bf16(f32(a) + f32(b)), the exact difference / sum rounded once.  out may be a
+ * or b (same strides) -- the sampler stores R = Y - X over the X it saved, and applies Y = X + R over X. */
+int osk_residual_sub_bf16(const void* a, int64_t a_batch_stride, int64_t a_row_stride, const void* b, int64_t b_batch_stride,
+                          int64_t b_row_stride, void* out, int64_t out_batch_stride, int64_t out_row_stride, int B, int L, int C,
+                          void* stream);
+int osk_residual_add_bf16(const void* a, int64_t a_batch_stride, int64_t a_row_stride, const void* b, int64_t b_batch_stride,
+                          int64_t b_row_stride, void* out, int64_t out_batch_stride, int64_t out_row_stride, int B, int L, int C,
+                          void* stream);
+
 /* =====================================================================================================
  * Causal 3-D VAE (HunyuanVideo VAE, /root/reference/opensora/models/hunyuan_vae).  Activations are channels-last
  * NDHWC bf16 ([B, T, H, W, C] contiguous); the NCTHW <-> NDHWC conversion happens once at the module boundary.

@@ -77,6 +77,10 @@ SIGNATURES = {
     "osk_cfg_euler_bf16": [_vp, _i64, _vp, _vp, _f32, _f32, _vp, _f32, _vp],
     "osk_cfg_euler_nb_bf16": [_vp, _i32, _i64, _vp, _vp, _f32, _f32, _vp, _f32, _vp],
     "osk_copy_rows_bf16": [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp],
+    "osk_step_delta_workspace_bytes": [_i32, _i32, _i32],
+    "osk_step_delta_bf16": [_vp, _i64, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp],
+    "osk_residual_sub_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp],
+    "osk_residual_add_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp],
     "osk_causal_conv3d_ndhwc_bf16": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32,
                                      _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp],
     "osk_causal_conv3d_gn_ndhwc_bf16": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32,
@@ -122,7 +126,8 @@ def _load() -> C.CDLL:
         fn.argtypes = argtypes
         fn.restype = (C.c_char_p if name in ("osk_arch", "osk_attention_kernel_name", "osk_attention_body_name") else
                       _i64 if name in ("osk_attention_workspace_bytes", "osk_attention_hd512_workspace_bytes",
-                                       "osk_attention_ragged_workspace_bytes", "osk_attention_window_workspace_bytes") else _i32)
+                                       "osk_attention_ragged_workspace_bytes", "osk_attention_window_workspace_bytes",
+                                       "osk_step_delta_workspace_bytes") else _i32)
     if lib.osk_abi_version() != 2:
         raise ImportError("libosk_hip.so ABI version mismatch")
     return lib
@@ -956,6 +961,72 @@ def cfg_euler_nb(pred: torch.Tensor, nb: int, x: torch.Tensor, x_out: torch.Tens
     _check(lib.osk_cfg_euler_nb_bf16(pred.data_ptr(), nb, n, x.data_ptr(), x_out.data_ptr(), g_txt, g_img,
                                      _p(g_img_vec), dt, _stream()), "osk_cfg_euler_nb_bf16")
     return x_out
+
+
+# ----------------------------------------------------------------------------------------------
+# step cache of the sampler (csrc/step_cache.hip)
+# ----------------------------------------------------------------------------------------------
+def _step_view(t, name: str, what: str) -> None:
+    """a bf16 [B, L, C] device view the step-cache kernels take: unit channel stride, C and the other strides multiples of 8, 16-byte
+    aligned -- ValueError before anything is launched"""
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.bfloat16 and t.ndim == 3 and t.numel() > 0):
+        raise ValueError(f"{what}: {name} must be a non-empty bf16 [B, L, C] tensor on the GPU; got "
+                         f"{(t.device.type, t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__}")
+    if t.shape[2] % 8 or t.stride(2) != 1 or t.stride(0) % 8 or t.stride(1) % 8 or t.data_ptr() % 16:
+        raise ValueError(f"{what}: {name} needs C % 8 == 0, unit channel stride, batch / row strides % 8 == 0 and 16-byte alignment; "
+                         f"got shape {tuple(t.shape)}, strides {t.stride()}")
+    if t.numel() // 8 >= 2 ** 31:
+        raise ValueError(f"{what}: {name} has {t.numel()} elements; the kernels index up to 2^34")
+
+
+def step_delta_workspace_bytes(B: int, L: int, C: int) -> int:
+    return int(lib.osk_step_delta_workspace_bytes(B, L, C))
+
+
+def step_delta(cur: torch.Tensor, prev: torch.Tensor, sums: torch.Tensor, workspace: torch.Tensor) -> torch.Tensor:
+    """sums f32 [2] = (sum |cur - prev|, sum |prev|), then prev := cur: osk_step_delta_bf16.  cur a bf16 [B, L, C] view, prev
+    contiguous of the same shape, workspace a uint8 tensor of step_delta_workspace_bytes(B, L, C).  Deterministic, capturable."""
+    what = "osk_step_delta_bf16"
+    _step_view(cur, "cur", what)
+    _step_view(prev, "prev", what)
+    if prev.shape != cur.shape or not prev.is_contiguous():
+        raise ValueError(f"{what}: prev must be contiguous and shaped like cur; got {tuple(prev.shape)} (strides {prev.stride()}) for {tuple(cur.shape)}")
+    if not (torch.is_tensor(sums) and sums.is_cuda and sums.dtype == torch.float32 and sums.numel() == 2 and sums.is_contiguous()):
+        raise ValueError(f"{what}: sums must be a contiguous f32 [2] tensor on the GPU")
+    B, L, Cc = cur.shape
+    if not (torch.is_tensor(workspace) and workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()
+            and workspace.numel() >= step_delta_workspace_bytes(B, L, Cc) and workspace.data_ptr() % 4 == 0):
+        raise ValueError(f"{what}: workspace must be a uint8 tensor on the GPU of at least step_delta_workspace_bytes({B}, {L}, {Cc}) bytes")
+    lo, hi = cur.data_ptr(), cur.data_ptr() + 2 * ((B - 1) * cur.stride(0) + (L - 1) * cur.stride(1) + Cc)
+    if lo < prev.data_ptr() + 2 * prev.numel() and prev.data_ptr() < hi:
+        raise ValueError(f"{what}: cur and prev overlap")
+    _check(lib.osk_step_delta_bf16(cur.data_ptr(), cur.stride(0), cur.stride(1), prev.data_ptr(), sums.data_ptr(), B, L, Cc,
+                                   workspace.data_ptr(), workspace.numel(), _stream()), what)
+    return sums
+
+
+def _residual(fn, what: str, a: torch.Tensor, b: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    for t, name in ((a, "a"), (b, "b"), (out, "out")):
+        _step_view(t, name, what)
+    if not (a.shape == b.shape == out.shape):
+        raise ValueError(f"{what}: a, b and out must have one shape; got {tuple(a.shape)}, {tuple(b.shape)}, {tuple(out.shape)}")
+    for t, name in ((a, "a"), (b, "b")):
+        if t.data_ptr() == out.data_ptr() and t.stride() != out.stride():
+            raise ValueError(f"{what}: out aliases {name} with other strides")
+    B, L, Cc = a.shape
+    _check(fn(a.data_ptr(), a.stride(0), a.stride(1), b.data_ptr(), b.stride(0), b.stride(1), out.data_ptr(), out.stride(0), out.stride(1),
+              B, L, Cc, _stream()), what)
+    return out
+
+
+def residual_sub(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """out = bf16(f32(a) - f32(b)) over bf16 [B, L, C] views, one rounding; out may be a or b"""
+    return _residual(lib.osk_residual_sub_bf16, "osk_residual_sub_bf16", a, b, out)
+
+
+def residual_add(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """out = bf16(f32(a) + f32(b)) over bf16 [B, L, C] views, one rounding; out may be a or b"""
+    return _residual(lib.osk_residual_add_bf16, "osk_residual_add_bf16", a, b, out)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -573,6 +573,33 @@ def _workspace(owner, B, L_txt, L_img, D, R, H, hd, device) -> _Workspace:
     return ws
 
 
+@dataclass
+class _StepState:
+    """what the head of one forward leaves for its blocks and its tail (MMDiTModel._forward_head)"""
+    ws: _Workspace
+    rope: object
+    mod: Tensor
+    plan: dict
+    sp: object
+    B: int
+    L_txt: int
+    dtype: torch.dtype
+    device: object
+
+
+class _StepCache:
+    """buffers of the sampler's step cache (MMDiTModel.step_cache_begin): prev = M_{i-1}[:n] bf16 [n, L_img, D], res = R bf16
+    [rows, L_img, D], sums f32 [2], the delta kernel's partials; have[row]: does the row hold a residual (host)"""
+
+    def __init__(self, key, n, rows, L_img, D, device):
+        self.key, self.n, self.rows, self.L_img = key, n, rows, L_img
+        self.prev = torch.zeros(n, L_img, D, dtype=BF16, device=device)
+        self.res = torch.empty(rows, L_img, D, dtype=BF16, device=device)
+        self.sums = torch.zeros(2, dtype=torch.float32, device=device)
+        self.partials = torch.empty(max(_OPS.step_delta_workspace_bytes(n, L_img, D), 8), dtype=torch.uint8, device=device)
+        self.have = [False] * rows
+
+
 # =============================================================================================
 # RoPE table handling
 # =============================================================================================
@@ -1328,34 +1355,114 @@ class MMDiTModel(_OskState, nn.Module):
             shard = sp.shard_range(L_txt + L_img, L_txt)  # None when a rank would hold no image tokens
             if shard is None:
                 sp = None
+        st = self._forward_head(sp, shard, img, img_ids, txt, txt_ids, timesteps, y_vec, cond, guidance)
+        self._forward_blocks(st)
+        return self._forward_tail(st)
+
+    # The forward in three parts (head / blocks / tail), the launches of forward_ckpt in its order; the sampler's step cache drives
+    # them one by one (step_head / step_run / step_skip below), everyone else through forward_ckpt above.
+    def _forward_head(self, sp, shard, img, img_ids, txt, txt_ids, timesteps, y_vec, cond, guidance) -> "_StepState":
+        """embeddings, vec, RoPE tables and the adaLN modulation of every block: everything in front of block 0"""
         ws, vec, rope = self.prepare_block_inputs(img, img_ids, txt, txt_ids, timesteps, y_vec, cond, guidance,
                                                   _shard=shard)
-        ws.attn_window = self._window_table(L_txt, L_img, sp)
+        ws.attn_window = self._window_table(txt.shape[1], img.shape[1], sp)
         p = self._plan
+        mod = torch.empty(img.shape[0], p["mod_cols"], dtype=torch.float32, device=img.device)
+        _OPS.gemv_tasks(vec, p["mod_tasks"], mod, act_in=1)
+        return _StepState(ws, rope, mod, p, sp, img.shape[0], txt.shape[1], img.dtype, img.device)
+
+    def _forward_blocks(self, st: "_StepState") -> None:
         D, H = self.hidden_size, self.num_heads
         hd = D // H
         R = int(D * self.config.mlp_ratio)
-        B = img.shape[0]
-        mod = torch.empty(B, p["mod_cols"], dtype=torch.float32, device=img.device)
-        _OPS.gemv_tasks(vec, p["mod_tasks"], mod, act_in=1)
+        p = st.plan
         for plan, (ci, ct) in zip(p["double"], p["col_double"]):
-            run_double_block(plan, ws, mod, ci, ct, rope, H, hd, sp)
+            run_double_block(plan, st.ws, st.mod, ci, ct, st.rope, H, hd, st.sp)
         for plan, c in zip(p["single"], p["col_single"]):
-            run_single_block(plan, ws, mod, c, rope, H, hd, R, sp)
+            run_single_block(plan, st.ws, st.mod, c, st.rope, H, hd, R, st.sp)
+
+    def _forward_tail(self, st: "_StepState") -> Tensor:
         # LastLayer (layers.py:398-402): (shift, scale) order
+        ws, mod, p, sp, B, D = st.ws, st.mod, st.plan, st.sp, st.B, self.hidden_size
         Lt = ws.L_txt
         cf = p["col_final"]
         shift, scale = mod[:, cf: cf + D], mod[:, cf + D: cf + 2 * D]
         C_out = p["final_w"].shape[0]
         if sp is None:
             _OPS.ln_modulate(ws.x[:, Lt:], shift, scale, ws.xm[:, Lt:], mod.stride(0))
-            out = torch.empty(B, ws.L_img, C_out, dtype=BF16, device=img.device)
+            out = torch.empty(B, ws.L_img, C_out, dtype=BF16, device=st.device)
             _OPS.gemm(ws.xm[:, Lt:], p["final_w"], p["final_b"], out)
         else:
             # equal-size gather: every rank projects ALL its rows (rank 0's few txt rows are discarded after)
             _OPS.ln_modulate(ws.x, shift, scale, ws.xm, mod.stride(0))
-            out = sp.gather_output(ws, lambda dst: _OPS.gemm(ws.xm, p["final_w"], p["final_b"], dst), C_out, L_txt)
-        return out.to(img.dtype) if img.dtype != BF16 else out
+            out = sp.gather_output(ws, lambda dst: _OPS.gemm(ws.xm, p["final_w"], p["final_b"], dst), C_out, st.L_txt)
+        return out.to(st.dtype) if st.dtype != BF16 else out
+
+    # ------------------------------------------------------------------ step cache (driven by sampling.I2VDenoiser)
+    def step_cache_begin(self, n: int, rows: int, L_img: int, device) -> "_StepCache":
+        """The buffers of one step-cached sampling loop of `n` samples whose steps run up to `rows` batch rows of L_img image tokens:
+        M_{i-1}[:n], the residual R of every row, the two sums and the delta kernel's partials.  They belong to the loop's
+        geometry, not to one batch size -- the three batch sizes of a pruned loop share them -- and are kept, like the activation
+        workspaces, per (geometry, device, stream): the last loop's set is reused, another geometry replaces it.  Which rows hold
+        a residual starts empty on every call."""
+        if getattr(self, "_sp", None) is not None:
+            raise ValueError("step_cache: a model under sequence parallelism is out of scope for the step cache (every rank would "
+                             "need the same distance); run it without seqpar.enable or leave step_cache off")
+        if len(self.double_blocks) == 0:
+            raise ValueError("step_cache: the distance is taken at double block 0's image stream; this model has no double block")
+        key = (n, rows, L_img, self.hidden_size, str(device), _stream_key(device), id(_OPS))
+        sc = getattr(self, "_osk_step_cache", None)
+        if sc is None or sc.key != key:
+            sc = _StepCache(key, n, rows, L_img, self.hidden_size, device)
+            object.__setattr__(self, "_osk_step_cache", sc)
+        sc.have = [False] * rows
+        return sc
+
+    def step_head(self, sc: "_StepCache", img: Tensor, img_ids: Tensor, txt: Tensor, txt_ids: Tensor, timesteps: Tensor, y_vec: Tensor,
+                  cond: Tensor = None, guidance: Tensor | None = None, **kwargs) -> "_StepState":
+        """The head of a step plus its distance: the forward's own head, then block 0's image-stream LN + modulate of the n
+        conditional rows (M_i[:n], into the slot block 0 itself writes it to a moment later) and osk_step_delta_bf16 against the
+        previous step's, which it also replaces.  sc.sums then holds the two sums in stream order; nothing is read back here."""
+        if getattr(self, "_sp", None) is not None:
+            raise ValueError("step_cache: a model under sequence parallelism is out of scope for the step cache")
+        st = self._forward_head(None, None, img, img_ids, txt, txt_ids, timesteps, y_vec, cond, guidance)
+        ws, D, Lt = st.ws, self.hidden_size, st.ws.L_txt
+        if ws.L_img != sc.L_img or st.B > sc.rows or st.B < sc.n:
+            raise ValueError(f"step_head: {st.B} rows of {ws.L_img} image tokens do not fit the step cache of {sc.n} samples, {sc.rows} rows of {sc.L_img}")
+        (sh1, sc1), mbs = _mod_views(st.mod, st.plan["col_double"][0][0], 2, D)
+        m_cur = ws.xm[:sc.n, Lt:]
+        _OPS.ln_modulate(ws.x[:sc.n, Lt:], sh1, sc1, m_cur, mbs)
+        _OPS.step_delta(m_cur, sc.prev, sc.sums, sc.partials)
+        return st
+
+    def step_run(self, sc: "_StepCache", st: "_StepState") -> Tensor:
+        """a computed step: X_i of the rows it runs is saved, the blocks run, R[row] = bf16(f32(Y) - f32(X_i)) replaces the saved
+        rows; the other rows keep their older residual"""
+        ws, m = st.ws, st.B
+        x_img, r = ws.x[:, ws.L_txt:], sc.res[:m]
+        _OPS.copy_rows(x_img, r)
+        self._forward_blocks(st)
+        _OPS.residual_sub(x_img, r, r)
+        sc.have[:m] = [True] * m
+        return self._forward_tail(st)
+
+    def step_skip(self, sc: "_StepCache", st: "_StepState") -> Tensor:
+        """a skipped step: Y = bf16(f32(X_i) + f32(R[rows])) in place of the block stack, then the final layer; no block is launched"""
+        ws, m = st.ws, st.B
+        if not all(sc.have[:m]):
+            raise ValueError(f"step_skip: rows {[r for r in range(m) if not sc.have[r]]} hold no residual yet")
+        x_img = ws.x[:, ws.L_txt:]
+        _OPS.residual_add(x_img, sc.res[:m], x_img)
+        return self._forward_tail(st)
+
+    @staticmethod
+    def step_distance(sc: "_StepCache") -> float:
+        """d_i of the last step_head: sum |M_i - M_{i-1}| / sum |M_{i-1}| over the conditional rows, +inf when the denominator is 0
+        or either sum is not finite.  Reads 8 bytes back: the step cache's one host synchronisation per step."""
+        num, den = (float(v) for v in sc.sums.tolist())
+        if not (math.isfinite(num) and math.isfinite(den)) or den == 0.0:
+            return math.inf
+        return num / den
 
 
 def Flux(cache_dir: str = None, from_pretrained: str = None, device_map="cuda", torch_dtype: torch.dtype = BF16,

@@ -136,6 +136,34 @@ def _window_default():
     return int(v) if v else None
 
 
+def _step_cache_default():
+    """OSK_STEP_CACHE, read at call time like OSK_CFG_PRUNE: the threshold as a float (unset or empty: off)"""
+    v = os.environ.get("OSK_STEP_CACHE", "").strip()
+    return float(v) if v else None
+
+
+def step_cache_poly(coefficients, d: float) -> float:
+    """the rescaling polynomial of the step cache at d, coefficients highest power first (Horner, Python floats); None = [1, 0]"""
+    r = 0.0
+    for c in ([1.0, 0.0] if coefficients is None else coefficients):
+        r = r * d + float(c)
+    return r
+
+
+def step_cache_decide(i: int, n_steps: int, d: float, acc: float, threshold: float, coefficients=None,
+                      have_rows: bool = True) -> tuple[bool, float]:
+    """The step cache's decision for step i of n_steps, in Python floats: (computed, acc to carry on).
+    Step 0 and the last step are computed.  Any other step adds poly(d) to acc and is SKIPPED iff acc < threshold and every row
+    it needs holds a residual (have_rows); otherwise it is computed.  A computed step carries acc = 0 on, a skipped one its acc.
+    d = +inf (no usable distance) makes acc +inf, a NaN anywhere fails the comparison: both compute."""
+    if i <= 0 or i >= n_steps - 1:
+        return True, 0.0
+    acc = acc + step_cache_poly(coefficients, d)
+    if acc < threshold and have_rows:
+        return False, acc
+    return True, 0.0
+
+
 class I2VDenoiser:
     """sampling.py:158-245.  `denoise(model, img=..., timesteps=[...], guidance=..., guidance_img=..., masks=...,
     masked_ref=..., img_ids=..., txt=..., txt_ids=..., y_vec=..., [text_osci, image_osci, scale_temporal_osci,
@@ -159,7 +187,17 @@ class I2VDenoiser:
     `attn_window_frames=W` (default: OSK_ATTN_WINDOW_FRAMES, read at call time; unset = off): opt-in frame-window attention for
     this loop -- MMDiTModel.set_attention_window(W, frame_tokens) with frame_tokens from masked_ref's h, w and patch_size, also
     under hip_graph and cfg_prune; the model's previous setting is restored afterwards.  Results differ from the reference's
-    (every query sees every key) by what the dropped keys carried; output quality on real checkpoints is not measured."""
+    (every query sees every key) by what the dropped keys carried; output quality on real checkpoints is not measured.
+
+    `step_cache=threshold` (default: OSK_STEP_CACHE, read at call time; unset = off) with `step_cache_coefficients=None`: opt-in
+    step cache of the TeaCache kind.  Every step runs the model's head and measures how far block 0's modulated image input of
+    the conditional rows moved since the previous step (relative L1, osk_step_delta_bf16); while the accumulated, polynomial-
+    rescaled movement stays under the threshold (step_cache_decide) the block stack is skipped and the last computed residual
+    of each row is added to the embedded latents instead (DESIGN.md section 4 states the rule).  Works with cfg_prune (residuals
+    are kept per row of the triple) and attn_window_frames; refused with hip_graph, under sequence parallelism and for models
+    without the head / blocks / tail split.  One 8-byte read back per step.  `last_step_cache` holds (d, acc, computed) per step
+    of the last run (None when off).  No calibrated polynomial ships (default: the identity), and neither the skip rate nor the
+    output quality on real checkpoints is measured: a skipped step's result DIFFERS from the reference's."""
 
     def denoise(self, model, **kwargs) -> Tensor:
         img = kwargs.pop("img")
@@ -179,6 +217,22 @@ class I2VDenoiser:
         attn_window_frames = kwargs.pop("attn_window_frames", "env")
         if isinstance(attn_window_frames, str) and attn_window_frames == "env":
             attn_window_frames = _window_default()
+        step_cache = kwargs.pop("step_cache", "env")
+        if isinstance(step_cache, str) and step_cache == "env":
+            step_cache = _step_cache_default()
+        coefficients = kwargs.pop("step_cache_coefficients", None)
+        self.last_step_cache = None
+        if step_cache is not None:
+            step_cache = float(step_cache)
+            coefficients = None if coefficients is None else [float(c) for c in coefficients]
+            # out of scope for this change, refused before anything runs
+            if not all(hasattr(model, a) for a in ("step_cache_begin", "step_head", "step_run", "step_skip", "step_distance")):
+                raise ValueError("step_cache needs a model with the head / blocks / tail split (open_sora_amd.mmdit.MMDiTModel); "
+                                 f"{type(model).__name__} has none")
+            if getattr(model, "_sp", None) is not None:
+                raise ValueError("step_cache does not run under sequence parallelism (every rank would have to take the same decision)")
+            if hip_graph:
+                raise ValueError("step_cache and hip_graph=True do not combine: the decision sits on the host between the head and the blocks")
         if attn_window_frames is not None:
             # opt-in frame-window attention for this loop (MMDiTModel.set_attention_window): a latent frame is (h / patch) * (w / patch)
             # tokens of the packed sequence; the model's previous setting comes back afterwards, whatever the loop does
@@ -191,7 +245,8 @@ class I2VDenoiser:
                 return self.denoise(model, img=img, timesteps=timesteps, guidance=guidance, guidance_img=guidance_img, masks=masks,
                                     masked_ref=masked_ref, text_osci=text_osci, image_osci=image_osci,
                                     scale_temporal_osci=scale_temporal_osci, patch_size=patch_size, hip_graph=hip_graph,
-                                    cfg_prune=cfg_prune, attn_window_frames=None, **kwargs)
+                                    cfg_prune=cfg_prune, attn_window_frames=None, step_cache=step_cache,
+                                    step_cache_coefficients=coefficients, **kwargs)
             finally:
                 model.set_attention_window(*(previous if previous is not None else (None,)))
 
@@ -216,6 +271,11 @@ class I2VDenoiser:
         x_next = torch.empty_like(x)
         img3 = torch.empty(n3, *x.shape[1:], device=dev, dtype=dt)
         t_vec = torch.empty(n3, dtype=dt, device=dev)
+        if step_cache is not None:
+            self.last_step_cache = []
+            return self._loop_step_cache(model, kwargs, x, x_next, img3, t_vec, cond3, guidance_vec, timesteps, guidance, guidance_img,
+                                         text_osci, image_osci, scale_temporal_osci, patch_size, b, c, t, h_, w_, dev, counts, cfg_prune,
+                                         step_cache, coefficients, self.last_step_cache).to(dt)
         graph, pred = None, None
         if hip_graph:
             # capture needs a non-default stream, and the model's workspaces are keyed on the stream: run the WHOLE loop (the
@@ -324,6 +384,54 @@ class I2VDenoiser:
             x, x_next = x_next, x
         return x
 
+    @staticmethod
+    def _loop_step_cache(model, kwargs, x, x_next, img3, t_vec, cond3, guidance_vec, timesteps, guidance, guidance_img, text_osci,
+                         image_osci, scale_temporal_osci, patch_size, b, c, t, h_, w_, dev, counts, pruned, threshold, coefficients,
+                         record):
+        """_loop (pruned: _loop_pruned) with the step cache: the model's forward is driven in its three parts.  Every step runs the
+        head on its counts[i] leading branches and the distance of the conditional rows; step_cache_decide then picks the block
+        stack (step_run: the rows' residuals are stored) or the stored residuals (step_skip).  The inputs, the combine kernel and
+        their order are those of the loop it stands for, so a run that computes every step gives that loop's bits."""
+        n = x.shape[0]
+        n_steps = len(timesteps) - 1
+        sc = model.step_cache_begin(n, max(counts, default=3) * n, img3.shape[1], dev)
+        inputs = {}    # branch count -> the model's keyword arguments for it (views made once, as in _loop_pruned)
+        acc = 0.0
+        for i, (t_curr, t_prev) in enumerate(zip(timesteps[:-1], timesteps[1:])):
+            nb = counts[i]
+            m = nb * n
+            kw = inputs.get(nb)
+            if kw is None:
+                kw = inputs[nb] = {k: (v[:m] if torch.is_tensor(v) and v.ndim >= 1 and v.shape[0] == 3 * n else v) for k, v in kwargs.items()}
+                kw.update(img=img3[:m], cond=cond3[:m], timesteps=t_vec[:m], guidance=guidance_vec[:m])
+            t_vec.fill_(t_curr)
+            dst = kw["img"]
+            if _ops().copy_rows_ok(x, dst[:n]):
+                for j in ([None] if n == 1 else range(nb)):
+                    _ops().copy_rows(x, dst if j is None else dst[j * n:(j + 1) * n])
+            else:
+                dst.view(nb, *x.shape).copy_(x.unsqueeze(0).expand(nb, *x.shape))
+            st = model.step_head(sc, **kw)
+            d = math.inf if i == 0 else model.step_distance(sc)       # the one host synchronisation of a step
+            computed, acc = step_cache_decide(i, n_steps, d, acc, threshold, coefficients, all(sc.have[:m]))
+            pred = model.step_run(sc, st) if computed else model.step_skip(sc, st)
+            record.append((d, acc, computed))
+            text_gs = get_oscillation_gs(guidance, i) if text_osci else guidance
+            image_gs = get_oscillation_gs(guidance_img, i) if image_osci else guidance_img
+            gvec = None
+            if nb == 3 and image_gs > 1.0 and scale_temporal_osci:
+                upper = torch.linspace(image_gs, 1.0, len(timesteps))[i]
+                ramp = torch.linspace(1.0, float(upper), t)[None, None, :, None, None].repeat(b, c, 1, h_, w_)
+                gvec = pack(ramp, patch_size=patch_size).to(dev, torch.float32).contiguous()
+                image_gs = 1.0
+            pred = pred.to(torch.bfloat16).contiguous()
+            if pruned:
+                _ops().cfg_euler_nb(pred, nb, x, x_next, float(text_gs), float(image_gs), float(t_prev - t_curr), gvec)
+            else:
+                _ops().cfg_euler(pred, x, x_next, float(text_gs), float(image_gs), float(t_prev - t_curr), gvec)
+            x, x_next = x_next, x
+        return x
+
     def prepare_guidance(self, text: list, optional_models: dict, device, dtype, **kwargs):
         ret = {"guidance_img": kwargs.pop("guidance_img")}
         neg = kwargs.get("neg", None)
@@ -346,6 +454,10 @@ class DistilledDenoiser:
         timesteps = kwargs.pop("timesteps")
         guidance = kwargs.pop("guidance")
         hip_graph = bool(kwargs.pop("hip_graph", False))
+        kwargs.pop("step_cache_coefficients", None)
+        if kwargs.pop("step_cache", None) is not None:
+            # (the keyword only: OSK_STEP_CACHE is I2VDenoiser's default and leaves the image stage of a t2i2v run alone)
+            raise ValueError("step_cache is out of scope for DistilledDenoiser: its loop has no head / blocks / tail split")
         guidance_vec = torch.full((img.shape[0],), guidance, device=img.device, dtype=img.dtype)
         if not hip_graph:
             for t_curr, t_prev in zip(timesteps[:-1], timesteps[1:]):
