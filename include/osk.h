@@ -455,7 +455,8 @@ int osk_attention_merge_into_bf16(void* out, int64_t o_batch_stride, int64_t o_r
  * n_prefix > 0: out 16-byte aligned with strides multiples of 8, workspace required -- osk_attention_window_workspace_bytes(B, H,
  * Lq, hd) is always enough (f32 partials + launch A's lse when the caller keeps none).
  * OSK_EINVAL: n_windows != ceil(Lq / 256), NULL / misaligned table, n_prefix not a multiple of 64 or >= Lk, missing / short
- * workspace with n_prefix > 0, negative or NaN score_bound.  hd in {64, 72, 128} (else OSK_EUNSUPPORTED).  bf16 operands only.
+ * workspace with n_prefix > 0, negative or NaN score_bound.  hd in {64, 72, 128} (else OSK_EUNSUPPORTED).  bf16 operands; the fp8
+ * operand kinds have the entry below.
  * No allocation, no memset, no host synchronisation: capturable in a hipGraph.
  * Cost: work units are always 256 rows (no wide head_dim-72 layout) and the grid's last round is not split along the keys; a
  * unit's time follows its tile count, so the launch ends with its longest windows.  On top of launch A: launch B walks n_prefix
@@ -467,6 +468,36 @@ int osk_attention_fwd_window_bf16(const void* q, int64_t q_batch_stride, int64_t
                                   int B, int H, int Lq, int Lk, int n_prefix, int hd, float scale, int q_prescaled,
                                   int kv_batches, float score_bound, const int32_t* windows, int n_windows,
                                   void* workspace, int64_t workspace_bytes, void* stream);
+/* The same entry in fp8 mode (an additive entry, the version stays 2).  Like the entry above it replaces nothing in the reference
+ * -- opensora/models/mmdit/math.py:22-36 lets every query see every key -- and the arithmetic under the mask is that of
+ * osk_attention_fwd_pv8_bf16 / osk_attention_fwd_qk8_bf16.  Mask, exactly as above: keys [0, n_prefix) are seen by every query; rows
+ * 256 i .. 256 i + 255 see, of the body keys [n_prefix, Lk), the 64-key tiles [first, first + count) of windows[i] and NOTHING
+ * else; the kernel clamps a table row as above.  Arguments: those of osk_attention_fwd_window_bf16 without score_bound (the fp8
+ * kernels have no bounded body), plus the scales and
+ *   mode  OSK_ATTN_PV8  hd in {72, 128}: k = the bf16 K [Bkv, Lk, H*hd] view, read in place (strides in elements);
+ *                       vt = the e4m3 V^T of ALL Lk keys from osk_v_transpose_fp8, [Bkv, H, RP, Lp], Lp = round_up(Lk, 64);
+ *                       v_scale f32 [Bkv, H]; k_scale ignored.
+ *         OSK_ATTN_QK8  hd == 128 only: k = the e4m3 K of all Lk keys from osk_k_pack_fp8, [Bkv, H, Lp, 128], k_batch_stride in BYTES
+ *                       (a non-negative multiple of 16), k_row_stride = 128 (anything else: OSK_EUNSUPPORTED); k_scale f32 [Bkv, H]
+ *                       = the scales the pack used; vt, v_scale as for OSK_ATTN_PV8.  Q stays bf16 and is quantised in the kernel
+ *                       prologue per query row and head, as osk_attention_fwd_qk8_bf16 states.
+ *         OSK_ATTN_BF16 OSK_EINVAL (that is the entry above).
+ * The call enqueues the launches A, B, M of the entry above on the pv8 / qk8 kernels: A enters K and V^T n_prefix keys in (n_prefix
+ * rows of K; n_prefix bytes along the key axis of every V^T row, the validity row included) and keeps the head and batch strides of
+ * the whole tensors; B walks the prefix from the tensors' origin with the same scales.
+ * n_prefix == 0: launch A alone, workspace may be NULL; with full windows the result is bit-identical to osk_attention_fwd_pv8_bf16
+ * / osk_attention_fwd_qk8_bf16 called without a workspace.  n_prefix > 0: out 16-byte aligned with strides multiples of 8,
+ * workspace required -- osk_attention_window_workspace_bytes(B, H, Lq, hd) is always enough.  lse: f32 [B, H, Lq] or NULL.
+ * OSK_EINVAL: the list of the entry above, NULL or misaligned scales (v_scale; k_scale in qk8 mode), a k_batch_stride that is no
+ * non-negative multiple of 16 in qk8 mode, a mode other than the two.  OSK_EUNSUPPORTED: hd outside the mode's set, k_row_stride
+ * != 128 in qk8 mode.  A refused call launches nothing.  No allocation, no memset, no host synchronisation: capturable in a hipGraph.
+ * Cost: as above; the V^T pack (and in qk8 mode the K pack) in front of the call still touch every key.  profiles/attn_window.md. */
+int osk_attention_fwd_window_fp8_bf16(const void* q, int64_t q_batch_stride, int64_t q_row_stride,
+                                      const void* k, int64_t k_batch_stride, int64_t k_row_stride, const float* k_scale,
+                                      const void* vt, const float* v_scale, void* out, int64_t o_batch_stride,
+                                      int64_t o_row_stride, float* lse, int B, int H, int Lq, int Lk, int n_prefix, int hd,
+                                      float scale, int q_prescaled, int kv_batches, int mode, const int32_t* windows,
+                                      int n_windows, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- short-sequence attention with an optional ALiBi bias (the STDiT-generation block's temporal
  * self-attention over T <= 64 frames, B * H * W independent sequences, "RoPE/ALiBi" in BASELINE.json's north_star).  The mounted

@@ -61,6 +61,8 @@ SIGNATURES = {
     "osk_attention_window_workspace_bytes": [_i32, _i32, _i32, _i32],
     "osk_attention_fwd_window_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
                                       _f32, _i32, _i32, _f32, _vp, _i32, _vp, _i64, _vp],
+    "osk_attention_fwd_window_fp8_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32,
+                                          _i32, _i32, _f32, _i32, _i32, _i32, _vp, _i32, _vp, _i64, _vp],
     "osk_rownorm2_max_bf16": [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp],
     "osk_attention_workspace_bytes": [],
     "osk_v_scale_fp8": [_vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _vp],
@@ -907,6 +909,58 @@ def attention_fwd_qk8(q: torch.Tensor, k8: torch.Tensor, k_scale: torch.Tensor, 
                                               out.stride(0), out.stride(1), _p(lse), B, H, Lq, n_seg, seg_len, hd, scale,
                                               int(q_prescaled), kv_batches, _p(workspace),
                                               0 if workspace is None else workspace.numel(), _stream()), "osk_attention_fwd_qk8_bf16")
+    return out
+
+
+ATTN_MODES = {"pv8": 1, "qk8": 2}     # OSK_ATTN_PV8, OSK_ATTN_QK8 of include/osk.h
+
+
+def attention_fwd_window_fp8(q: torch.Tensor, k: torch.Tensor, k_scale: torch.Tensor | None, vt8: torch.Tensor, v_scale: torch.Tensor,
+                             out: torch.Tensor, H: int, hd: int, scale: float, *, n_prefix: int, windows: torch.Tensor, mode: str,
+                             lse=None, q_prescaled: bool = False, kv_batches: int = 0, workspace: torch.Tensor | None = None,
+                             Lk: int | None = None):
+    """attention_fwd_window on fp8 operands (osk_attention_fwd_window_fp8_bf16): the same mask -- query block i sees keys
+    [0, n_prefix) and the body tiles windows[i] = (first, count), nothing else -- with the kernels of attention_fwd_pv8 (mode "pv8",
+    head_dim 72 / 128: k the bf16 [Bkv, Lk, H*hd] view, k_scale None) or attention_fwd_qk8 (mode "qk8", head_dim 128: k = k8
+    [Bkv, H, Lp, 128] from k_pack_fp8 of all Lk keys, k_scale its scales, Lk = the key count -- k8 only shows Lp, as seg_len of
+    attention_fwd_qk8).  vt8 / v_scale: v_transpose_fp8 of all Lk keys.  windows, lse, workspace as attention_fwd_window."""
+    if mode not in ATTN_MODES:
+        raise ValueError(f"attention_fwd_window_fp8: mode {mode!r}, expected 'pv8' or 'qk8'")
+    assert q.dim() == 3 and out.dim() == 3 and q.shape == out.shape and q.shape[2] == H * hd, (q.shape, out.shape, H, hd)
+    assert q.dtype == torch.bfloat16 and out.dtype == torch.bfloat16 and q.stride(2) == 1 and out.stride(2) == 1, (q.dtype, out.dtype)
+    B, Lq, _ = q.shape
+    Bkv = kv_batches or B
+    assert v_scale.dtype == torch.float32 and v_scale.is_contiguous() and v_scale.numel() == Bkv * H, "v_scale: f32 [Bkv, H]"
+    if mode == "qk8":
+        assert hd == 128, f"the fp8 QK^T kernel exists for head_dim 128 only, not {hd}"
+        assert k.dtype == torch.uint8 and k.dim() == 4 and k.stride(3) == 1 and k.stride(2) == 128, (k.dtype, k.shape, k.stride())
+        assert vt8.dim() == 4 and tuple(k.shape) == (Bkv, H, vt8.shape[-1], 128) and k.stride(1) == k.shape[2] * 128, (k.shape, k.stride())
+        assert k.data_ptr() % 16 == 0 and k.stride(0) % 16 == 0, (k.stride(), k.data_ptr() % 16)
+        assert k_scale is not None and k_scale.dtype == torch.float32 and k_scale.is_contiguous() and k_scale.numel() == Bkv * H, "k_scale: f32 [Bkv, H]"
+        kbs, krs = k.stride(0), 128
+        assert Lk is not None and (Lk + 63) // 64 * 64 == k.shape[2], f"qk8: Lk = the key count (k8 only shows Lp = {k.shape[2]}); got {Lk}"
+    else:
+        assert k.dtype == torch.bfloat16 and k.dim() == 3 and k.shape[2] == H * hd and k.stride(2) == 1, (k.dtype, k.shape, k.stride())
+        assert k.stride(0) % 8 == 0 and k.stride(1) % 8 == 0 and k.data_ptr() % 16 == 0, (k.stride(), k.data_ptr() % 16)
+        kbs, krs = k.stride(0), k.stride(1)
+        assert Lk is None or Lk == k.shape[1], (Lk, k.shape)
+        Lk = k.shape[1]
+    assert q.stride(0) % 8 == 0 and q.stride(1) % 8 == 0 and q.data_ptr() % 16 == 0, (q.stride(), q.data_ptr() % 16)
+    check_window_table(windows, Lq, Lk, n_prefix)
+    assert vt8.dtype == torch.uint8 and vt8.is_contiguous() and vt8.data_ptr() % 16 == 0, (vt8.dtype, vt8.stride())
+    assert vt8.shape[-1] == (Lk + 63) // 64 * 64 and vt8.shape[-2] == vt8_rows(hd), (vt8.shape, Lk, hd)
+    if lse is not None:
+        assert lse.dtype == torch.float32 and lse.is_contiguous() and tuple(lse.shape) == (B, H, Lq), (lse.dtype, lse.shape)
+    if n_prefix > 0 and workspace is None:
+        workspace = attention_window_workspace(B, H, Lq, hd, q.device)
+    win = _window_on_device(windows, q.device)
+    with _attn_prof():
+        _check(lib.osk_attention_fwd_window_fp8_bf16(q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), kbs, krs, _p(k_scale),
+                                                     vt8.data_ptr(), v_scale.data_ptr(), out.data_ptr(), out.stride(0), out.stride(1),
+                                                     _p(lse), B, H, Lq, Lk, n_prefix, hd, scale, int(q_prescaled), kv_batches,
+                                                     ATTN_MODES[mode], win.data_ptr(), win.shape[0], _p(workspace),
+                                                     0 if workspace is None else workspace.numel(), _stream()),
+               "osk_attention_fwd_window_fp8_bf16")
     return out
 
 

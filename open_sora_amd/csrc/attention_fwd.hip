@@ -811,3 +811,76 @@ extern "C" int osk_attention_fwd_window_bf16(const void* q, int64_t q_batch_stri
   b.out = a.out; b.lse = a.lse;
   return osk_attn::launch_merge_into(b, hd, 0.6931471805599453f, st);
 }
+
+// The same entry on the fp8 operands of osk_attention_fwd_pv8_bf16 (mode OSK_ATTN_PV8: bf16 K in place, e4m3 V^T) or
+// osk_attention_fwd_qk8_bf16 (OSK_ATTN_QK8: e4m3 K too, head_dim 128).  The scheme is the one above -- launch A the windowed body into
+// finished rows, launch B the prefix into f32 partials, one in-place merge -- driven through the pv8 / qk8 kernels the way the ragged
+// entry drives them.  What the loops meet is nothing the single-segment tail split does not already hand them: key_part()'s `win` branch
+// gives the loaders a run of tiles (offsets of its first tile, tps = nt = its length, ragged only where it ends in the last tile); the
+// fp8 kernels bake key validity into V^T's row hd (no first-tile LDS mask to write), their slot words see only `ragged`, and the q8 K
+// loader steps whole 64 x 128-byte tiles from k_off = first tile * 64 * krs with krs = 128 (tests/attention_cases.py: p72_1tile_ragged,
+// p72_merge, q128_1tile_ragged_plain, q128_tile_runs_merge run 1- and 2-tile parts, full and ragged).
+// Neither launch goes through dispatch(): launch A keeps rows = 256, tail_first = 0x7fffffff, tail_split = 1 (the table is per 256
+// rows and a windowed unit has a key run of its own; split_tail() would return at p.win anyway, and only launch_shape() -- bf16 mode
+// -- ever picks the wide layout), launch B is the every-unit partial launch.
+extern "C" int osk_attention_fwd_window_fp8_bf16(const void* q, int64_t q_batch_stride, int64_t q_row_stride,
+                                                 const void* k, int64_t k_batch_stride, int64_t k_row_stride, const float* k_scale,
+                                                 const void* vt, const float* v_scale, void* out, int64_t o_batch_stride,
+                                                 int64_t o_row_stride, float* lse, int B, int H, int Lq, int Lk, int n_prefix, int hd,
+                                                 float scale, int q_prescaled, int kv_batches, int mode, const int32_t* windows,
+                                                 int n_windows, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (mode != OSK_ATTN_PV8 && mode != OSK_ATTN_QK8) return OSK_EINVAL;   // (OSK_ATTN_BF16: osk_attention_fwd_window_bf16)
+  if (!windows || ((uintptr_t)windows & 3) || !v_scale || ((uintptr_t)v_scale & 3)) return OSK_EINVAL;
+  if (mode == OSK_ATTN_QK8 && (!k_scale || ((uintptr_t)k_scale & 3) || (k_batch_stride & 15) || k_batch_stride < 0)) return OSK_EINVAL;
+  if (Lq <= 0 || Lk <= 0 || n_windows != (Lq + 255) / 256 || n_prefix < 0 || (n_prefix & 63) || n_prefix >= Lk) return OSK_EINVAL;
+  if (n_prefix > 0) {
+    // the merge reads and writes `out` in 16-byte pieces; the prefix's partials are not optional, so neither is the workspace
+    if (((uintptr_t)out & 15) || (o_batch_stride & 7) || (o_row_stride & 7) || !workspace) return OSK_EINVAL;
+    if (B > 0 && H > 0 && hd > 0 && workspace_bytes < ragged_partial_bytes(B, H, Lq, hd) + (lse ? 0 : ragged_lse_bytes(B, H, Lq)))
+      return OSK_EINVAL;
+  }
+  AttnParams a;
+  int rc = attn_params(a, q, q_batch_stride, q_row_stride, k, 0, k_batch_stride, k_row_stride, vt, 0, 15, out, o_batch_stride,
+                       o_row_stride, lse, B, H, Lq, 1, Lk, hd,
+                       mode == OSK_ATTN_QK8 ? std::initializer_list<int>{128} : std::initializer_list<int>{72, 128}, scale, q_prescaled,
+                       kv_batches, workspace, workspace_bytes);
+  if (rc != OSK_OK) return rc;
+  if (mode == OSK_ATTN_QK8 && k_row_stride != 128) return OSK_EUNSUPPORTED;   // the packed layout: rows of 128 bytes, heads Lp rows apart
+  a.vt = nullptr; a.vt8 = (const unsigned char*)vt; a.v_scale = v_scale;
+  if (mode == OSK_ATTN_QK8) { a.k = nullptr; a.k8 = (const unsigned char*)k; a.k_scale = k_scale; }
+  a.rows = 256;                                  // the table is per 256-row block; tail_first stays off: finished rows
+  // Both launches walk a key range of ONE tensor laid out for all Lk keys: V^T [Bkv, H, RP, Lp] and, in qk8 mode, K [Bkv, H, Lp, 128]
+  // with Lp = round_up(Lk, 64).  The kernels take a head's stride from seg_lp (RP * seg_lp bytes of V^T, seg_lp * 128 of K) and a V^T
+  // row's from seg_lp as well, so seg_lp stays the whole tensor's after set_segments() below, as the bf16 entry keeps it for its V^T.
+  // kbs needs no such care here: it is the caller's batch stride of that one tensor (H * Lp * 128 when packed), which set_segments()
+  // does not touch -- the ragged entry re-derives it only because its last segment is a tensor of its own with another Lp.
+  const int64_t seg_lp = a.seg_lp;
+  AttnParams b = a;
+  // launch A: the body, windowed, entered n_prefix keys in.  bf16 K: n_prefix rows of krs elements.  e4m3 K: n_prefix rows of 128
+  // bytes inside every head's [Lp, 128] block.  e4m3 V^T: n_prefix bytes along the key axis of EVERY row -- the hd dims and the
+  // validity / denominator row hd alike, since all rows of a head share the one base pointer and the row stride seg_lp.  n_prefix is a
+  // multiple of 64, so the body's tiles are tiles of the whole tensor: the key order inside a tile, the repeated last K row and the
+  // zero validity bytes behind key Lk - 1 sit where a launch over Lk - n_prefix keys expects its ragged last tile.
+  if (a.k) a.k += (int64_t)n_prefix * a.krs;
+  if (a.k8) a.k8 += (int64_t)n_prefix * 128;
+  a.vt8 += n_prefix;
+  set_segments(a, 1, Lk - n_prefix);
+  a.seg_lp = (int)seg_lp;
+  a.win = windows;
+  hipStream_t st = (hipStream_t)stream;
+  if (n_prefix == 0) return run_mode(a, hd, mode, st);
+  if (!lse) a.lse = (float*)((char*)workspace + ragged_partial_bytes(B, H, Lq, hd));
+  // launch B: the prefix alone from the tensors' origin -- whole tiles (n_prefix % 64 == 0: never ragged), the same scales, every
+  // unit an f32 partial O + log2-domain lse of all of it (tail_first = 0, tail_split = 1)
+  set_segments(b, 1, n_prefix);
+  b.seg_lp = (int)seg_lp;
+  b.tail_first = 0; b.tail_split = 1;
+  b.ws_o = (float*)workspace;
+  b.ws_lse = b.ws_o + (int64_t)osk_attn::attn_units(b) * 256 * hd;
+  rc = run_mode(a, hd, mode, st);
+  if (rc != 0) return rc;
+  rc = run_mode(b, hd, mode, st);
+  if (rc != 0) return rc;
+  b.out = a.out; b.lse = a.lse;
+  return osk_attn::launch_merge_into(b, hd, 0.6931471805599453f, st);
+}

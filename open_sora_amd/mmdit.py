@@ -731,6 +731,20 @@ def _window_env_default():
     return int(v) if v else None
 
 
+def _window_fp8_ok() -> bool:
+    """does the kernel table have the fp8 frame-window entry?  (looked up like attention_fwd_auto in _joint_attention and
+    kv_scale_fp8 in _sp_qk8: the HIP library always has it -- a missing symbol fails its import -- while a substituted table from
+    before the entry keeps the refusals it was written against)"""
+    return hasattr(_OPS, "attention_fwd_window_fp8")
+
+
+def _window_mode(pv8: bool, qk8: bool, hd: int) -> str:
+    """operand kind of a windowed attention call: what the unwindowed path picks for the same plan and head dim"""
+    if not (pv8 and hd in (72, 128)):
+        return "bf16"
+    return "qk8" if qk8 and hd == 128 else "pv8"
+
+
 def _joint_attention(ws: _Workspace, q: Tensor, k: Tensor, v: Tensor, H: int, hd: int, pv8: bool = False,
                      score_bound: float = 0.0, vt_ready: bool = False, qk8: bool = False):
     """attention() of math.py:22-36 on the joint [txt;img] sequence; the output overwrites the (dead) v slot.
@@ -740,12 +754,31 @@ def _joint_attention(ws: _Workspace, q: Tensor, k: Tensor, v: Tensor, H: int, hd
     if getattr(ws, "attn_window", None) is not None:
         # opt-in frame-window attention: the text keys as the always-attended prefix, the image keys by the table.  The FAST body
         # where the plan's weight-derived bound admits it, else the general body (no auto-dispatched pair for this entry)
-        if pv8:
+        if pv8 and not _window_fp8_ok():
             raise ValueError("frame-window attention has no fp8 kernels: disable enable_fp8() or set_attention_window(None)")
-        if not vt_ready:
-            _OPS.v_transpose(v, ws.vt, H, hd)
         if ws.win_ws is None:
             ws.win_ws = torch.empty(_OPS.attention_window_workspace_bytes(q.shape[0], H, q.shape[1], hd), dtype=torch.uint8, device=q.device)
+        if pv8 and hd in (72, 128):
+            # fp8 mode: the operand preparation of the unwindowed path below (scales on the device, no host synchronisation; the
+            # packs still touch every key), then ONE call of the fp8 window entry.  qk8 at another head dim takes pv8, as there.
+            B = v.shape[0]
+            vt8 = getattr(ws, "vt8", None)
+            if vt8 is None:
+                vt8 = ws.vt8 = torch.empty(B, H, _OPS.vt8_rows(hd), ws.vt.shape[-1], dtype=torch.uint8, device=v.device)
+            sv = v_scale_fp8(v, H, hd)
+            _OPS.v_transpose_fp8(v, sv, vt8, H, hd)
+            kk, sk = k, None
+            if qk8 and hd == 128:
+                kk = getattr(ws, "k8", None)
+                if kk is None or tuple(kk.shape) != _OPS.k8_shape(B, H, k.shape[1], hd):
+                    kk = ws.k8 = torch.empty(_OPS.k8_shape(B, H, k.shape[1], hd), dtype=torch.uint8, device=k.device)
+                sk = v_scale_fp8(k, H, hd)
+                _OPS.k_pack_fp8(k, sk, kk, H, hd)
+            _OPS.attention_fwd_window_fp8(q, kk, sk, vt8, sv, v, H, hd, hd ** -0.5, n_prefix=ws.L_txt, windows=ws.attn_window,
+                                          mode=_window_mode(pv8, qk8, hd), q_prescaled=True, workspace=ws.win_ws, Lk=k.shape[1])
+            return
+        if not vt_ready:
+            _OPS.v_transpose(v, ws.vt, H, hd)
         _OPS.attention_fwd_window(q, k, ws.vt, v, H, hd, hd ** -0.5, n_prefix=ws.L_txt, windows=ws.attn_window, q_prescaled=True,
                                   score_bound=score_bound if 0.0 < score_bound <= SCORE_BOUND_LIMIT else 0.0, workspace=ws.win_ws)
         return
@@ -1098,7 +1131,7 @@ class MMDiTModel(_OskState, nn.Module):
         K is packed after the all-to-all, with no collective.  Recommended for head_dim 128: the attention launch takes
         0.77 - 0.79 of the pv8 time with the K pack counted (A/B spread under 2 %) at the same model-level error; DESIGN.md
         section 4, profiles/attn_qk8.md, profiles/attn_qk8_sp.md (a rank's launch at the sharded shape)."""
-        if on and getattr(self, "_attn_window", None) is not None:
+        if on and getattr(self, "_attn_window", None) is not None and not _window_fp8_ok():
             raise ValueError("enable_fp8: frame-window attention (set_attention_window) has no fp8 kernels; turn it off first")
         for b in list(self.double_blocks) + list(self.single_blocks):
             object.__setattr__(b, "_osk_fp8", bool(on))
@@ -1110,11 +1143,12 @@ class MMDiTModel(_OskState, nn.Module):
     def set_attention_window(self, window_frames="env", frame_tokens: int | None = None):
         """Opt-in frame-window attention, off by default: text keys stay visible to every query, an image query block keeps the
         image keys of its own frames +- window_frames (attention_window_table: a block-granular superset of each row's window) and
-        the attention runs osk_attention_fwd_window_bf16.  frame_tokens: image tokens per latent frame, (h / patch) * (w / patch).
+        the attention runs osk_attention_fwd_window_bf16 -- in fp8 mode (enable_fp8, either order) osk_attention_fwd_window_fp8_bf16
+        on the pv8 / qk8 operands the unwindowed attention of that mode would take.  frame_tokens: image tokens per latent frame, (h / patch) * (w / patch).
         None turns it off; without the argument the environment's OSK_ATTN_WINDOW_FRAMES decides (unset: off).  Exact with respect
         to the mask it states; the reference attends to every key, so outputs DIFFER from it by what the dropped keys carried, and
-        the quality of that on real checkpoints is not measured.  bf16 attention without sequence parallelism
-        only, L_txt % 64 == 0 (checked when a forward sees the text).  The setting is not part of state_dict."""
+        the quality of that on real checkpoints is not measured.  Not under sequence parallelism,
+        L_txt % 64 == 0 (checked when a forward sees the text).  The setting is not part of state_dict."""
         if isinstance(window_frames, str) and window_frames == "env":
             window_frames = _window_env_default()
         if window_frames is None:
@@ -1122,7 +1156,7 @@ class MMDiTModel(_OskState, nn.Module):
             return self
         if int(window_frames) < 0 or frame_tokens is None or int(frame_tokens) <= 0:
             raise ValueError(f"set_attention_window: window_frames >= 0 and frame_tokens > 0 expected; got {window_frames}, {frame_tokens}")
-        if any(getattr(b, "_osk_fp8", False) for b in list(self.double_blocks) + list(self.single_blocks)):
+        if any(getattr(b, "_osk_fp8", False) for b in list(self.double_blocks) + list(self.single_blocks)) and not _window_fp8_ok():
             raise ValueError("set_attention_window: frame-window attention has no fp8 kernels; call enable_fp8(False) first")
         if getattr(self, "_sp", None) is not None:
             raise ValueError("set_attention_window: frame-window attention does not run under sequence parallelism yet")
@@ -1178,6 +1212,11 @@ class MMDiTModel(_OskState, nn.Module):
             t = self._attn_window_table
             window = {"attention_window": {"window_frames": self._attn_window[0], "frame_tokens": self._attn_window[1],
                                            "visited_tile_fraction": None if t is None else window_tile_fraction(t[1], t[0][0], t[0][1])}}
+            # "mode": the operand kind of the windowed calls in fp8 mode, "pv8" | "qk8" (osk_attention_fwd_window_fp8_bf16).  bf16
+            # attention reports no "mode" key: the entry is the one from before fp8 mode had a window, and so is its report
+            mode = _window_mode(any(p.pv8 for p in plans), any(p.qk8 for p in plans), hd)
+            if mode != "bf16" and _window_fp8_ok():
+                window["attention_window"]["mode"] = mode
         return {**ragged, **window, "kv_chunks": chunks, "score_bound_min": min(bounds), "score_bound_max": max(bounds), "bound_limit": SCORE_BOUND_LIMIT, "bodies": bodies,
                 "blocks_on_fast_body": sum(1 for b in bounds if 0.0 < b <= SCORE_BOUND_LIMIT), "blocks": len(bounds),
                 # blocks whose weight-derived bound is too large: FAST / general chosen per (batch, head) on the device from the operands
