@@ -582,16 +582,51 @@ def attention_merge(parts: torch.Tensor, lse: torch.Tensor, out: torch.Tensor, H
     return out
 
 
-def attention_ragged_workspace(B: int, H: int, Lq: int, hd: int, device) -> torch.Tensor:
-    """workspace of attention_fwd_ragged for these query dimensions, one per (device, stream) like attention_workspace(): the f32
-    partials of the last-segment launch, launch A's lse, and the tail-split room of a plain call.  Grows to the largest request."""
+def _grown_workspace(kind: str, need: int, device) -> torch.Tensor:
+    """a uint8 buffer of at least `need` bytes, one per (kind, device, stream) like attention_workspace(); grows to the largest request"""
     dev = torch.device(device)
-    key = ("ragged", str(dev), torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0)
-    need = lib.osk_attention_ragged_workspace_bytes(B, H, Lq, hd)
+    key = (kind, str(dev), torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0)
     ws = _ATTN_WS.get(key)
     if ws is None or ws.numel() < need:
         ws = _ATTN_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
     return ws
+
+
+def attention_ragged_workspace(B: int, H: int, Lq: int, hd: int, device) -> torch.Tensor:
+    """workspace of attention_fwd_ragged for these query dimensions, one per (device, stream) like attention_workspace(): the f32
+    partials of the last-segment launch, launch A's lse, and the tail-split room of a plain call.  Grows to the largest request."""
+    return _grown_workspace("ragged", lib.osk_attention_ragged_workspace_bytes(B, H, Lq, hd), device)
+
+
+def _attn_operands(mode: int, q, k, k_scale, vt, v_scale, out, lse, H: int, hd: int, kv_batches: int, Lk: int, k_seg_stride: int = 0,
+                   vt_seg_stride: int = 0, vt_keys: int | None = None):
+    """the operand facts attention_fwd_ragged, attention_fwd_qk8 and the two window wrappers share, by mode (0 bf16, 1 pv8, 2 qk8:
+    OSK_ATTN_* of include/osk.h, ATTN_MODES): q / out bf16 [B, Lq, H*hd] views; k the bf16 [Bkv, Lk, H*hd] view or, in mode 2, the
+    packed k8 [Bkv, H, Lp, 128] of a segment of Lk keys (byte strides); the mode's f32 [Bkv, H] scale vectors; vt bf16 / vt8 bytes
+    (with vt_keys: [..., hd | vt8_rows(hd), vt_keys]); lse f32 [B, H, Lq] when given.  Returns K's (batch stride, row stride) as
+    the C calls take them."""
+    assert mode != 2 or hd == 128, f"the fp8 QK^T kernel exists for head_dim 128 only, not {hd}"
+    assert q.dim() == 3 and q.shape[2] == H * hd, (q.shape, H, hd)
+    assert q.dtype == torch.bfloat16 and out.dtype == torch.bfloat16 and q.stride(2) == 1 and out.stride(2) == 1, (q.dtype, out.dtype, q.stride(), out.stride())
+    assert q.stride(0) % 8 == 0 and q.stride(1) % 8 == 0 and q.data_ptr() % 16 == 0, (q.stride(), q.data_ptr() % 16)
+    B, Lq, _ = q.shape
+    Bkv = kv_batches or B
+    for s_ in ((), (v_scale,), (k_scale, v_scale))[mode]:
+        assert s_ is not None and s_.dtype == torch.float32 and s_.is_contiguous() and s_.numel() == Bkv * H, "scales: f32 [Bkv, H]"
+    if mode == 2:
+        assert k.dtype == torch.uint8 and k.dim() == 4 and k.stride(3) == 1 and k.stride(2) == 128, (k.dtype, k.shape, k.stride())
+        assert tuple(k.shape) == k8_shape(Bkv, H, Lk, hd) and k.stride(1) == k.shape[2] * 128, (k.shape, k.stride(), Lk)
+        assert k.data_ptr() % 16 == 0 and k.stride(0) % 16 == 0 and k_seg_stride % 16 == 0, (k.stride(), k_seg_stride)
+    else:
+        assert k.dtype == torch.bfloat16 and k.dim() == 3 and k.stride(2) == 1 and k.shape[2] == H * hd, (k.dtype, k.shape, k.stride())
+        assert k.stride(0) % 8 == 0 and k.stride(1) % 8 == 0 and k_seg_stride % 8 == 0 and k.data_ptr() % 16 == 0, (k.stride(), k_seg_stride)
+    assert vt.dtype == (torch.bfloat16 if mode == 0 else torch.uint8) and vt.data_ptr() % 16 == 0, (vt.dtype, vt.data_ptr() % 16)
+    assert vt_seg_stride % (8 if mode == 0 else 16) == 0, vt_seg_stride
+    if vt_keys is not None:
+        assert vt.shape[-2] == (hd if mode == 0 else vt8_rows(hd)) and vt.shape[-1] == vt_keys, (vt.shape, hd, vt_keys)
+    if lse is not None:
+        assert lse.dtype == torch.float32 and lse.is_contiguous() and tuple(lse.shape) == (B, H, Lq), (lse.dtype, lse.shape)
+    return k.stride(0), 128 if mode == 2 else k.stride(1)
 
 
 def attention_fwd_ragged(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Tensor, H: int, hd: int, scale: float, *,
@@ -604,30 +639,14 @@ def attention_fwd_ragged(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out
     k8 [Bkv, H, Lp, 128], byte stride, as attention_fwd_qk8).  The last segment lies n_seg - 1 segment strides in, laid out as a
     tensor of last_seg_len keys of its own (v_transpose / v_transpose_fp8 / k_pack_fp8 of those keys alone).  workspace: from
     attention_ragged_workspace()."""
-    assert q.dim() == 3 and out.dim() == 3 and q.shape == out.shape and q.shape[2] == H * hd, (q.shape, out.shape, H, hd)
-    assert q.dtype == torch.bfloat16 and out.dtype == torch.bfloat16 and q.stride(2) == 1 and out.stride(2) == 1, (q.dtype, out.dtype)
+    assert out.dim() == 3 and q.shape == out.shape, (q.shape, out.shape)
     assert n_seg >= 2 and 1 <= last_seg_len <= seg_len, (n_seg, seg_len, last_seg_len)
-    assert q.stride(0) % 8 == 0 and q.stride(1) % 8 == 0 and q.data_ptr() % 16 == 0, (q.stride(), q.data_ptr() % 16)
     assert out.stride(0) % 8 == 0 and out.stride(1) % 8 == 0 and out.data_ptr() % 16 == 0, (out.stride(), out.data_ptr() % 16)
+    assert k_scale is None or v_scale is not None, "qk8 operands come with both scale vectors"
+    mode = 0 if v_scale is None else (1 if k_scale is None else 2)
+    kbs, krs = _attn_operands(mode, q, k, k_scale, vt, v_scale, out, lse, H, hd, kv_batches, seg_len, k_seg_stride, vt_seg_stride)
     B, Lq, _ = q.shape
     Bkv = kv_batches or B
-    mode = 0 if v_scale is None else (1 if k_scale is None else 2)
-    assert k_scale is None or v_scale is not None, "qk8 operands come with both scale vectors"
-    for s_ in (k_scale, v_scale):
-        assert s_ is None or (s_.dtype == torch.float32 and s_.is_contiguous() and s_.numel() == Bkv * H), "scales: f32 [Bkv, H]"
-    if mode == 2:
-        assert hd == 128 and k.dtype == torch.uint8 and k.dim() == 4 and k.stride(3) == 1 and k.stride(2) == 128, (hd, k.dtype, k.stride())
-        assert tuple(k.shape) == k8_shape(Bkv, H, seg_len, hd) and k.stride(1) == k.shape[2] * 128, (k.shape, k.stride())
-        assert k.data_ptr() % 16 == 0 and k.stride(0) % 16 == 0 and k_seg_stride % 16 == 0, (k.stride(), k_seg_stride)
-        kbs, krs = k.stride(0), 128
-    else:
-        assert k.dtype == torch.bfloat16 and k.dim() == 3 and k.stride(2) == 1 and k.shape[2] == H * hd, (k.dtype, k.shape, k.stride())
-        assert k.stride(0) % 8 == 0 and k.stride(1) % 8 == 0 and k_seg_stride % 8 == 0 and k.data_ptr() % 16 == 0, (k.stride(), k_seg_stride)
-        kbs, krs = k.stride(0), k.stride(1)
-    assert vt.dtype == (torch.bfloat16 if mode == 0 else torch.uint8) and vt.data_ptr() % 16 == 0, (vt.dtype, vt.data_ptr() % 16)
-    assert vt_seg_stride % (8 if mode == 0 else 16) == 0, vt_seg_stride
-    if lse is not None:
-        assert lse.dtype == torch.float32 and lse.is_contiguous() and tuple(lse.shape) == (B, H, Lq), (lse.dtype, lse.shape)
     assert workspace is not None and workspace.dtype == torch.uint8 and workspace.data_ptr() % 16 == 0
     if CHECK_SCORE_BOUND and mode == 0 and score_bound > 0 and not torch.cuda.is_current_stream_capturing():
         _assert_score_bound(q, k, H, hd, scale, n_seg - 1, seg_len, k_seg_stride, q_prescaled, kv_batches, score_bound)
@@ -650,13 +669,7 @@ def attention_window_workspace_bytes(B: int, H: int, Lq: int, hd: int) -> int:
 def attention_window_workspace(B: int, H: int, Lq: int, hd: int, device) -> torch.Tensor:
     """workspace of attention_fwd_window for these query dimensions, one per (device, stream) like attention_workspace(): the f32
     partials of the prefix launch and launch A's lse.  Grows to the largest request."""
-    dev = torch.device(device)
-    key = ("window", str(dev), torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0)
-    need = lib.osk_attention_window_workspace_bytes(B, H, Lq, hd)
-    ws = _ATTN_WS.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _ATTN_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
-    return ws
+    return _grown_workspace("window", lib.osk_attention_window_workspace_bytes(B, H, Lq, hd), device)
 
 
 def check_window_table(windows: torch.Tensor, Lq: int, Lk: int, n_prefix: int) -> None:
@@ -697,6 +710,36 @@ def _window_on_device(windows: torch.Tensor, device) -> torch.Tensor:
     return dev
 
 
+def _attention_window(mode: int, q, k, k_scale, vt, v_scale, out, H, hd, scale, n_prefix, windows, lse, q_prescaled, kv_batches, score_bound,
+                      workspace, Lk):
+    """the body of attention_fwd_window (mode 0) and attention_fwd_window_fp8 (modes 1, 2): checks, table upload, the C call of the mode"""
+    assert out.dim() == 3 and q.shape == out.shape, (q.shape, out.shape)
+    if mode == 2:
+        assert Lk is not None and vt.dim() == 4, f"qk8: Lk = the key count (k8 only shows Lp = {k.shape[2]}); got {Lk}"
+    else:
+        assert Lk is None or Lk == k.shape[1], (Lk, k.shape)
+        Lk = k.shape[1]
+    Lp = (Lk + 63) // 64 * 64
+    kbs, krs = _attn_operands(mode, q, k, k_scale, vt, v_scale, out, lse, H, hd, kv_batches, Lk, vt_keys=Lp)
+    B, Lq, _ = q.shape
+    check_window_table(windows, Lq, Lk, n_prefix)
+    assert vt.is_contiguous(), vt.stride()
+    if n_prefix > 0 and workspace is None:
+        workspace = attention_window_workspace(B, H, Lq, hd, q.device)
+    win = _window_on_device(windows, q.device)
+    if CHECK_SCORE_BOUND and mode == 0 and score_bound > 0 and not torch.cuda.is_current_stream_capturing():
+        _assert_score_bound(q, k, H, hd, scale, 1, Lk, 0, q_prescaled, kv_batches, score_bound)
+    name = "osk_attention_fwd_window_bf16" if mode == 0 else "osk_attention_fwd_window_fp8_bf16"
+    own = (float(score_bound),) if mode == 0 else (mode,)          # the argument between kv_batches and the table
+    fp8 = ((_p(k_scale),), (v_scale.data_ptr(),)) if mode else ((), ())   # the scale vectors behind K's strides and behind V^T
+    with _attn_prof():
+        _check(getattr(lib, name)(q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), kbs, krs, *fp8[0], vt.data_ptr(), *fp8[1],
+                                  out.data_ptr(), out.stride(0), out.stride(1), _p(lse), B, H, Lq, Lk, n_prefix, hd, scale,
+                                  int(q_prescaled), kv_batches, *own, win.data_ptr(), win.shape[0], _p(workspace),
+                                  0 if workspace is None else workspace.numel(), _stream()), name)
+    return out
+
+
 def attention_fwd_window(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Tensor, H: int, hd: int, scale: float, *,
                          n_prefix: int, windows: torch.Tensor, lse=None, q_prescaled: bool = False, kv_batches: int = 0,
                          score_bound: float = 0.0, workspace: torch.Tensor | None = None):
@@ -705,27 +748,8 @@ def attention_fwd_window(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out
     one key segment: k bf16 [Bkv, Lk, H*hd] view, vt = v_transpose of all Lk keys.  windows: HOST int32 [ceil(Lq / 256), 2],
     validated here (ValueError) and uploaded once per content.  workspace: from attention_window_workspace(); needed when
     n_prefix > 0 (taken from there when None)."""
-    assert q.dim() == 3 and out.dim() == 3 and q.shape == out.shape and q.shape[2] == H * hd, (q.shape, out.shape, H, hd)
-    assert q.dtype == torch.bfloat16 and k.dtype == torch.bfloat16 and vt.dtype == torch.bfloat16 and out.dtype == torch.bfloat16
-    assert k.dim() == 3 and k.shape[2] == H * hd and q.stride(2) == 1 and k.stride(2) == 1 and out.stride(2) == 1, (k.shape, q.stride(), k.stride())
-    B, Lq, _ = q.shape
-    Lk = k.shape[1]
-    check_window_table(windows, Lq, Lk, n_prefix)
-    assert vt.is_contiguous() and vt.shape[-1] == (Lk + 63) // 64 * 64 and vt.shape[-2] == hd, (vt.shape, Lk, hd)
-    if lse is not None:
-        assert lse.dtype == torch.float32 and lse.is_contiguous() and tuple(lse.shape) == (B, H, Lq), (lse.dtype, lse.shape)
-    if n_prefix > 0 and workspace is None:
-        workspace = attention_window_workspace(B, H, Lq, hd, q.device)
-    win = _window_on_device(windows, q.device)
-    if CHECK_SCORE_BOUND and score_bound > 0 and not torch.cuda.is_current_stream_capturing():
-        _assert_score_bound(q, k, H, hd, scale, 1, Lk, 0, q_prescaled, kv_batches, score_bound)
-    with _attn_prof():
-        _check(lib.osk_attention_fwd_window_bf16(q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1),
-                                                 vt.data_ptr(), out.data_ptr(), out.stride(0), out.stride(1), _p(lse), B, H, Lq, Lk,
-                                                 n_prefix, hd, scale, int(q_prescaled), kv_batches, float(score_bound), win.data_ptr(),
-                                                 win.shape[0], _p(workspace), 0 if workspace is None else workspace.numel(), _stream()),
-               "osk_attention_fwd_window_bf16")
-    return out
+    return _attention_window(0, q, k, None, vt, None, out, H, hd, scale, n_prefix, windows, lse, q_prescaled, kv_batches, score_bound,
+                             workspace, None)
 
 
 def attention_merge_into(out: torch.Tensor, lse: torch.Tensor, o_b: torch.Tensor, lse_b: torch.Tensor, H: int, hd: int) -> torch.Tensor:
@@ -891,20 +915,12 @@ def attention_fwd_qk8(q: torch.Tensor, k8: torch.Tensor, k_scale: torch.Tensor, 
                       workspace: torch.Tensor | None = None):
     """attention_fwd_pv8 with QK^T on the fp8 MFMA as well (head_dim 128): k8 / k_scale from k_pack_fp8 -- k8 is segment 0's
     [Bkv, H, Lp, 128] tensor, further segments k_seg_stride BYTES apart; seg_len = keys per segment (k8 only shows Lp)."""
-    assert hd == 128, f"the fp8 QK^T kernel exists for head_dim 128 only, not {hd}"
-    assert q.dtype == torch.bfloat16 and out.dtype == torch.bfloat16 and q.dim() == 3 and q.shape[2] == H * hd, (q.dtype, out.dtype, q.shape)
-    assert q.stride(2) == 1 and out.stride(2) == 1, (q.stride(), out.stride())
-    B = q.shape[0]
-    Bkv = kv_batches or B
-    assert k8.dtype == torch.uint8 and k8.dim() == 4 and k8.stride(3) == 1 and k8.stride(2) == 128, (k8.dtype, k8.shape, k8.stride())
-    assert tuple(k8.shape) == k8_shape(Bkv, H, seg_len, hd) and k8.stride(1) == k8.shape[2] * 128, (k8.shape, k8.stride())
-    assert k8.data_ptr() % 16 == 0 and k8.stride(0) % 16 == 0 and k_seg_stride % 16 == 0, (k8.stride(), k_seg_stride)
-    for s_ in (k_scale, v_scale):
-        assert s_.dtype == torch.float32 and s_.is_contiguous() and s_.numel() == Bkv * H, (s_.dtype, s_.shape)
-    assert vt8.dtype == torch.uint8 and vt8.shape[-2] == vt8_rows(hd) and vt8.shape[-1] == k8.shape[2], (vt8.dtype, vt8.shape)
-    Lq = q.shape[1]
+    # (lse: this wrapper has never looked at its shape)
+    kbs, krs = _attn_operands(2, q, k8, k_scale, vt8, v_scale, out, None, H, hd, kv_batches, seg_len, k_seg_stride, vt_seg_stride,
+                              vt_keys=(seg_len + 63) // 64 * 64)
+    B, Lq, _ = q.shape
     with _attn_prof():
-        _check(lib.osk_attention_fwd_qk8_bf16(q.data_ptr(), q.stride(0), q.stride(1), k8.data_ptr(), k_seg_stride, k8.stride(0), 128,
+        _check(lib.osk_attention_fwd_qk8_bf16(q.data_ptr(), q.stride(0), q.stride(1), k8.data_ptr(), k_seg_stride, kbs, krs,
                                               k_scale.data_ptr(), vt8.data_ptr(), vt_seg_stride, v_scale.data_ptr(), out.data_ptr(),
                                               out.stride(0), out.stride(1), _p(lse), B, H, Lq, n_seg, seg_len, hd, scale,
                                               int(q_prescaled), kv_batches, _p(workspace),
@@ -926,42 +942,8 @@ def attention_fwd_window_fp8(q: torch.Tensor, k: torch.Tensor, k_scale: torch.Te
     attention_fwd_qk8).  vt8 / v_scale: v_transpose_fp8 of all Lk keys.  windows, lse, workspace as attention_fwd_window."""
     if mode not in ATTN_MODES:
         raise ValueError(f"attention_fwd_window_fp8: mode {mode!r}, expected 'pv8' or 'qk8'")
-    assert q.dim() == 3 and out.dim() == 3 and q.shape == out.shape and q.shape[2] == H * hd, (q.shape, out.shape, H, hd)
-    assert q.dtype == torch.bfloat16 and out.dtype == torch.bfloat16 and q.stride(2) == 1 and out.stride(2) == 1, (q.dtype, out.dtype)
-    B, Lq, _ = q.shape
-    Bkv = kv_batches or B
-    assert v_scale.dtype == torch.float32 and v_scale.is_contiguous() and v_scale.numel() == Bkv * H, "v_scale: f32 [Bkv, H]"
-    if mode == "qk8":
-        assert hd == 128, f"the fp8 QK^T kernel exists for head_dim 128 only, not {hd}"
-        assert k.dtype == torch.uint8 and k.dim() == 4 and k.stride(3) == 1 and k.stride(2) == 128, (k.dtype, k.shape, k.stride())
-        assert vt8.dim() == 4 and tuple(k.shape) == (Bkv, H, vt8.shape[-1], 128) and k.stride(1) == k.shape[2] * 128, (k.shape, k.stride())
-        assert k.data_ptr() % 16 == 0 and k.stride(0) % 16 == 0, (k.stride(), k.data_ptr() % 16)
-        assert k_scale is not None and k_scale.dtype == torch.float32 and k_scale.is_contiguous() and k_scale.numel() == Bkv * H, "k_scale: f32 [Bkv, H]"
-        kbs, krs = k.stride(0), 128
-        assert Lk is not None and (Lk + 63) // 64 * 64 == k.shape[2], f"qk8: Lk = the key count (k8 only shows Lp = {k.shape[2]}); got {Lk}"
-    else:
-        assert k.dtype == torch.bfloat16 and k.dim() == 3 and k.shape[2] == H * hd and k.stride(2) == 1, (k.dtype, k.shape, k.stride())
-        assert k.stride(0) % 8 == 0 and k.stride(1) % 8 == 0 and k.data_ptr() % 16 == 0, (k.stride(), k.data_ptr() % 16)
-        kbs, krs = k.stride(0), k.stride(1)
-        assert Lk is None or Lk == k.shape[1], (Lk, k.shape)
-        Lk = k.shape[1]
-    assert q.stride(0) % 8 == 0 and q.stride(1) % 8 == 0 and q.data_ptr() % 16 == 0, (q.stride(), q.data_ptr() % 16)
-    check_window_table(windows, Lq, Lk, n_prefix)
-    assert vt8.dtype == torch.uint8 and vt8.is_contiguous() and vt8.data_ptr() % 16 == 0, (vt8.dtype, vt8.stride())
-    assert vt8.shape[-1] == (Lk + 63) // 64 * 64 and vt8.shape[-2] == vt8_rows(hd), (vt8.shape, Lk, hd)
-    if lse is not None:
-        assert lse.dtype == torch.float32 and lse.is_contiguous() and tuple(lse.shape) == (B, H, Lq), (lse.dtype, lse.shape)
-    if n_prefix > 0 and workspace is None:
-        workspace = attention_window_workspace(B, H, Lq, hd, q.device)
-    win = _window_on_device(windows, q.device)
-    with _attn_prof():
-        _check(lib.osk_attention_fwd_window_fp8_bf16(q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), kbs, krs, _p(k_scale),
-                                                     vt8.data_ptr(), v_scale.data_ptr(), out.data_ptr(), out.stride(0), out.stride(1),
-                                                     _p(lse), B, H, Lq, Lk, n_prefix, hd, scale, int(q_prescaled), kv_batches,
-                                                     ATTN_MODES[mode], win.data_ptr(), win.shape[0], _p(workspace),
-                                                     0 if workspace is None else workspace.numel(), _stream()),
-               "osk_attention_fwd_window_fp8_bf16")
-    return out
+    return _attention_window(ATTN_MODES[mode], q, k, k_scale, vt8, v_scale, out, H, hd, scale, n_prefix, windows, lse, q_prescaled,
+                             kv_batches, 0.0, workspace, Lk)
 
 
 def copy_rows_ok(src: torch.Tensor, dst: torch.Tensor) -> bool:

@@ -216,6 +216,38 @@ static int dispatch(AttnParams& p, int hd, int mode, void* workspace, int64_t wo
   return then_merge(run_mode(p, hd, mode, st), p, hd, st);
 }
 
+// The operands of a call by mode (OSK_ATTN_* of include/osk.h), in front of attn_params(): the mode's OSK_EINVAL checks, attn_params() with
+// the mode's V^T stride mask (7: bf16, elements; 15: e4m3, bytes) and head dims, the mode's OSK_EUNSUPPORTED check, then K and V^T retagged
+// as the kernel family reads them and the bound set.  k_scale / v_scale of another mode are ignored; score_bound is checked in every mode
+// and used in OSK_ATTN_BF16 (an entry without one passes 0).  v_scale_mask: 3, the alignment of an f32 vector -- osk_attention_fwd_pv8_bf16
+// alone has never checked it and passes 0.  Status precedence as attn_params states it: an entry makes its own OSK_EINVAL checks first.
+static int mode_params(AttnParams& p, int mode, const float* k_scale, const float* v_scale, uintptr_t v_scale_mask, float score_bound,
+                       const void* q, int64_t q_batch_stride, int64_t q_row_stride, const void* k, int64_t k_seg_stride,
+                       int64_t k_batch_stride, int64_t k_row_stride, const void* vt, int64_t vt_seg_stride, void* out,
+                       int64_t o_batch_stride, int64_t o_row_stride, float* lse, int B, int H, int Lq, int n_seg, int seg_len, int hd,
+                       float scale, int q_prescaled, int kv_batches, const void* workspace, int64_t workspace_bytes) {
+  using hds = std::initializer_list<int>;
+  if (mode != OSK_ATTN_BF16 && mode != OSK_ATTN_PV8 && mode != OSK_ATTN_QK8) return OSK_EINVAL;
+  if (!(score_bound >= 0.f)) return OSK_EINVAL;   // (also rejects NaN)
+  if (mode != OSK_ATTN_BF16 && (!v_scale || ((uintptr_t)v_scale & v_scale_mask))) return OSK_EINVAL;
+  if (mode == OSK_ATTN_QK8 && (!k_scale || ((uintptr_t)k_scale & 3) || (k_seg_stride & 15) || (k_batch_stride & 15) || k_seg_stride < 0 ||
+                               k_batch_stride < 0))
+    return OSK_EINVAL;
+  const int rc = attn_params(p, q, q_batch_stride, q_row_stride, k, k_seg_stride, k_batch_stride, k_row_stride, vt, vt_seg_stride,
+                             mode == OSK_ATTN_BF16 ? 7 : 15, out, o_batch_stride, o_row_stride, lse, B, H, Lq, n_seg, seg_len, hd,
+                             mode == OSK_ATTN_BF16 ? hds{64, 72, 128} : mode == OSK_ATTN_PV8 ? hds{72, 128} : hds{128}, scale, q_prescaled,
+                             kv_batches, workspace, workspace_bytes);
+  if (rc != OSK_OK) return rc;
+  if (mode == OSK_ATTN_QK8 && k_row_stride != 128) return OSK_EUNSUPPORTED;   // the packed layout: rows of 128 bytes, heads seg_lp rows apart
+  if (mode == OSK_ATTN_BF16) {
+    p.bound = bound_to_bf16_up(score_bound);
+  } else {
+    p.vt = nullptr; p.vt8 = (const unsigned char*)vt; p.v_scale = v_scale;
+    if (mode == OSK_ATTN_QK8) { p.k = nullptr; p.k8 = (const unsigned char*)k; p.k_scale = k_scale; }
+  }
+  return OSK_OK;
+}
+
 extern "C" int osk_attention_fwd_bounded_bf16(const void* q, int64_t q_batch_stride, int64_t q_row_stride,
                                          const void* k, int64_t k_seg_stride, int64_t k_batch_stride,
                                          int64_t k_row_stride, const void* vt, int64_t vt_seg_stride,
@@ -223,13 +255,11 @@ extern "C" int osk_attention_fwd_bounded_bf16(const void* q, int64_t q_batch_str
                                          float* lse, int B, int H, int Lq, int n_seg, int seg_len, int hd,
                                          float scale, int q_prescaled, int kv_batches, float score_bound,
                                          void* workspace, int64_t workspace_bytes, void* stream) {
-  if (!(score_bound >= 0.f)) return OSK_EINVAL;   // (also rejects NaN)
   AttnParams p;
-  const int rc = attn_params(p, q, q_batch_stride, q_row_stride, k, k_seg_stride, k_batch_stride, k_row_stride, vt, vt_seg_stride, 7,
-                             out, o_batch_stride, o_row_stride, lse, B, H, Lq, n_seg, seg_len, hd, {64, 72, 128}, scale, q_prescaled,
-                             kv_batches, workspace, workspace_bytes);
+  const int rc = mode_params(p, OSK_ATTN_BF16, nullptr, nullptr, 3, score_bound, q, q_batch_stride, q_row_stride, k, k_seg_stride,
+                             k_batch_stride, k_row_stride, vt, vt_seg_stride, out, o_batch_stride, o_row_stride, lse, B, H, Lq, n_seg,
+                             seg_len, hd, scale, q_prescaled, kv_batches, workspace, workspace_bytes);
   if (rc != OSK_OK) return rc;
-  p.bound = bound_to_bf16_up(score_bound);
   return dispatch(p, hd, OSK_ATTN_BF16, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -585,13 +615,11 @@ extern "C" int osk_attention_fwd_pv8_bf16(const void* q, int64_t q_batch_stride,
                                           float* lse, int B, int H, int Lq, int n_seg, int seg_len, int hd,
                                           float scale, int q_prescaled, int kv_batches, void* workspace,
                                           int64_t workspace_bytes, void* stream) {
-  if (!v_scale) return OSK_EINVAL;
   AttnParams p;
-  int rc = attn_params(p, q, q_batch_stride, q_row_stride, k, k_seg_stride, k_batch_stride, k_row_stride, vt8, vt8_seg_stride, 15,
-                       out, o_batch_stride, o_row_stride, lse, B, H, Lq, n_seg, seg_len, hd, {72, 128}, scale, q_prescaled,
-                       kv_batches, workspace, workspace_bytes);
+  const int rc = mode_params(p, OSK_ATTN_PV8, nullptr, v_scale, /* v_scale_mask: null is all this entry checks */ 0, 0.f, q, q_batch_stride,
+                             q_row_stride, k, k_seg_stride, k_batch_stride, k_row_stride, vt8, vt8_seg_stride, out, o_batch_stride,
+                             o_row_stride, lse, B, H, Lq, n_seg, seg_len, hd, scale, q_prescaled, kv_batches, workspace, workspace_bytes);
   if (rc != OSK_OK) return rc;
-  p.vt = nullptr; p.vt8 = (const unsigned char*)vt8; p.v_scale = v_scale;
   return dispatch(p, hd, OSK_ATTN_PV8, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -662,16 +690,11 @@ extern "C" int osk_attention_fwd_qk8_bf16(const void* q, int64_t q_batch_stride,
                                           float* lse, int B, int H, int Lq, int n_seg, int seg_len, int hd,
                                           float scale, int q_prescaled, int kv_batches, void* workspace,
                                           int64_t workspace_bytes, void* stream) {
-  if (!v_scale || !k_scale || ((uintptr_t)k_scale & 3) || ((uintptr_t)v_scale & 3)) return OSK_EINVAL;
-  if ((k8_seg_stride & 15) || (k8_batch_stride & 15) || k8_seg_stride < 0 || k8_batch_stride < 0) return OSK_EINVAL;
   AttnParams p;
-  int rc = attn_params(p, q, q_batch_stride, q_row_stride, k8, k8_seg_stride, k8_batch_stride, k8_row_stride, vt8, vt8_seg_stride, 15,
-                       out, o_batch_stride, o_row_stride, lse, B, H, Lq, n_seg, seg_len, hd, {128}, scale, q_prescaled,
-                       kv_batches, workspace, workspace_bytes);
+  const int rc = mode_params(p, OSK_ATTN_QK8, k_scale, v_scale, 3, 0.f, q, q_batch_stride, q_row_stride, k8, k8_seg_stride, k8_batch_stride,
+                             k8_row_stride, vt8, vt8_seg_stride, out, o_batch_stride, o_row_stride, lse, B, H, Lq, n_seg, seg_len, hd, scale,
+                             q_prescaled, kv_batches, workspace, workspace_bytes);
   if (rc != OSK_OK) return rc;
-  if (k8_row_stride != 128) return OSK_EUNSUPPORTED;   // the packed layout: rows of 128 bytes, heads seg_lp rows apart
-  p.k = nullptr; p.k8 = (const unsigned char*)k8; p.k_scale = k_scale;
-  p.vt = nullptr; p.vt8 = (const unsigned char*)vt8; p.v_scale = v_scale;
   return dispatch(p, hd, OSK_ATTN_QK8, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -691,6 +714,46 @@ extern "C" int64_t osk_attention_ragged_workspace_bytes(int B, int H, int Lq, in
   return ragged_partial_bytes(B, H, Lq, hd) + ragged_lse_bytes(B, H, Lq) + osk_attention_workspace_bytes();
 }
 
+// ---- the two-launch scheme the ragged entry and the window entries share: launch A writes finished rows, launch B -- over other keys --
+// writes an f32 partial per unit, attn_merge_into_kernel folds B into A's rows in place.
+// workspace: [f32 partials of launch B | lse of launch A when the caller keeps none | the rest: a tail split of launch A's own]
+//
+// What a call of the scheme must satisfy, checked with the entry's other OSK_EINVAL checks (in front of mode_params(), so that a malformed
+// call is reported as malformed whatever head dim it asks for): the merge reads and writes `out` in 16-byte pieces, and the partials are
+// not optional, so neither is the workspace.
+static bool merge_args_ok(const void* out, int64_t o_batch_stride, int64_t o_row_stride, const float* lse, int B, int H, int Lq, int hd,
+                          const void* workspace, int64_t workspace_bytes) {
+  if (((uintptr_t)out & 15) || (o_batch_stride & 7) || (o_row_stride & 7) || !workspace) return false;
+  return !(B > 0 && H > 0 && Lq > 0 && hd > 0 && workspace_bytes < ragged_partial_bytes(B, H, Lq, hd) + (lse ? 0 : ragged_lse_bytes(B, H, Lq)));
+}
+
+static float* borrowed_lse(void* workspace, int B, int H, int Lq, int hd) {
+  return (float*)((char*)workspace + ragged_partial_bytes(B, H, Lq, hd));
+}
+
+// a parameter block -> the every-unit partial launch: 256-row units, each writes an f32 partial O + the log2-domain lse of its whole key range
+static void partial_launch(AttnParams& p, int hd, void* workspace) {
+  p.rows = 256;
+  p.tail_first = 0; p.tail_split = 1;
+  p.ws_o = (float*)workspace;
+  p.ws_lse = p.ws_o + (int64_t)osk_attn::attn_units(p) * 256 * hd;
+}
+
+// launch A (finished rows; its lse borrowed from the workspace when the caller keeps none), launch B as the partial launch, the merge.
+// dispatch_a: A goes through dispatch() with the rest of the workspace, else it is launched as the caller shaped it.
+static int run_pair(AttnParams& a, AttnParams& b, int hd, int mode, bool dispatch_a, void* workspace, int64_t workspace_bytes, hipStream_t st) {
+  const int64_t used = ragged_partial_bytes(a.B, a.H, a.Lq, hd) + (a.lse ? 0 : ragged_lse_bytes(a.B, a.H, a.Lq));
+  if (!a.lse) a.lse = borrowed_lse(workspace, a.B, a.H, a.Lq, hd);
+  partial_launch(b, hd, workspace);
+  int rc = dispatch_a ? dispatch(a, hd, mode, workspace_bytes > used ? (char*)workspace + used : nullptr, workspace_bytes - used, st)
+                      : run_mode(a, hd, mode, st);
+  if (rc != 0) return rc;
+  rc = run_mode(b, hd, mode, st);
+  if (rc != 0) return rc;
+  b.out = a.out; b.lse = a.lse;
+  return osk_attn::launch_merge_into(b, hd, 0.6931471805599453f, st);
+}
+
 extern "C" int osk_attention_fwd_ragged_bf16(const void* q, int64_t q_batch_stride, int64_t q_row_stride,
                                              const void* k, int64_t k_seg_stride, int64_t k_batch_stride, int64_t k_row_stride,
                                              const float* k_scale, const void* vt, int64_t vt_seg_stride, const float* v_scale,
@@ -698,60 +761,26 @@ extern "C" int osk_attention_fwd_ragged_bf16(const void* q, int64_t q_batch_stri
                                              int B, int H, int Lq, int n_seg, int seg_len, int last_seg_len, int hd,
                                              float scale, int q_prescaled, int kv_batches, float score_bound, int mode,
                                              void* workspace, int64_t workspace_bytes, void* stream) {
-  if (mode != OSK_ATTN_BF16 && mode != OSK_ATTN_PV8 && mode != OSK_ATTN_QK8) return OSK_EINVAL;
-  if (!(score_bound >= 0.f) || n_seg < 2 || last_seg_len < 1 || last_seg_len > seg_len) return OSK_EINVAL;
-  if (mode != OSK_ATTN_BF16 && (!v_scale || ((uintptr_t)v_scale & 3))) return OSK_EINVAL;
-  if (mode == OSK_ATTN_QK8 && (!k_scale || ((uintptr_t)k_scale & 3) || (k_seg_stride & 15) || (k_batch_stride & 15) || k_seg_stride < 0 ||
-                               k_batch_stride < 0))
-    return OSK_EINVAL;
-  // the merge reads and writes `out` in 16-byte pieces; the partials are not optional, so neither is the workspace
-  if (((uintptr_t)out & 15) || (o_batch_stride & 7) || (o_row_stride & 7) || !workspace) return OSK_EINVAL;
-  // (with the other OSK_EINVAL checks, in front of attn_params' head-dim OSK_EUNSUPPORTED: a malformed call is reported as malformed)
-  if (B > 0 && H > 0 && Lq > 0 && hd > 0 && workspace_bytes < ragged_partial_bytes(B, H, Lq, hd) + (lse ? 0 : ragged_lse_bytes(B, H, Lq)))
-    return OSK_EINVAL;
+  if (n_seg < 2 || last_seg_len < 1 || last_seg_len > seg_len) return OSK_EINVAL;
+  if (!merge_args_ok(out, o_batch_stride, o_row_stride, lse, B, H, Lq, hd, workspace, workspace_bytes)) return OSK_EINVAL;
   AttnParams a;
-  int rc = mode == OSK_ATTN_BF16
-               ? attn_params(a, q, q_batch_stride, q_row_stride, k, k_seg_stride, k_batch_stride, k_row_stride, vt, vt_seg_stride, 7, out,
-                             o_batch_stride, o_row_stride, lse, B, H, Lq, n_seg - 1, seg_len, hd, {64, 72, 128}, scale, q_prescaled,
-                             kv_batches, workspace, workspace_bytes)
-               : attn_params(a, q, q_batch_stride, q_row_stride, k, k_seg_stride, k_batch_stride, k_row_stride, vt, vt_seg_stride, 15, out,
-                             o_batch_stride, o_row_stride, lse, B, H, Lq, n_seg - 1, seg_len, hd,
-                             mode == OSK_ATTN_QK8 ? std::initializer_list<int>{128} : std::initializer_list<int>{72, 128}, scale,
+  const int rc = mode_params(a, mode, k_scale, v_scale, 3, score_bound, q, q_batch_stride, q_row_stride, k, k_seg_stride, k_batch_stride,
+                             k_row_stride, vt, vt_seg_stride, out, o_batch_stride, o_row_stride, lse, B, H, Lq, n_seg - 1, seg_len, hd, scale,
                              q_prescaled, kv_batches, workspace, workspace_bytes);
   if (rc != OSK_OK) return rc;
-  if (mode == OSK_ATTN_QK8 && k_row_stride != 128) return OSK_EUNSUPPORTED;
-  const int64_t part_bytes = ragged_partial_bytes(B, H, Lq, hd), lse_bytes = lse ? 0 : ragged_lse_bytes(B, H, Lq);
-  // workspace: [f32 partials of launch B | lse of launch A when the caller keeps none | the rest: launch A's own tail split]
-  char* wsb = (char*)workspace;
-  if (!lse) a.lse = (float*)(wsb + part_bytes);
-  void* ws_a = wsb + part_bytes + lse_bytes;
-  const int64_t ws_a_bytes = workspace_bytes - part_bytes - lse_bytes;
-  if (mode == OSK_ATTN_BF16) {
-    a.bound = bound_to_bf16_up(score_bound);
-  } else {
-    a.vt = nullptr; a.vt8 = (const unsigned char*)vt; a.v_scale = v_scale;
-    if (mode == OSK_ATTN_QK8) { a.k = nullptr; a.k8 = (const unsigned char*)k; a.k_scale = k_scale; }
-  }
   // launch B: the last segment alone, laid out as a tensor of last_seg_len keys of its own (V^T rows of round_up(last_seg_len, 64)
-  // positions; e4m3 K [Bkv, H, that many rows, 128]) n_seg - 1 segment strides in; same queries, scales, bound
+  // positions; e4m3 K [Bkv, H, that many rows, 128], hence a batch stride of its own) n_seg - 1 segment strides in; same queries,
+  // scales, bound
   AttnParams b = a;
+  if (!lse) b.lse = borrowed_lse(workspace, B, H, Lq, hd);   // (as launch A; a partial launch writes none)
   set_segments(b, 1, last_seg_len);
   const int64_t skip = n_seg - 1;
   if (b.k) b.k += skip * a.kss;
   if (b.k8) { b.k8 += skip * a.kss; b.kbs = (int64_t)H * b.seg_lp * 128; }
   if (b.vt) b.vt += skip * a.vtss;
   if (b.vt8) b.vt8 += skip * a.vtss;
-  b.rows = 256;
-  b.tail_first = 0; b.tail_split = 1;          // every unit: f32 partial O + log2-domain lse of its whole key range
-  b.ws_o = (float*)workspace;
-  b.ws_lse = b.ws_o + (int64_t)osk_attn::attn_units(b) * 256 * hd;
-  hipStream_t st = (hipStream_t)stream;
-  rc = dispatch(a, hd, mode, ws_a_bytes > 0 ? ws_a : nullptr, ws_a_bytes, st);
-  if (rc != 0) return rc;
-  rc = run_mode(b, hd, mode, st);
-  if (rc != 0) return rc;
-  b.out = a.out; b.lse = a.lse;
-  return osk_attn::launch_merge_into(b, hd, 0.6931471805599453f, st);
+  // launch A through dispatch(): the launch shape of a plain call over the full segments (wide layout, tail split from the rest of the workspace)
+  return run_pair(a, b, hd, mode, /* dispatch_a */ true, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // =============================================================================================
@@ -760,11 +789,63 @@ extern "C" int osk_attention_fwd_ragged_bf16(const void* q, int64_t q_batch_stri
 // Keys [0, n_prefix) (text) are seen by every query; keys [n_prefix, Lk) are the body, of which 256-row query block qb sees the
 // 64-key tiles [first, first + count) of its table row and nothing else.  Launch A runs over the body as a key axis of its own
 // -- K and V^T advanced by n_prefix keys, V^T's row stride still that of the whole tensor -- with the table (key_part() hands
-// every work unit its run of tiles) and writes finished rows; launch B runs over the prefix in the partial mode of the ragged
-// entry above (tail_first = 0, tail_split = 1) and attn_merge_into_kernel folds it into launch A's rows in place.
+// every work unit its run of tiles) and writes finished rows; launch B runs over the prefix as the partial launch of run_pair()
+// (tail_first = 0, tail_split = 1) and attn_merge_into_kernel folds it into launch A's rows in place.
 extern "C" int64_t osk_attention_window_workspace_bytes(int B, int H, int Lq, int hd) {
   if (B <= 0 || H <= 0 || Lq <= 0 || hd <= 0) return 0;
   return ragged_partial_bytes(B, H, Lq, hd) + ragged_lse_bytes(B, H, Lq);
+}
+
+// One function behind osk_attention_fwd_window_bf16 (mode OSK_ATTN_BF16, score_bound) and osk_attention_fwd_window_fp8_bf16 (the fp8
+// operands of osk_attention_fwd_pv8_bf16 -- OSK_ATTN_PV8: bf16 K in place, e4m3 V^T -- or of osk_attention_fwd_qk8_bf16 -- OSK_ATTN_QK8:
+// e4m3 K too, head_dim 128), driven through the kernels of the mode the way the ragged entry drives them.  What the loops meet is nothing
+// the single-segment tail split does not already hand them: key_part()'s `win` branch gives the loaders a run of tiles (offsets of its
+// first tile, tps = nt = its length, ragged only where it ends in the last tile); the fp8 kernels bake key validity into V^T's row hd (no
+// first-tile LDS mask to write), their slot words see only `ragged`, and the q8 K loader steps whole 64 x 128-byte tiles from k_off = first
+// tile * 64 * krs with krs = 128 (tests/attention_cases.py: p72_1tile_ragged, p72_merge, q128_1tile_ragged_plain, q128_tile_runs_merge run
+// 1- and 2-tile parts, full and ragged).
+// Launch A does not go through dispatch(): it keeps rows = 256, tail_first = 0x7fffffff, tail_split = 1 (the table is per 256 rows and a
+// windowed unit has a key run of its own; split_tail() would return at p.win anyway, and only launch_shape() -- bf16 mode -- ever picks
+// the wide layout).
+static int window_fwd(int mode, const void* q, int64_t q_batch_stride, int64_t q_row_stride, const void* k, int64_t k_batch_stride,
+                      int64_t k_row_stride, const float* k_scale, const void* vt, const float* v_scale, void* out, int64_t o_batch_stride,
+                      int64_t o_row_stride, float* lse, int B, int H, int Lq, int Lk, int n_prefix, int hd, float scale, int q_prescaled,
+                      int kv_batches, float score_bound, const int32_t* windows, int n_windows, void* workspace, int64_t workspace_bytes,
+                      void* stream) {
+  if (!windows || ((uintptr_t)windows & 3)) return OSK_EINVAL;
+  if (Lq <= 0 || Lk <= 0 || n_windows != (Lq + 255) / 256 || n_prefix < 0 || (n_prefix & 63) || n_prefix >= Lk) return OSK_EINVAL;
+  // (n_prefix == 0: a single launch, no partials, no workspace)
+  if (n_prefix > 0 && !merge_args_ok(out, o_batch_stride, o_row_stride, lse, B, H, Lq, hd, workspace, workspace_bytes)) return OSK_EINVAL;
+  AttnParams a;
+  const int rc = mode_params(a, mode, k_scale, v_scale, 3, score_bound, q, q_batch_stride, q_row_stride, k, 0, k_batch_stride, k_row_stride, vt,
+                             0, out, o_batch_stride, o_row_stride, lse, B, H, Lq, 1, Lk, hd, scale, q_prescaled, kv_batches, workspace,
+                             workspace_bytes);
+  if (rc != OSK_OK) return rc;
+  a.rows = 256;                                  // the table is per 256-row block; tail_first stays off: finished rows
+  // Both launches walk a key range of ONE tensor laid out for all Lk keys: V^T [Bkv, H, hd | RP, Lp] and, in qk8 mode, K [Bkv, H, Lp, 128]
+  // with Lp = round_up(Lk, 64).  The kernels take a head's stride from seg_lp (rows * seg_lp positions of V^T, seg_lp * 128 bytes of e4m3
+  // K) and a V^T row's from seg_lp as well, so seg_lp stays the whole tensor's after set_segments() below.  kbs needs no such care here: it
+  // is the caller's batch stride of that one tensor (H * Lp * 128 when packed), which set_segments() does not touch -- the ragged entry
+  // re-derives it only because its last segment is a tensor of its own with another Lp.
+  const int64_t seg_lp = a.seg_lp;
+  AttnParams b = a;
+  // launch A: the body, windowed, entered n_prefix keys in.  bf16 K: n_prefix rows of krs elements.  e4m3 K: n_prefix rows of 128
+  // bytes inside every head's [Lp, 128] block.  V^T: n_prefix positions along the key axis of EVERY row -- in the e4m3 layout the hd dims
+  // and the validity / denominator row hd alike, since all rows of a head share the one base pointer and the row stride seg_lp.  n_prefix
+  // is a multiple of 64, so the body's tiles are tiles of the whole tensor: the key order inside a tile, the repeated last K row and the
+  // zero validity bytes behind key Lk - 1 sit where a launch over Lk - n_prefix keys expects its ragged last tile.
+  if (a.k) a.k += (int64_t)n_prefix * a.krs;
+  if (a.k8) a.k8 += (int64_t)n_prefix * 128;
+  if (a.vt) a.vt += n_prefix;
+  if (a.vt8) a.vt8 += n_prefix;
+  set_segments(a, 1, Lk - n_prefix);
+  a.seg_lp = (int)seg_lp;
+  a.win = windows;
+  if (n_prefix == 0) return run_mode(a, hd, mode, (hipStream_t)stream);
+  // launch B: the prefix alone from the tensors' origin -- whole tiles (n_prefix % 64 == 0: never ragged), the same scales and bound
+  set_segments(b, 1, n_prefix);
+  b.seg_lp = (int)seg_lp;
+  return run_pair(a, b, hd, mode, /* dispatch_a */ false, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int osk_attention_fwd_window_bf16(const void* q, int64_t q_batch_stride, int64_t q_row_stride,
@@ -773,56 +854,11 @@ extern "C" int osk_attention_fwd_window_bf16(const void* q, int64_t q_batch_stri
                                              int B, int H, int Lq, int Lk, int n_prefix, int hd, float scale, int q_prescaled,
                                              int kv_batches, float score_bound, const int32_t* windows, int n_windows,
                                              void* workspace, int64_t workspace_bytes, void* stream) {
-  if (!(score_bound >= 0.f) || !windows || ((uintptr_t)windows & 3)) return OSK_EINVAL;
-  if (Lq <= 0 || Lk <= 0 || n_windows != (Lq + 255) / 256 || n_prefix < 0 || (n_prefix & 63) || n_prefix >= Lk) return OSK_EINVAL;
-  if (n_prefix > 0) {
-    // the merge reads and writes `out` in 16-byte pieces; the prefix's partials are not optional, so neither is the workspace
-    if (((uintptr_t)out & 15) || (o_batch_stride & 7) || (o_row_stride & 7) || !workspace) return OSK_EINVAL;
-    if (B > 0 && H > 0 && hd > 0 && workspace_bytes < ragged_partial_bytes(B, H, Lq, hd) + (lse ? 0 : ragged_lse_bytes(B, H, Lq)))
-      return OSK_EINVAL;
-  }
-  AttnParams a;
-  int rc = attn_params(a, q, q_batch_stride, q_row_stride, k, 0, k_batch_stride, k_row_stride, vt, 0, 7, out, o_batch_stride,
-                       o_row_stride, lse, B, H, Lq, 1, Lk, hd, {64, 72, 128}, scale, q_prescaled, kv_batches, workspace, workspace_bytes);
-  if (rc != OSK_OK) return rc;
-  a.bound = bound_to_bf16_up(score_bound);
-  a.rows = 256;                                  // the table is per 256-row block: no wide layout; no tail split (tail_first stays off)
-  const int64_t seg_lp = a.seg_lp;               // V^T rows keep the whole tensor's length, whichever keys a launch walks
-  AttnParams b = a;
-  // launch A: the body, windowed
-  a.k += (int64_t)n_prefix * a.krs;
-  a.vt += n_prefix;
-  set_segments(a, 1, Lk - n_prefix);
-  a.seg_lp = (int)seg_lp;
-  a.win = windows;
-  hipStream_t st = (hipStream_t)stream;
-  if (n_prefix == 0) return run(a, hd, st);
-  if (!lse) a.lse = (float*)((char*)workspace + ragged_partial_bytes(B, H, Lq, hd));
-  // launch B: the prefix, every unit an f32 partial O + log2-domain lse of all of it
-  set_segments(b, 1, n_prefix);
-  b.seg_lp = (int)seg_lp;
-  b.tail_first = 0; b.tail_split = 1;
-  b.ws_o = (float*)workspace;
-  b.ws_lse = b.ws_o + (int64_t)osk_attn::attn_units(b) * 256 * hd;
-  rc = run(a, hd, st);
-  if (rc != 0) return rc;
-  rc = run(b, hd, st);
-  if (rc != 0) return rc;
-  b.out = a.out; b.lse = a.lse;
-  return osk_attn::launch_merge_into(b, hd, 0.6931471805599453f, st);
+  return window_fwd(OSK_ATTN_BF16, q, q_batch_stride, q_row_stride, k, k_batch_stride, k_row_stride, nullptr, vt, nullptr, out, o_batch_stride,
+                    o_row_stride, lse, B, H, Lq, Lk, n_prefix, hd, scale, q_prescaled, kv_batches, score_bound, windows, n_windows, workspace,
+                    workspace_bytes, stream);
 }
 
-// The same entry on the fp8 operands of osk_attention_fwd_pv8_bf16 (mode OSK_ATTN_PV8: bf16 K in place, e4m3 V^T) or
-// osk_attention_fwd_qk8_bf16 (OSK_ATTN_QK8: e4m3 K too, head_dim 128).  The scheme is the one above -- launch A the windowed body into
-// finished rows, launch B the prefix into f32 partials, one in-place merge -- driven through the pv8 / qk8 kernels the way the ragged
-// entry drives them.  What the loops meet is nothing the single-segment tail split does not already hand them: key_part()'s `win` branch
-// gives the loaders a run of tiles (offsets of its first tile, tps = nt = its length, ragged only where it ends in the last tile); the
-// fp8 kernels bake key validity into V^T's row hd (no first-tile LDS mask to write), their slot words see only `ragged`, and the q8 K
-// loader steps whole 64 x 128-byte tiles from k_off = first tile * 64 * krs with krs = 128 (tests/attention_cases.py: p72_1tile_ragged,
-// p72_merge, q128_1tile_ragged_plain, q128_tile_runs_merge run 1- and 2-tile parts, full and ragged).
-// Neither launch goes through dispatch(): launch A keeps rows = 256, tail_first = 0x7fffffff, tail_split = 1 (the table is per 256
-// rows and a windowed unit has a key run of its own; split_tail() would return at p.win anyway, and only launch_shape() -- bf16 mode
-// -- ever picks the wide layout), launch B is the every-unit partial launch.
 extern "C" int osk_attention_fwd_window_fp8_bf16(const void* q, int64_t q_batch_stride, int64_t q_row_stride,
                                                  const void* k, int64_t k_batch_stride, int64_t k_row_stride, const float* k_scale,
                                                  const void* vt, const float* v_scale, void* out, int64_t o_batch_stride,
@@ -830,57 +866,8 @@ extern "C" int osk_attention_fwd_window_fp8_bf16(const void* q, int64_t q_batch_
                                                  float scale, int q_prescaled, int kv_batches, int mode, const int32_t* windows,
                                                  int n_windows, void* workspace, int64_t workspace_bytes, void* stream) {
   if (mode != OSK_ATTN_PV8 && mode != OSK_ATTN_QK8) return OSK_EINVAL;   // (OSK_ATTN_BF16: osk_attention_fwd_window_bf16)
-  if (!windows || ((uintptr_t)windows & 3) || !v_scale || ((uintptr_t)v_scale & 3)) return OSK_EINVAL;
-  if (mode == OSK_ATTN_QK8 && (!k_scale || ((uintptr_t)k_scale & 3) || (k_batch_stride & 15) || k_batch_stride < 0)) return OSK_EINVAL;
-  if (Lq <= 0 || Lk <= 0 || n_windows != (Lq + 255) / 256 || n_prefix < 0 || (n_prefix & 63) || n_prefix >= Lk) return OSK_EINVAL;
-  if (n_prefix > 0) {
-    // the merge reads and writes `out` in 16-byte pieces; the prefix's partials are not optional, so neither is the workspace
-    if (((uintptr_t)out & 15) || (o_batch_stride & 7) || (o_row_stride & 7) || !workspace) return OSK_EINVAL;
-    if (B > 0 && H > 0 && hd > 0 && workspace_bytes < ragged_partial_bytes(B, H, Lq, hd) + (lse ? 0 : ragged_lse_bytes(B, H, Lq)))
-      return OSK_EINVAL;
-  }
-  AttnParams a;
-  int rc = attn_params(a, q, q_batch_stride, q_row_stride, k, 0, k_batch_stride, k_row_stride, vt, 0, 15, out, o_batch_stride,
-                       o_row_stride, lse, B, H, Lq, 1, Lk, hd,
-                       mode == OSK_ATTN_QK8 ? std::initializer_list<int>{128} : std::initializer_list<int>{72, 128}, scale, q_prescaled,
-                       kv_batches, workspace, workspace_bytes);
-  if (rc != OSK_OK) return rc;
-  if (mode == OSK_ATTN_QK8 && k_row_stride != 128) return OSK_EUNSUPPORTED;   // the packed layout: rows of 128 bytes, heads Lp rows apart
-  a.vt = nullptr; a.vt8 = (const unsigned char*)vt; a.v_scale = v_scale;
-  if (mode == OSK_ATTN_QK8) { a.k = nullptr; a.k8 = (const unsigned char*)k; a.k_scale = k_scale; }
-  a.rows = 256;                                  // the table is per 256-row block; tail_first stays off: finished rows
-  // Both launches walk a key range of ONE tensor laid out for all Lk keys: V^T [Bkv, H, RP, Lp] and, in qk8 mode, K [Bkv, H, Lp, 128]
-  // with Lp = round_up(Lk, 64).  The kernels take a head's stride from seg_lp (RP * seg_lp bytes of V^T, seg_lp * 128 of K) and a V^T
-  // row's from seg_lp as well, so seg_lp stays the whole tensor's after set_segments() below, as the bf16 entry keeps it for its V^T.
-  // kbs needs no such care here: it is the caller's batch stride of that one tensor (H * Lp * 128 when packed), which set_segments()
-  // does not touch -- the ragged entry re-derives it only because its last segment is a tensor of its own with another Lp.
-  const int64_t seg_lp = a.seg_lp;
-  AttnParams b = a;
-  // launch A: the body, windowed, entered n_prefix keys in.  bf16 K: n_prefix rows of krs elements.  e4m3 K: n_prefix rows of 128
-  // bytes inside every head's [Lp, 128] block.  e4m3 V^T: n_prefix bytes along the key axis of EVERY row -- the hd dims and the
-  // validity / denominator row hd alike, since all rows of a head share the one base pointer and the row stride seg_lp.  n_prefix is a
-  // multiple of 64, so the body's tiles are tiles of the whole tensor: the key order inside a tile, the repeated last K row and the
-  // zero validity bytes behind key Lk - 1 sit where a launch over Lk - n_prefix keys expects its ragged last tile.
-  if (a.k) a.k += (int64_t)n_prefix * a.krs;
-  if (a.k8) a.k8 += (int64_t)n_prefix * 128;
-  a.vt8 += n_prefix;
-  set_segments(a, 1, Lk - n_prefix);
-  a.seg_lp = (int)seg_lp;
-  a.win = windows;
-  hipStream_t st = (hipStream_t)stream;
-  if (n_prefix == 0) return run_mode(a, hd, mode, st);
-  if (!lse) a.lse = (float*)((char*)workspace + ragged_partial_bytes(B, H, Lq, hd));
-  // launch B: the prefix alone from the tensors' origin -- whole tiles (n_prefix % 64 == 0: never ragged), the same scales, every
-  // unit an f32 partial O + log2-domain lse of all of it (tail_first = 0, tail_split = 1)
-  set_segments(b, 1, n_prefix);
-  b.seg_lp = (int)seg_lp;
-  b.tail_first = 0; b.tail_split = 1;
-  b.ws_o = (float*)workspace;
-  b.ws_lse = b.ws_o + (int64_t)osk_attn::attn_units(b) * 256 * hd;
-  rc = run_mode(a, hd, mode, st);
-  if (rc != 0) return rc;
-  rc = run_mode(b, hd, mode, st);
-  if (rc != 0) return rc;
-  b.out = a.out; b.lse = a.lse;
-  return osk_attn::launch_merge_into(b, hd, 0.6931471805599453f, st);
+  return window_fwd(mode, q, q_batch_stride, q_row_stride, k, k_batch_stride, k_row_stride, k_scale, vt, v_scale, out, o_batch_stride,
+                    o_row_stride, lse, B, H, Lq, Lk, n_prefix, hd, scale, q_prescaled, kv_batches, 0.f, windows, n_windows, workspace,
+                    workspace_bytes, stream);
 }
+

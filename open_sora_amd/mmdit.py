@@ -745,6 +745,26 @@ def _window_mode(pv8: bool, qk8: bool, hd: int) -> str:
     return "qk8" if qk8 and hd == 128 else "pv8"
 
 
+def _fp8_operands(ws: _Workspace, k: Tensor, v: Tensor, H: int, hd: int, qk8: bool):
+    """the fp8 operands of one attention call, prepared on the device (no host synchronisation): V^T as e4m3 into ws.vt8 with one scale
+    per (batch, head) and, for qk8 at head_dim 128, K as e4m3 into ws.k8 with its scales.  Both buffers are allocated on first use and
+    kept.  Returns (k operand, k_scale or None, vt8, v_scale): k itself and None where K stays bf16."""
+    B = v.shape[0]
+    vt8 = getattr(ws, "vt8", None)
+    if vt8 is None:
+        vt8 = ws.vt8 = torch.empty(B, H, _OPS.vt8_rows(hd), ws.vt.shape[-1], dtype=torch.uint8, device=v.device)
+    sv = v_scale_fp8(v, H, hd)
+    _OPS.v_transpose_fp8(v, sv, vt8, H, hd)
+    if not (qk8 and hd == 128):
+        return k, None, vt8, sv
+    k8 = getattr(ws, "k8", None)
+    if k8 is None or tuple(k8.shape) != _OPS.k8_shape(B, H, k.shape[1], hd):
+        k8 = ws.k8 = torch.empty(_OPS.k8_shape(B, H, k.shape[1], hd), dtype=torch.uint8, device=k.device)
+    sk = v_scale_fp8(k, H, hd)
+    _OPS.k_pack_fp8(k, sk, k8, H, hd)
+    return k8, sk, vt8, sv
+
+
 def _joint_attention(ws: _Workspace, q: Tensor, k: Tensor, v: Tensor, H: int, hd: int, pv8: bool = False,
                      score_bound: float = 0.0, vt_ready: bool = False, qk8: bool = False):
     """attention() of math.py:22-36 on the joint [txt;img] sequence; the output overwrites the (dead) v slot.
@@ -761,19 +781,7 @@ def _joint_attention(ws: _Workspace, q: Tensor, k: Tensor, v: Tensor, H: int, hd
         if pv8 and hd in (72, 128):
             # fp8 mode: the operand preparation of the unwindowed path below (scales on the device, no host synchronisation; the
             # packs still touch every key), then ONE call of the fp8 window entry.  qk8 at another head dim takes pv8, as there.
-            B = v.shape[0]
-            vt8 = getattr(ws, "vt8", None)
-            if vt8 is None:
-                vt8 = ws.vt8 = torch.empty(B, H, _OPS.vt8_rows(hd), ws.vt.shape[-1], dtype=torch.uint8, device=v.device)
-            sv = v_scale_fp8(v, H, hd)
-            _OPS.v_transpose_fp8(v, sv, vt8, H, hd)
-            kk, sk = k, None
-            if qk8 and hd == 128:
-                kk = getattr(ws, "k8", None)
-                if kk is None or tuple(kk.shape) != _OPS.k8_shape(B, H, k.shape[1], hd):
-                    kk = ws.k8 = torch.empty(_OPS.k8_shape(B, H, k.shape[1], hd), dtype=torch.uint8, device=k.device)
-                sk = v_scale_fp8(k, H, hd)
-                _OPS.k_pack_fp8(k, sk, kk, H, hd)
+            kk, sk, vt8, sv = _fp8_operands(ws, k, v, H, hd, qk8)
             _OPS.attention_fwd_window_fp8(q, kk, sk, vt8, sv, v, H, hd, hd ** -0.5, n_prefix=ws.L_txt, windows=ws.attn_window,
                                           mode=_window_mode(pv8, qk8, hd), q_prescaled=True, workspace=ws.win_ws, Lk=k.shape[1])
             return
@@ -784,19 +792,9 @@ def _joint_attention(ws: _Workspace, q: Tensor, k: Tensor, v: Tensor, H: int, hd
         return
     wsp = _OPS.attention_workspace(q.device)
     if pv8 and hd in (72, 128):
-        B = v.shape[0]
-        vt8 = getattr(ws, "vt8", None)
-        if vt8 is None:
-            vt8 = ws.vt8 = torch.empty(B, H, _OPS.vt8_rows(hd), ws.vt.shape[-1], dtype=torch.uint8, device=v.device)
-        sv = v_scale_fp8(v, H, hd)
-        _OPS.v_transpose_fp8(v, sv, vt8, H, hd)
-        if qk8 and hd == 128:
-            k8 = getattr(ws, "k8", None)
-            if k8 is None or tuple(k8.shape) != _OPS.k8_shape(B, H, k.shape[1], hd):
-                k8 = ws.k8 = torch.empty(_OPS.k8_shape(B, H, k.shape[1], hd), dtype=torch.uint8, device=k.device)
-            sk = v_scale_fp8(k, H, hd)
-            _OPS.k_pack_fp8(k, sk, k8, H, hd)
-            _OPS.attention_fwd_qk8(q, k8, sk, vt8, sv, v, H, hd, hd ** -0.5, seg_len=k.shape[1], q_prescaled=True, workspace=wsp)
+        kk, sk, vt8, sv = _fp8_operands(ws, k, v, H, hd, qk8)
+        if sk is not None:
+            _OPS.attention_fwd_qk8(q, kk, sk, vt8, sv, v, H, hd, hd ** -0.5, seg_len=k.shape[1], q_prescaled=True, workspace=wsp)
             return
         _OPS.attention_fwd_pv8(q, k, vt8, sv, v, H, hd, hd ** -0.5, q_prescaled=True, workspace=wsp)
         return
