@@ -218,6 +218,26 @@ int osk_qknorm_rope_bf16(void* q, void* k, int64_t batch_stride, int64_t row_str
 int osk_v_transpose_bf16(const void* v, int64_t batch_stride, int64_t row_stride,
                          void* vt, int B, int L, int H, int hd, void* stream);
 
+/* ---- gathered K / V segments -> the operands of ONE key segment (an additive entry, the version stays 2).
+ * It stands beside the KV exchange around attention of opensora/models/mmdit/distributed.py (ring hops + LSE merge :223-313,
+ * Ulysses all-to-all :473-495) and replaces nothing there: the reference never re-lays its exchanged K / V out.  Here the exchange
+ * buffers of open_sora_amd/seqpar.py are segment-major, and osk_attention_fwd_window_bf16 takes one key segment; this call turns
+ * the one into the other in a single HBM-bound launch (K and V each read once and written once).
+ * k_seg, v_seg: key j < L of batch b, head h lives in segment s = j / seg_len, row r = j % seg_len, at
+ *   base + s*seg_stride + b*batch_stride + r*row_stride + h*hd (elements; the strides are shared by K and V).
+ *   (n_seg - 1)*seg_len < L <= n_seg*seg_len: the last segment may be short; its rows >= L - (n_seg - 1)*seg_len are never read.
+ * k_out: k_out[b, j, :] = that K row for j < L -- a [B, L, H*hd] view, batches ko_batch_stride and rows ko_row_stride elements apart.
+ * vt_out: [B, H, hd, round_up(L, 64)] contiguous, bit-identical to what osk_v_transpose_bf16 writes for the contiguous [B, L, H*hd]
+ *   V of the same keys: the key order inside each 64-key tile documented above, zeros for keys >= L.
+ * OSK_EINVAL: L / n_seg / seg_len outside the rule above, B or H <= 0, a NULL pointer or one not 16-byte aligned, a stride that is
+ * no multiple of 8.  hd in {64, 72, 128} (else OSK_EUNSUPPORTED).  A refused call launches nothing.
+ * No allocation, no memset, no atomics on global memory, no host synchronisation: capturable in a hipGraph. */
+int osk_kv_join_bf16(const void* k_seg, const void* v_seg,
+                     int64_t seg_stride, int64_t batch_stride, int64_t row_stride,   /* elements, shared by K and V */
+                     void* k_out, int64_t ko_batch_stride, int64_t ko_row_stride,
+                     void* vt_out,
+                     int B, int H, int hd, int n_seg, int seg_len, int L, void* stream);
+
 /* ---- flash attention forward, non-causal: out = softmax(q k^T * scale) v, bf16 I/O, f32 softmax.
  * replaces flash_attn_func (math.py:16-19,33) and _flash_attn_forward with LSE
  * (distributed.py:148-161).

@@ -45,6 +45,7 @@ SIGNATURES = {
     "osk_qknorm_rope_bf16": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i64,
                              _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp],
     "osk_v_transpose_bf16": [_vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _vp],
+    "osk_kv_join_bf16": [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "osk_attention_fwd_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp,
                                _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _vp],
     "osk_attention_fwd_ws_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp,
@@ -497,6 +498,20 @@ def v_transpose(v: torch.Tensor, vt: torch.Tensor, H: int, hd: int):
            "osk_v_transpose_bf16")
 
 
+def kv_join(k_seg: torch.Tensor, v_seg: torch.Tensor, k_out: torch.Tensor, vt_out: torch.Tensor, H: int, hd: int, L: int):
+    """k_seg, v_seg bf16 [n_seg, B, seg_len, H*hd] views with the same strides (the gathered exchange buffers: key j in segment
+    j // seg_len, row j % seg_len) -> k_out bf16 [B, L, H*hd] view and vt_out bf16 [B, H, hd, round_up(L, 64)] contiguous, vt_out
+    bit for bit v_transpose() of the L keys as one contiguous V (osk_kv_join_bf16).  (n_seg - 1) * seg_len < L <= n_seg * seg_len."""
+    n_seg, B, seg_len, D = k_seg.shape
+    assert k_seg.dtype == v_seg.dtype == k_out.dtype == vt_out.dtype == torch.bfloat16 and D == H * hd, (k_seg.dtype, v_seg.dtype, D, H, hd)
+    assert v_seg.shape == k_seg.shape and v_seg.stride() == k_seg.stride() and k_seg.stride(3) == 1, (v_seg.shape, v_seg.stride(), k_seg.stride())
+    assert tuple(k_out.shape) == (B, L, D) and k_out.stride(2) == 1, (k_out.shape, k_out.stride())
+    assert tuple(vt_out.shape) == (B, H, hd, (L + 63) // 64 * 64) and vt_out.is_contiguous(), (vt_out.shape, vt_out.stride())
+    _check(lib.osk_kv_join_bf16(k_seg.data_ptr(), v_seg.data_ptr(), k_seg.stride(0), k_seg.stride(1), k_seg.stride(2), k_out.data_ptr(),
+                                k_out.stride(0), k_out.stride(1), vt_out.data_ptr(), B, H, hd, n_seg, seg_len, L, _stream()),
+           "osk_kv_join_bf16")
+
+
 _ATTN_WS: dict = {}
 
 
@@ -704,7 +719,7 @@ def _window_on_device(windows: torch.Tensor, device) -> torch.Tensor:
     if dev is None:
         if torch.device(device).type == "cuda" and torch.cuda.is_current_stream_capturing():
             raise RuntimeError("attention_fwd_window: this table was never uploaded; call once outside the captured region first")
-        while len(_WINDOW_DEV) >= 16:
+        while len(_WINDOW_DEV) >= 64:    # (head-exchange sequence parallelism keeps one table per source rank and geometry)
             _WINDOW_DEV.pop(next(iter(_WINDOW_DEV)))
         dev = _WINDOW_DEV[key] = c.to(device)
     return dev

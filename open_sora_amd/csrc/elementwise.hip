@@ -2,6 +2,7 @@
 // V transpose, skinny GEMV task list (adaLN modulation / embedders), timestep embedding, RoPE tables,
 // CFG + Euler update.  All loads/stores are 16 B per lane (8 bf16) where the layout allows (guide G13).
 #include "osk_common.h"
+#include "vt_tile.h"
 #include "../../include/osk.h"
 
 // =============================================================================================
@@ -498,33 +499,7 @@ __global__ void __launch_bounds__(256) v_transpose_kernel(const unsigned short* 
   }
   __syncthreads();
   // output: HD rows of 64 keys = 8 chunks of 8 keys, in the key order the attention kernel of this head_dim bakes into its P operand
-  unsigned short* obase = vt + ((int64_t)(b * H + h) * HD) * Lp + key0;
-  for (int i = threadIdx.x; i < HD * 8; i += 256) {
-    const int d = i >> 3, pc = i & 7;  // pc: 8-position chunk within the 64-key row
-    unsigned short e[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      int key;
-      if constexpr (HD == 72 || HD == 64) {
-        // head_dim 72 and 64 (P.V on v_mfma_f32_16x16x32_bf16, attention_asm72.hip): chunk pc of the 64-key row = 32-key half pc / 4,
-        // lane row r = pc % 4 of the MFMA operands, whose 8 keys are {0-3, 8-11}, {16-19, 24-27}, {4-7, 12-15}, {20-23, 28-31}
-        const int r = pc & 3;
-        key = 32 * (pc >> 2) + ((r & 1) << 4) + ((r >> 1) << 2) + ((j >> 2) << 3) + (j & 3);
-      } else {
-        // head_dim 128 (P.V on 32x32x16): per 16 keys, positions 0-3 -> keys 0-3, 4-7 -> keys 8-11, 8-11 -> keys 4-7, 12-15 -> keys 12-15
-        const int p = pc * 8 + j;                  // position within tile
-        const int p16 = p & 15, grp = p & ~15;
-        key = grp + ((p16 < 4 || p16 >= 12) ? p16 : (p16 < 8 ? p16 + 4 : p16 - 4));
-      }
-      e[j] = tile[key][d];
-    }
-    uint4 u;
-    u.x = e[0] | ((unsigned)e[1] << 16);
-    u.y = e[2] | ((unsigned)e[3] << 16);
-    u.z = e[4] | ((unsigned)e[5] << 16);
-    u.w = e[6] | ((unsigned)e[7] << 16);
-    *reinterpret_cast<uint4*>(obase + (int64_t)d * Lp + pc * 8) = u;
-  }
+  vt_tile_store<HD>(tile, vt + ((int64_t)(b * H + h) * HD) * Lp + key0, Lp);
 }
 
 extern "C" int osk_v_transpose_bf16(const void* v, int64_t bs, int64_t rs, void* vt, int B, int L,

@@ -542,6 +542,7 @@ class _Workspace:
         # hipGraph replays into it: it must not move when another batch size asks for more)
         self.attn_window = None
         self.win_ws = None
+        self.sp_window = None   # sharded forward with the window on: (L_txt, L_img, window_frames, frame_tokens) of the FULL sequence
 
     def y_double(self, D):
         return self.y[: self.B * self.L * 3 * D].view(self.B, self.L, 3 * D)
@@ -693,24 +694,31 @@ def _bf16_operands(*xs) -> bool:
     return all(not isinstance(x, (tuple, Fp8Weight)) for x in xs)
 
 
-def attention_window_table(L_txt: int, L_img: int, frame_tokens: int, window_frames: int) -> Tensor:
+def attention_window_table(L_txt: int, L_img: int, frame_tokens: int, window_frames: int, *, row0: int = 0, n_rows: int | None = None) -> Tensor:
     """The key ranges of frame-window attention on the joint [txt; img] sequence, for osk_attention_fwd_window_bf16 with
     n_prefix = L_txt: host int32 [ceil((L_txt + L_img) / 256), 2] of (first tile, tile count), one row per 256 query rows, in
     64-key tiles of the image keys.  Frame f is image rows [f N, (f + 1) N), N = frame_tokens, T = L_img / N frames, W =
     window_frames.  A block that holds any text row gets every tile (text queries see everything).  A block whose image rows lie in
     frames f0..f1 gets the image keys [max(0, f0 - W) N, min(T, f1 + W + 1) N), rounded OUTWARD to whole tiles.
     This is a block-granular SUPERSET of each row's own +-W frames: a row also sees the windows of the other rows of its block and
-    the keys that share a tile with the range's ends -- up to 255 rows' worth of frames and 63 keys per side more than its own."""
+    the keys that share a tile with the range's ends -- up to 255 rows' worth of frames and 63 keys per side more than its own.
+    row0 / n_rows (a sequence-parallel rank's share, seqpar.SeqPar): the table of query rows [row0, row0 + n_rows) of the joint axis
+    alone, cut into 256-row blocks that START AT row0 -- [ceil(n_rows / 256), 2], the same rule per block, the key tiles still those
+    of all L_img image keys.  The defaults describe the whole axis."""
     if L_txt < 0 or L_img <= 0 or frame_tokens <= 0 or window_frames < 0:
         raise ValueError(f"attention_window_table: L_txt >= 0, L_img > 0, frame_tokens > 0, window_frames >= 0 expected; got {(L_txt, L_img, frame_tokens, window_frames)}")
     if L_img % frame_tokens:
         raise ValueError(f"attention_window_table: {L_img} image tokens are not whole frames of {frame_tokens}")
     N, W, T = frame_tokens, window_frames, L_img // frame_tokens
     L = L_txt + L_img
+    n_rows = L - row0 if n_rows is None else n_rows
+    if row0 < 0 or n_rows < 1 or row0 + n_rows > L:
+        raise ValueError(f"attention_window_table: rows [{row0}, {row0} + {n_rows}) do not lie inside the {L} rows of the joint axis")
+    end = row0 + n_rows
     tiles = (L_img + 63) // 64
     rows = []
-    for r0 in range(0, L, 256):
-        r1 = min(r0 + 256, L) - 1                      # the block's last row
+    for r0 in range(row0, end, 256):
+        r1 = min(r0 + 256, end) - 1                    # the block's last row
         if r0 < L_txt:
             rows.append((0, tiles))
             continue
@@ -823,6 +831,13 @@ def _sp_qk8(sp, plan) -> dict:
     return {"qk8": True} if plan.qk8 and getattr(sp, "kv_qk8", False) and hasattr(_OPS, "kv_scale_fp8") else {}
 
 
+def _sp_window(ws) -> dict:
+    """the window argument of sp.gather_kv_start in a sharded forward with frame-window attention on (MMDiTModel._forward_head leaves
+    the full sequence's geometry in ws.sp_window), else no argument: with the window off the call is the one from before"""
+    spec = getattr(ws, "sp_window", None)
+    return {} if spec is None else {"window": spec}
+
+
 def run_double_block(plan: _DoublePlan, ws: _Workspace, mod: Tensor, col_img: int, col_txt: int, rope: _RopeTable,
                      H: int, hd: int, sp=None, x_in=None, x_out=None):
     """DoubleStreamBlockProcessor.__call__ (layers.py:195-253) on the workspace's joint buffers.
@@ -880,7 +895,8 @@ def run_double_block(plan: _DoublePlan, ws: _Workspace, mod: Tensor, col_img: in
         # K, V first: their exchange overlaps the Q projection.  All-gather mode, bf16: V goes straight into this rank's slot of the
         # gathered V^T buffer (osk_gemm_group_bf16's V^T task, round 6) -- no token-major V, no osk_v_transpose_bf16 pass on the rank
         vt_ready = False
-        vt_loc = sp.local_vt(ws.B, ws.L, H, hd, ws.x.device) if (ws.vt_group and not plan.pv8 and Lt % 64 == 0 and hasattr(sp, "local_vt") and
+        win = _sp_window(ws)      # frame-window attention: V travels token-major (the join writes V^T of the whole key axis)
+        vt_loc = sp.local_vt(ws.B, ws.L, H, hd, ws.x.device) if (ws.vt_group and not plan.pv8 and Lt % 64 == 0 and hasattr(sp, "local_vt") and not win and
                                                                   _bf16_operands(*acts, *(s_[0].qkv_w for s_ in streams))) else None
         if vt_loc is not None:
             tasks = []
@@ -896,7 +912,7 @@ def run_double_block(plan: _DoublePlan, ws: _Workspace, mod: Tensor, col_img: in
             for (aw, x_s, xm_s, y_s, sh1, sc1), act in zip(streams, acts):
                 _linear(act, aw.qkv_w[D:], None if aw.qkv_b is None else aw.qkv_b[D:], y_s[:, :, D:])
         _OPS.qknorm_rope(None, k, *scales, Lt, rope.cos, rope.sin, csb, H, hd, rope.mode)
-        pending = sp.gather_kv_start(ws, k, v, H, hd, plan.pv8, vt_ready=vt_ready, **_sp_qk8(sp, plan))
+        pending = sp.gather_kv_start(ws, k, v, H, hd, plan.pv8, vt_ready=vt_ready, **_sp_qk8(sp, plan), **win)
         for (aw, x_s, xm_s, y_s, sh1, sc1), act in zip(streams, acts):
             _linear(act, aw.qkv_w[:D], None if aw.qkv_b is None else aw.qkv_b[:D], y_s[:, :, :D])
         _OPS.qknorm_rope(q, None, *scales, Lt, rope.cos, rope.sin, csb, H, hd, rope.mode, q_mult=q_mult(hd))
@@ -955,7 +971,8 @@ def run_single_block(plan: _SinglePlan, ws: _Workspace, mod: Tensor, col: int, r
     else:
         b1 = plan.b1
         vt_ready = False
-        vt_loc = sp.local_vt(ws.B, ws.L, H, hd, ws.x.device) if (ws.vt_group and not plan.pv8 and hasattr(sp, "local_vt") and
+        win = _sp_window(ws)      # (see run_double_block)
+        vt_loc = sp.local_vt(ws.B, ws.L, H, hd, ws.x.device) if (ws.vt_group and not plan.pv8 and hasattr(sp, "local_vt") and not win and
                                                                   _bf16_operands(act, plan.w1)) else None
         if vt_loc is not None:     # (see run_double_block)
             vt_ready = _OPS.gemm_group([
@@ -966,7 +983,7 @@ def run_single_block(plan: _SinglePlan, ws: _Workspace, mod: Tensor, col: int, r
         if not vt_ready:
             _linear(act, plan.w1[D: 3 * D], None if b1 is None else b1[D: 3 * D], y[:, :, D: 3 * D])
         _OPS.qknorm_rope(None, k, *scales, 0, rope.cos, rope.sin, csb, H, hd, rope.mode)
-        pending = sp.gather_kv_start(ws, k, v, H, hd, plan.pv8, vt_ready=vt_ready, **_sp_qk8(sp, plan))
+        pending = sp.gather_kv_start(ws, k, v, H, hd, plan.pv8, vt_ready=vt_ready, **_sp_qk8(sp, plan), **win)
         mlp_up = lambda: _linear(act, plan.w1[3 * D:], None if b1 is None else b1[3 * D:], y[:, :, 3 * D:], gelu_from=0)
         head_mode = sp.head_parallel(H)
         if not head_mode:    # K / V^T all-gather: the MLP-up and Q projections both overlap it
@@ -1131,6 +1148,8 @@ class MMDiTModel(_OskState, nn.Module):
         section 4, profiles/attn_qk8.md, profiles/attn_qk8_sp.md (a rank's launch at the sharded shape)."""
         if on and getattr(self, "_attn_window", None) is not None and not _window_fp8_ok():
             raise ValueError("enable_fp8: frame-window attention (set_attention_window) has no fp8 kernels; turn it off first")
+        if on and getattr(self, "_attn_window", None) is not None and getattr(self, "_sp", None) is not None:
+            raise ValueError("enable_fp8: frame-window attention under sequence parallelism has no fp8 path; set_attention_window(None) first")
         for b in list(self.double_blocks) + list(self.single_blocks):
             object.__setattr__(b, "_osk_fp8", bool(on))
             object.__setattr__(b, "_osk_qk8", bool(on and qk8))
@@ -1145,8 +1164,11 @@ class MMDiTModel(_OskState, nn.Module):
         on the pv8 / qk8 operands the unwindowed attention of that mode would take.  frame_tokens: image tokens per latent frame, (h / patch) * (w / patch).
         None turns it off; without the argument the environment's OSK_ATTN_WINDOW_FRAMES decides (unset: off).  Exact with respect
         to the mask it states; the reference attends to every key, so outputs DIFFER from it by what the dropped keys carried, and
-        the quality of that on real checkpoints is not measured.  Not under sequence parallelism,
-        L_txt % 64 == 0 (checked when a forward sees the text).  The setting is not part of state_dict."""
+        the quality of that on real checkpoints is not measured.  L_txt % 64 == 0 (checked when a forward
+        sees the text).  Under sequence parallelism (seqpar.enable, either order) the bf16 attention runs it in both exchange modes:
+        K and V travel token-major, osk_kv_join_bf16 lays the gathered segments out as one key segment and every rank runs the
+        window entry on the table of its own rows (seqpar.SeqPar); refused there: enable_fp8, kv_chunks > 1, the step cache.
+        The setting is not part of state_dict."""
         if isinstance(window_frames, str) and window_frames == "env":
             window_frames = _window_env_default()
         if window_frames is None:
@@ -1156,17 +1178,30 @@ class MMDiTModel(_OskState, nn.Module):
             raise ValueError(f"set_attention_window: window_frames >= 0 and frame_tokens > 0 expected; got {window_frames}, {frame_tokens}")
         if any(getattr(b, "_osk_fp8", False) for b in list(self.double_blocks) + list(self.single_blocks)) and not _window_fp8_ok():
             raise ValueError("set_attention_window: frame-window attention has no fp8 kernels; call enable_fp8(False) first")
-        if getattr(self, "_sp", None) is not None:
-            raise ValueError("set_attention_window: frame-window attention does not run under sequence parallelism yet")
+        self._sp_window_check(getattr(self, "_sp", None), "set_attention_window")
         self._attn_window = (int(window_frames), int(frame_tokens))
         return self
+
+    def _sp_window_check(self, sp, who: str) -> None:
+        """what frame-window attention under sequence parallelism still refuses (sp: the model's seqpar object or None)"""
+        if sp is None:
+            return
+        if not getattr(sp, "kv_window", False):    # (guarded like kv_qk8: a caller's own sp object from before the window path)
+            raise ValueError(f"{who}: frame-window attention does not run under sequence parallelism with this sp object "
+                             f"(seqpar.SeqPar.kv_window)")
+        if any(getattr(b, "_osk_fp8", False) for b in list(self.double_blocks) + list(self.single_blocks)):
+            raise ValueError(f"{who}: frame-window attention under sequence parallelism has no fp8 path (the packed e4m3 K gathers per "
+                             f"segment and needs a join of its own); call enable_fp8(False) or set_attention_window(None)")
+        if getattr(sp, "kv_chunks", 1) > 1:
+            raise ValueError(f"{who}: frame-window attention under sequence parallelism takes one gather; kv_chunks = {sp.kv_chunks} "
+                             f"is refused (seqpar.enable(kv_chunks=1))")
 
     def _window_table(self, L_txt: int, L_img: int, sp):
         """the host table of this forward's geometry (rebuilt when L_txt, L_img or the setting changed), or None when off"""
         if getattr(self, "_attn_window", None) is None:
             return None
-        if sp is not None or getattr(self, "_sp", None) is not None:
-            raise ValueError("frame-window attention does not run under sequence parallelism yet: set_attention_window(None)")
+        # (a forward whose split was declined -- sp None with self._sp set -- is a single-device forward; the checks hold for it too)
+        self._sp_window_check(getattr(self, "_sp", None) if sp is None else sp, "forward")
         if L_txt % 64:
             raise ValueError(f"frame-window attention needs a text length that is a multiple of 64 (the key prefix of "
                              f"osk_attention_fwd_window_bf16); got L_txt = {L_txt}")
@@ -1402,7 +1437,11 @@ class MMDiTModel(_OskState, nn.Module):
         """embeddings, vec, RoPE tables and the adaLN modulation of every block: everything in front of block 0"""
         ws, vec, rope = self.prepare_block_inputs(img, img_ids, txt, txt_ids, timesteps, y_vec, cond, guidance,
                                                   _shard=shard)
-        ws.attn_window = self._window_table(txt.shape[1], img.shape[1], sp)
+        table = self._window_table(txt.shape[1], img.shape[1], sp)
+        # one device: the table of the whole axis for _joint_attention.  Sharded: every rank builds the tables of its own rows
+        # (seqpar.SeqPar.window_table) from the geometry -- ws holds this rank's rows, so ws.attn_window stays None there
+        ws.attn_window = table if sp is None else None
+        ws.sp_window = None if (sp is None or table is None) else (txt.shape[1], img.shape[1]) + self._attn_window
         p = self._plan
         mod = torch.empty(img.shape[0], p["mod_cols"], dtype=torch.float32, device=img.device)
         _OPS.gemv_tasks(vec, p["mod_tasks"], mod, act_in=1)

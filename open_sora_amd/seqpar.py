@@ -45,6 +45,11 @@ Ltail = L - (P - 1) Lc that remain (SeqPar.split).  Every buffer above keeps P s
 only its Ltail rows -- so the collectives do not change; token-wise work runs on the true row count; attention sees P - 1 key segments of
 Lc keys and one of Ltail, which the kernels take as two launches and an in-place merge (osk_attention_fwd_ragged_bf16, bf16 / pv8 / qk8);
 the gathered prediction [P, B, Lc, C] is cut to L rows.  P | L never takes that path.  kv_chunks is ignored on a ragged split.
+
+Frame-window attention (MMDiTModel.set_attention_window, opt-in; bf16 attention, both modes): the window entry takes one key segment,
+so K and V travel token-major through the same collectives, osk_kv_join_bf16 lays the gathered segments out as K [B, L, D] and
+V^T [B, H, hd, round_up(L, 64)], and the rank runs osk_attention_fwd_window_bf16 on the table of its own rows -- once per source
+rank in head-exchange mode.  A ragged split is the join's short last segment.  See "frame-window attention" below.
 """
 from __future__ import annotations
 
@@ -131,7 +136,8 @@ class SeqPar:
         self.tp = transport if transport is not None else DistTransport(group)
         self.P, self.rank = self.tp.P, self.tp.rank
         self._bufs = {}
-        self.geom = None      # (Lc, Ltail) of the split shard_range() last made
+        self._win_tables = {}  # host tables of frame-window attention, per (geometry, W, rows): window_table()
+        self.geom = None     # (Lc, Ltail) of the split shard_range() last made
         self.exposed = None   # a list while bench.py measures exposed communication (see _timed_wait)
         self.mode = mode or os.environ.get("OSK_SP_MODE", "auto")   # "allgather" | "ulysses" | "auto"
         if self.mode not in ("allgather", "ulysses", "auto"):
@@ -361,7 +367,7 @@ class SeqPar:
                                  score_bound=score_bound if kind == "bf16" else 0.0, k_scale=k_scale, v_scale=v_scale)
 
     def gather_kv_start(self, ws, k: Tensor, v: Tensor, H: int, hd: int, pv8: bool = False, vt_ready: bool = False,
-                        qk8: bool = False):
+                        qk8: bool = False, window=None):
         """k, v: this rank's [B, L/P, D] views (K already normed + rotated with GLOBAL positions).  Starts the
         exchange of K and V and returns the handles; the caller keeps computing.
         pv8 (fp8 mode): V travels as e4m3 V^T (half the bytes); its per-(batch, head) scale must be the same on
@@ -371,6 +377,8 @@ class SeqPar:
         aside).  K's and V's scales come from one osk_kv_scale_fp8 launch into one [2, B, H] buffer: still ONE reducing collective."""
         pv8 = pv8 and hd in (72, 128)
         qk8 = qk8 and pv8 and hd == 128
+        if window is not None:     # frame-window attention (mmdit passes the argument only with the window on)
+            return self._window_kv_start(k, v, H, hd, pv8, vt_ready, window)
         if self.head_parallel(H):
             return self._heads_kv_start(k, v, H, hd, pv8, qk8)
         B, Lloc, _ = k.shape
@@ -431,6 +439,8 @@ class SeqPar:
         """Local queries against the gathered keys: one launch, P key segments of L/P keys.  score_bound: the block's bound on
         |q . k| (mmdit._score_bound; it holds for every key of the joint sequence whichever rank projected it) -- the kernel's
         FAST body takes segmented / ragged key layouts since round 4, so sequence-parallel calls run it too."""
+        if isinstance(pending[0], str) and pending[0] == "window":
+            return self._window_attention(pending, q, out, H, hd, score_bound)
         if isinstance(pending[0], str) and pending[0] == "heads":
             return self._heads_attention(pending, q, out, H, hd, score_bound)
         if isinstance(pending[0], str) and pending[0] == "ragged":
@@ -526,6 +536,10 @@ class SeqPar:
         """Head-parallel mode: start the all-to-all of the (normed, rotated, pre-scaled) queries and return the extended handle
         tuple -- whatever the caller queues before attention() overlaps it (single blocks: the MLP-up projection, the largest GEMM of
         the block; round 4 started this exchange inside attention() and waited on the spot).  All-gather mode: nothing to do."""
+        if isinstance(pending[0], str) and pending[0] == "window" and pending[1] == "heads" and len(pending) == 7:
+            bufs = pending[4]
+            self._to_head_chunks(bufs["qs"], q)
+            return (*pending, self.tp.all_to_all(bufs["qr"].view(-1), bufs["qs"].view(-1)))
         if not (isinstance(pending[0], str) and pending[0] == "heads") or len(pending) > 5:
             return pending
         bufs = pending[1]
@@ -614,6 +628,100 @@ class SeqPar:
                                  k_seg_stride=k_op.stride(0), vt_seg_stride=vt.stride(0), q_prescaled=True, kv_batches=B,
                                  workspace=ops.attention_ragged_workspace(P * B, Hg, Lc, hd, qr.device),
                                  score_bound=0.0 if pv8 else score_bound, k_scale=k_scale, v_scale=v_scale)
+        self._timed_wait(self.tp.all_to_all(bufs["orr"].view(-1), bufs["os"].view(-1)), "o")
+        self._from_head_chunks(out, bufs["orr"])
+
+    # ------------------------------------------------------------------ frame-window attention (bf16, both exchange modes)
+    # osk_attention_fwd_window_bf16 takes ONE key segment with the text prefix at keys [0, L_txt); the exchange buffers are
+    # segment-major with segments that are no multiple of 64 keys.  K and V therefore travel token-major through the same collectives
+    # (V instead of V^T: the same bytes), osk_kv_join_bf16 turns the gathered segments into K [B, L, D] and V^T [B, H, hd,
+    # round_up(L, 64)] in one HBM-bound launch, and the window entry runs on the table of the query rows in hand (row0 = the owning
+    # rank's first row): once in all-gather mode, once per source rank in head-exchange mode.  A ragged split is the join's short last
+    # segment: the ragged two-launch entry is not used here.  No attention kernel and no generated loop differs for it.
+    kv_window = True     # gather_kv_start takes window (mmdit asks before it passes the argument, like kv_qk8)
+
+    def window_table(self, spec, row0: int, n_rows: int) -> Tensor:
+        """host table of query rows [row0, row0 + n_rows) for spec = (L_txt, L_img, window_frames, frame_tokens): built once per
+        (geometry, rows, W) and kept; the binding keeps its device copy by content (_C._window_on_device)"""
+        key = (*spec, row0, n_rows)
+        tabs = self._win_tables
+        t = tabs.get(key)
+        if t is None:
+            while len(tabs) >= 64:
+                tabs.pop(next(iter(tabs)))
+            L_txt, L_img, W, N = spec
+            t = tabs[key] = mmdit.attention_window_table(L_txt, L_img, N, W, row0=row0, n_rows=n_rows)
+        return t
+
+    def _window_buffers(self, B: int, Lc: int, Ltail: int, Hl: int, hd: int, Lq: int, device, gather: bool):
+        """per geometry, like the gather buffers: the joined K [B, L, Hl*hd] and V^T [B, Hl, hd, round_up(L, 64)] of the Hl heads this
+        rank attends with, the window entry's workspace for calls of B batches of up to Lq rows, and (all-gather mode) the token-major
+        gather buffers of K and V -- P slots of Lc rows; the join never reads the pad rows of a short last slot, so nothing is zeroed"""
+        def make():
+            L = (self.P - 1) * Lc + Ltail
+            b = dict(kj=torch.empty(B, L, Hl * hd, dtype=BF16, device=device),
+                     vtj=torch.empty(B, Hl, hd, (L + 63) // 64 * 64, dtype=BF16, device=device),
+                     ws=torch.empty(max(mmdit.ops().attention_window_workspace_bytes(B, Hl, Lq, hd), 16), dtype=torch.uint8, device=device))
+            if gather:
+                b["k"] = torch.empty(self.P, B, Lc, Hl * hd, dtype=BF16, device=device)
+                b["v"] = torch.empty(self.P, B, Lc, Hl * hd, dtype=BF16, device=device)
+            return b
+
+        return self._cached(("window", gather, B, Lc, Ltail, Hl, hd, Lq, str(device), mmdit._stream_key(device)), make)
+
+    def _window_kv_start(self, k: Tensor, v: Tensor, H: int, hd: int, pv8: bool, vt_ready: bool, spec):
+        if pv8:
+            raise ValueError("frame-window attention under sequence parallelism has no fp8 path: enable_fp8(False) or set_attention_window(None)")
+        if self.kv_chunks > 1:
+            raise ValueError(f"frame-window attention under sequence parallelism takes one gather: kv_chunks = {self.kv_chunks} is refused")
+        assert not vt_ready, "local_vt() is not asked for with the window on: the projection writes V token-major"
+        B, Lloc, _ = k.shape
+        Lc, Ltail = self._geom(Lloc)
+        if (self.P - 1) * Lc + Ltail != spec[0] + spec[1]:
+            raise ValueError(f"frame-window attention: {self.P} ranks of {Lc} rows (last {Ltail}) are not the {spec[0]} + {spec[1]} rows of the window's geometry")
+        if self.head_parallel(H):
+            bufs = self._heads_buffers(B, Lc, H, hd, k.device, Ltail)
+            self._to_head_chunks(bufs["ks"], k)
+            wk = self.tp.all_to_all(bufs["kr"].view(-1), bufs["ks"].view(-1))
+            self._to_head_chunks(bufs["vs"], v)
+            wv = self.tp.all_to_all(bufs["vr"].view(-1), bufs["vs"].view(-1))
+            return "window", "heads", spec, (Lc, Ltail), bufs, wk, wv
+        bufs = self._window_buffers(B, Lc, Ltail, H, hd, Lloc, k.device, True)
+        ops = mmdit.ops()
+        ops.copy_rows(k, bufs["k"][self.rank][:, :Lloc])
+        wk = self.tp.all_gather(bufs["k"].view(-1), bufs["k"][self.rank].view(-1))
+        ops.copy_rows(v, bufs["v"][self.rank][:, :Lloc])
+        wv = self.tp.all_gather(bufs["v"].view(-1), bufs["v"][self.rank].view(-1))
+        return "window", "gather", spec, (Lc, Ltail), bufs, wk, wv
+
+    def _window_attention(self, pending, q: Tensor, out: Tensor, H: int, hd: int, score_bound: float):
+        """join, then the window entry: FAST body where the block's bound admits it, else the general one (the rule of
+        mmdit._joint_attention's window path)"""
+        pending = self.q_exchange_start(pending, q, H, hd)     # (head-exchange mode, a caller that did not start it earlier)
+        _, kind, spec, (Lc, Ltail), bufs, wk, wv, *wq = pending
+        P, L = self.P, (self.P - 1) * Lc + Ltail
+        ops = mmdit.ops()
+        bound = score_bound if 0.0 < score_bound <= mmdit.SCORE_BOUND_LIMIT else 0.0
+        kw = dict(n_prefix=spec[0], q_prescaled=True, score_bound=bound)
+        if kind == "gather":
+            self._timed_wait(wk, "k")
+            self._timed_wait(wv, "v")
+            ops.kv_join(bufs["k"], bufs["v"], bufs["kj"], bufs["vtj"], H, hd, L)
+            ops.attention_fwd_window(q, bufs["kj"], bufs["vtj"], out, H, hd, hd ** -0.5, workspace=bufs["ws"],
+                                     windows=self.window_table(spec, self.rank * Lc, q.shape[1]), **kw)
+            return
+        B, Hg = q.shape[0], H // P
+        jb = self._window_buffers(B, Lc, Ltail, Hg, hd, Lc, q.device, False)
+        self._timed_wait(wq[0], "q")
+        self._timed_wait(wk, "k")
+        self._timed_wait(wv, "v")
+        ops.kv_join(bufs["kr"], bufs["vr"], jb["kj"], jb["vtj"], Hg, hd, L)
+        # received query chunk p = source rank p's rows [p Lc, p Lc + rows): one call each with that rank's table, straight into the
+        # slot the return all-to-all sends; the calls share the workspace (one stream, in order)
+        for p_ in range(P):
+            rows = Ltail if p_ == P - 1 else Lc
+            ops.attention_fwd_window(bufs["qr"][p_][:, :rows], jb["kj"], jb["vtj"], bufs["os"][p_][:, :rows], Hg, hd, hd ** -0.5,
+                                     workspace=jb["ws"], windows=self.window_table(spec, p_ * Lc, rows), **kw)
         self._timed_wait(self.tp.all_to_all(bufs["orr"].view(-1), bufs["os"].view(-1)), "o")
         self._from_head_chunks(out, bufs["orr"])
 
