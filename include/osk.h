@@ -454,6 +454,15 @@ int osk_attention_fwd_ragged_bf16(const void* q, int64_t q_batch_stride, int64_t
  * of the rows, where osk_attention_merge_bf16 with S = 2 moves 6 bytes per element and needs two partial images beside out. */
 int osk_attention_merge_into_bf16(void* out, int64_t o_batch_stride, int64_t o_row_stride, float* lse, const float* o_b,
                                   const float* lse_b, int B, int H, int Lq, int hd, void* stream);
+/* The same with TWO partials (o_b, lse_b) and (o_c, lse_c), each laid out as above, folded into (out, lse) in ONE pass (an additive
+ * entry, the version stays 2): per (b, l, h) osk_attention_merge_bf16 with S = 3 -- f32 sums, ONE rounding.  A part whose lse is
+ * -inf contributes nothing (its row may hold anything); all three -inf: out = 0, lse = -inf, never NaN.  Arguments, alignment and
+ * status codes as osk_attention_merge_into_bf16 (o_c, lse_c as o_b, lse_b); hd in {64, 72, 128}.  HBM per output element: out read
+ * + written (2 + 2) + two f32 partials (4 + 4) = 12 bytes in 16-byte loads and stores, where two passes of the entry above move
+ * 16 and round twice.  No allocation, no memset, no atomics, no synchronisation: capturable in a hipGraph. */
+int osk_attention_merge_into2_bf16(void* out, int64_t o_batch_stride, int64_t o_row_stride, float* lse, const float* o_b,
+                                   const float* lse_b, const float* o_c, const float* lse_c, int B, int H, int Lq, int hd,
+                                   void* stream);
 
 /* ---- frame-window attention: every 256-row query block sees an always-attended key prefix and ONE run of 64-key tiles of the rest
  * (opt-in; an additive entry, the version stays 2).  It replaces nothing in the reference: opensora/models/mmdit/math.py:22-36 lets
@@ -518,6 +527,39 @@ int osk_attention_fwd_window_fp8_bf16(const void* q, int64_t q_batch_stride, int
                                       int64_t o_row_stride, float* lse, int B, int H, int Lq, int Lk, int n_prefix, int hd,
                                       float scale, int q_prescaled, int kv_batches, int mode, const int32_t* windows,
                                       int n_windows, void* workspace, int64_t workspace_bytes, void* stream);
+/* The window entries with always-attended TRAILING keys as well (an additive entry, the version stays 2): the mask a windowed video
+ * DiT wants for its conditioning ("anchor" / "sink") frames -- leading frames extend the prefix behind the text, trailing frames are
+ * the suffix.  Like the entries above it replaces nothing in the reference.  Mask, exact:
+ *   keys [0, n_prefix)    seen by every query.  n_prefix % 64 == 0, 0 <= n_prefix
+ *   keys [s0, Lk)         s0 = Lk - n_suffix: seen by every query.  n_suffix >= 0; with n_suffix > 0, s0 % 64 == 0 and s0 > n_prefix
+ *                         (the body keeps at least one tile); the tensor's last tile may be ragged (the kernels' own tail mask)
+ *   keys [n_prefix, s0)   the body; table tile j = body keys 64 j .. 64 j + 63 -- with n_suffix > 0 all whole tiles;
+ *                         rows 256 i .. 256 i + 255 see the tiles [first, first + count) of windows[i] and NOTHING else of the body.
+ *                         The kernel clamps a row to 0 <= first < tiles, 1 <= count <= tiles - first (a count of 0 is NOT an empty
+ *                         run: it reads as 1).
+ * Arguments: those of osk_attention_fwd_window_bf16 / osk_attention_fwd_window_fp8_bf16 (k_scale, v_scale: ignored by the modes
+ * that have none; score_bound: OSK_ATTN_BF16 only, ignored otherwise) plus n_suffix, and mode = OSK_ATTN_BF16 | OSK_ATTN_PV8 |
+ * OSK_ATTN_QK8 with the operands of osk_attention_fwd_ragged_bf16 for ONE key segment of Lk keys.  The call enqueues, on `stream`:
+ *   A  the body [n_prefix, s0) as a key axis of its own with the table, finished rows into out / lse,
+ *   B  the prefix from the tensors' origin into f32 partials in the workspace (every work unit, one part),
+ *   C  the suffix, entered s0 keys in as A is entered n_prefix keys in, into a second set of f32 partials,
+ *   M  ONE in-place three-part merge of B and C into A's rows (osk_attention_merge_into2_bf16's kernel: one rounding).
+ * n_suffix == 0: the launches and the result of the window entry of that mode, bit for bit.  n_prefix == 0 < n_suffix: A, C and
+ * the two-part merge.  Workspace: osk_attention_window_anchor_workspace_bytes(B, H, Lq, hd) (two partial sets + launch A's lse when
+ * the caller keeps none) is always enough; out 16-byte aligned, strides multiples of 8.
+ * OSK_EINVAL: the lists of the two entries above; a negative n_suffix, Lk - n_suffix no multiple of 64 or <= n_prefix (a suffix that
+ * reaches the prefix), a workspace short of what the launches in use need, a mode other than the three.  OSK_EUNSUPPORTED: as
+ * there.  A refused call launches nothing.  No allocation, no memset, no host synchronisation: capturable in a hipGraph.
+ * Cost over the window entry: launch C walks n_suffix keys per unit, B the longer prefix, and the merge moves 12 bytes per output
+ * element instead of 8.  Measured: profiles/attn_window.md. */
+int64_t osk_attention_window_anchor_workspace_bytes(int B, int H, int Lq, int hd);
+int osk_attention_fwd_window_anchor_bf16(const void* q, int64_t q_batch_stride, int64_t q_row_stride,
+                                         const void* k, int64_t k_batch_stride, int64_t k_row_stride, const float* k_scale,
+                                         const void* vt, const float* v_scale, void* out, int64_t o_batch_stride,
+                                         int64_t o_row_stride, float* lse, int B, int H, int Lq, int Lk, int n_prefix,
+                                         int n_suffix, int hd, float scale, int q_prescaled, int kv_batches, float score_bound,
+                                         int mode, const int32_t* windows, int n_windows, void* workspace,
+                                         int64_t workspace_bytes, void* stream);
 
 /* ---- short-sequence attention with an optional ALiBi bias (the STDiT-generation block's temporal
  * self-attention over T <= 64 frames, B * H * W independent sequences, "RoPE/ALiBi" in BASELINE.json's north_star).  The mounted

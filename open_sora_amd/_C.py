@@ -64,6 +64,10 @@ SIGNATURES = {
                                       _f32, _i32, _i32, _f32, _vp, _i32, _vp, _i64, _vp],
     "osk_attention_fwd_window_fp8_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32,
                                           _i32, _i32, _f32, _i32, _i32, _i32, _vp, _i32, _vp, _i64, _vp],
+    "osk_attention_merge_into2_bf16": [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
+    "osk_attention_window_anchor_workspace_bytes": [_i32, _i32, _i32, _i32],
+    "osk_attention_fwd_window_anchor_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32,
+                                             _i32, _i32, _i32, _f32, _i32, _i32, _f32, _i32, _vp, _i32, _vp, _i64, _vp],
     "osk_rownorm2_max_bf16": [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp],
     "osk_attention_workspace_bytes": [],
     "osk_v_scale_fp8": [_vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _vp],
@@ -130,6 +134,7 @@ def _load() -> C.CDLL:
         fn.restype = (C.c_char_p if name in ("osk_arch", "osk_attention_kernel_name", "osk_attention_body_name") else
                       _i64 if name in ("osk_attention_workspace_bytes", "osk_attention_hd512_workspace_bytes",
                                        "osk_attention_ragged_workspace_bytes", "osk_attention_window_workspace_bytes",
+                                       "osk_attention_window_anchor_workspace_bytes",
                                        "osk_step_delta_workspace_bytes") else _i32)
     if lib.osk_abi_version() != 2:
         raise ImportError("libosk_hip.so ABI version mismatch")
@@ -687,15 +692,17 @@ def attention_window_workspace(B: int, H: int, Lq: int, hd: int, device) -> torc
     return _grown_workspace("window", lib.osk_attention_window_workspace_bytes(B, H, Lq, hd), device)
 
 
-def check_window_table(windows: torch.Tensor, Lq: int, Lk: int, n_prefix: int) -> None:
+def check_window_table(windows: torch.Tensor, Lq: int, Lk: int, n_prefix: int, n_suffix: int = 0) -> None:
     """ValueError unless `windows` is a host int32 [ceil(Lq / 256), 2] table of (first tile, tile count) whose every row lies
-    inside the ceil((Lk - n_prefix) / 64) tiles of the body.  (The kernel clamps what it reads; a table it would have to clamp is a
-    host bug and is refused here.)"""
+    inside the ceil((Lk - n_suffix - n_prefix) / 64) tiles of the body.  (The kernel clamps what it reads; a table it would have to
+    clamp is a host bug and is refused here.)  n_suffix > 0 (attention_fwd_window_anchor): Lk - n_suffix a multiple of 64 beyond n_prefix."""
     if not (isinstance(windows, torch.Tensor) and windows.device.type == "cpu" and windows.dtype == torch.int32):
         raise ValueError("windows: a host (CPU) int32 tensor is expected")
     if n_prefix < 0 or n_prefix % 64 or n_prefix >= Lk:
         raise ValueError(f"n_prefix = {n_prefix}: a multiple of 64 in [0, Lk = {Lk}) is expected")
-    nqb, tiles = (Lq + 255) // 256, (Lk - n_prefix + 63) // 64
+    if n_suffix < 0 or (n_suffix > 0 and ((Lk - n_suffix) % 64 or Lk - n_suffix <= n_prefix)):
+        raise ValueError(f"n_suffix = {n_suffix}: 0, or Lk - n_suffix a multiple of 64 greater than n_prefix = {n_prefix} is expected (Lk = {Lk})")
+    nqb, tiles = (Lq + 255) // 256, (Lk - n_suffix - n_prefix + 63) // 64
     if windows.dim() != 2 or tuple(windows.shape) != (nqb, 2):
         raise ValueError(f"windows: shape {tuple(windows.shape)}, expected ({nqb}, 2) = one row per 256 query rows")
     first, n = windows[:, 0], windows[:, 1]
@@ -726,8 +733,9 @@ def _window_on_device(windows: torch.Tensor, device) -> torch.Tensor:
 
 
 def _attention_window(mode: int, q, k, k_scale, vt, v_scale, out, H, hd, scale, n_prefix, windows, lse, q_prescaled, kv_batches, score_bound,
-                      workspace, Lk):
-    """the body of attention_fwd_window (mode 0) and attention_fwd_window_fp8 (modes 1, 2): checks, table upload, the C call of the mode"""
+                      workspace, Lk, n_suffix=None):
+    """the body of attention_fwd_window (mode 0) and attention_fwd_window_fp8 (modes 1, 2): checks, table upload, the C call of the mode.
+    n_suffix (an int, 0 included): attention_fwd_window_anchor -- the same checks, the anchored entry with the mode as an argument"""
     assert out.dim() == 3 and q.shape == out.shape, (q.shape, out.shape)
     if mode == 2:
         assert Lk is not None and vt.dim() == 4, f"qk8: Lk = the key count (k8 only shows Lp = {k.shape[2]}); got {Lk}"
@@ -737,13 +745,24 @@ def _attention_window(mode: int, q, k, k_scale, vt, v_scale, out, H, hd, scale, 
     Lp = (Lk + 63) // 64 * 64
     kbs, krs = _attn_operands(mode, q, k, k_scale, vt, v_scale, out, lse, H, hd, kv_batches, Lk, vt_keys=Lp)
     B, Lq, _ = q.shape
-    check_window_table(windows, Lq, Lk, n_prefix)
+    check_window_table(windows, Lq, Lk, n_prefix, n_suffix or 0)
     assert vt.is_contiguous(), vt.stride()
+    if n_suffix is not None and workspace is None:
+        workspace = attention_window_anchor_workspace(B, H, Lq, hd, q.device)
     if n_prefix > 0 and workspace is None:
         workspace = attention_window_workspace(B, H, Lq, hd, q.device)
     win = _window_on_device(windows, q.device)
     if CHECK_SCORE_BOUND and mode == 0 and score_bound > 0 and not torch.cuda.is_current_stream_capturing():
         _assert_score_bound(q, k, H, hd, scale, 1, Lk, 0, q_prescaled, kv_batches, score_bound)
+    if n_suffix is not None:
+        with _attn_prof():
+            _check(lib.osk_attention_fwd_window_anchor_bf16(q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), kbs, krs, _p(k_scale),
+                                                            vt.data_ptr(), _p(v_scale), out.data_ptr(), out.stride(0), out.stride(1),
+                                                            _p(lse), B, H, Lq, Lk, n_prefix, int(n_suffix), hd, scale, int(q_prescaled),
+                                                            kv_batches, float(score_bound), mode, win.data_ptr(), win.shape[0],
+                                                            workspace.data_ptr(), workspace.numel(), _stream()),
+                   "osk_attention_fwd_window_anchor_bf16")
+        return out
     name = "osk_attention_fwd_window_bf16" if mode == 0 else "osk_attention_fwd_window_fp8_bf16"
     own = (float(score_bound),) if mode == 0 else (mode,)          # the argument between kv_batches and the table
     fp8 = ((_p(k_scale),), (v_scale.data_ptr(),)) if mode else ((), ())   # the scale vectors behind K's strides and behind V^T
@@ -765,6 +784,50 @@ def attention_fwd_window(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out
     n_prefix > 0 (taken from there when None)."""
     return _attention_window(0, q, k, None, vt, None, out, H, hd, scale, n_prefix, windows, lse, q_prescaled, kv_batches, score_bound,
                              workspace, None)
+
+
+def attention_window_anchor_workspace_bytes(B: int, H: int, Lq: int, hd: int) -> int:
+    """bytes attention_fwd_window_anchor needs for these query dimensions: two partial sets and launch A's lse"""
+    return int(lib.osk_attention_window_anchor_workspace_bytes(B, H, Lq, hd))
+
+
+def attention_window_anchor_workspace(B: int, H: int, Lq: int, hd: int, device) -> torch.Tensor:
+    """workspace of attention_fwd_window_anchor for these query dimensions, one per (device, stream); grows to the largest request"""
+    return _grown_workspace("window_anchor", lib.osk_attention_window_anchor_workspace_bytes(B, H, Lq, hd), device)
+
+
+def attention_fwd_window_anchor(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Tensor, H: int, hd: int, scale: float, *,
+                                n_prefix: int, n_suffix: int, windows: torch.Tensor, mode: str = "bf16", k_scale: torch.Tensor | None = None,
+                                v_scale: torch.Tensor | None = None, lse=None, q_prescaled: bool = False, kv_batches: int = 0,
+                                score_bound: float = 0.0, workspace: torch.Tensor | None = None, Lk: int | None = None):
+    """frame-window attention with always-attended keys at BOTH ends (osk_attention_fwd_window_anchor_bf16): every query sees keys
+    [0, n_prefix) and [Lk - n_suffix, Lk); the 256-row query block i sees, of the body keys between them, the 64-key tiles
+    windows[i] = (first, count) and nothing else.  mode "bf16" (k, vt, score_bound as attention_fwd_window), "pv8" (vt = vt8 with
+    v_scale) or "qk8" (k = k8 with k_scale too, Lk given), the operands of attention_fwd_window_fp8.  n_suffix = 0 is the window
+    entry of that mode.  windows: HOST int32 [ceil(Lq / 256), 2] over the body's tiles, validated here.  workspace: from
+    attention_window_anchor_workspace() (taken from there when None)."""
+    if mode != "bf16" and mode not in ATTN_MODES:
+        raise ValueError(f"attention_fwd_window_anchor: mode {mode!r}, expected 'bf16', 'pv8' or 'qk8'")
+    m = 0 if mode == "bf16" else ATTN_MODES[mode]
+    return _attention_window(m, q, k, k_scale if m == 2 else None, vt, v_scale if m else None, out, H, hd, scale, n_prefix, windows, lse,
+                             q_prescaled, kv_batches, score_bound if m == 0 else 0.0, workspace, Lk, n_suffix=int(n_suffix))
+
+
+def attention_merge_into2(out: torch.Tensor, lse: torch.Tensor, o_b: torch.Tensor, lse_b: torch.Tensor, o_c: torch.Tensor,
+                          lse_c: torch.Tensor, H: int, hd: int) -> torch.Tensor:
+    """fold TWO further attention results over other keys into (out, lse) in place, in one pass and with one rounding
+    (osk_attention_merge_into2_bf16): the arguments of attention_merge_into with a second partial (o_c, lse_c) laid out as (o_b, lse_b)."""
+    assert out.dim() == 3 and out.dtype == torch.bfloat16 and out.shape[2] == H * hd and out.stride(2) == 1, (out.shape, out.dtype, out.stride())
+    B, Lq, _ = out.shape
+    Lqp = (Lq + 255) // 256 * 256
+    assert out.stride(0) % 8 == 0 and out.stride(1) % 8 == 0 and out.data_ptr() % 16 == 0, (out.stride(), out.data_ptr() % 16)
+    assert lse.dtype == torch.float32 and lse.is_contiguous() and tuple(lse.shape) == (B, H, Lq), (lse.dtype, lse.shape)
+    for o_, l_ in ((o_b, lse_b), (o_c, lse_c)):
+        assert o_.dtype == torch.float32 and o_.is_contiguous() and tuple(o_.shape) == (B, H, Lqp, hd) and o_.data_ptr() % 16 == 0, (o_.dtype, o_.shape)
+        assert l_.dtype == torch.float32 and l_.is_contiguous() and tuple(l_.shape) == (B, H, Lqp), (l_.dtype, l_.shape)
+    _check(lib.osk_attention_merge_into2_bf16(out.data_ptr(), out.stride(0), out.stride(1), lse.data_ptr(), o_b.data_ptr(), lse_b.data_ptr(),
+                                              o_c.data_ptr(), lse_c.data_ptr(), B, H, Lq, hd, _stream()), "osk_attention_merge_into2_bf16")
+    return out
 
 
 def attention_merge_into(out: torch.Tensor, lse: torch.Tensor, o_b: torch.Tensor, lse_b: torch.Tensor, H: int, hd: int) -> torch.Tensor:

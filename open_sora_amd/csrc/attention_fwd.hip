@@ -9,6 +9,7 @@
 #include <atomic>
 #include <initializer_list>
 #include "attention_params.h"
+#include "attention_merge_into2.h"
 #include "../../include/osk.h"
 
 using osk_attn::AttnParams;
@@ -754,6 +755,24 @@ static int run_pair(AttnParams& a, AttnParams& b, int hd, int mode, bool dispatc
   return osk_attn::launch_merge_into(b, hd, 0.6931471805599453f, st);
 }
 
+// The same with TWO partial launches over two further key sets (the anchored window entry: prefix B, suffix C) and ONE three-part merge.
+// workspace: [f32 partials of launch B | f32 partials of launch C | lse of launch A when the caller keeps none].  Launch A is launched as
+// the caller shaped it; B and C share the unit order (p.map) and the slot layout, which is all the merge needs of them.
+static int run_triple(AttnParams& a, AttnParams& b, AttnParams& c, int hd, int mode, void* workspace, hipStream_t st) {
+  const int64_t part = ragged_partial_bytes(a.B, a.H, a.Lq, hd);
+  if (!a.lse) a.lse = (float*)((char*)workspace + 2 * part);
+  partial_launch(b, hd, workspace);
+  partial_launch(c, hd, (char*)workspace + part);
+  int rc = run_mode(a, hd, mode, st);
+  if (rc != 0) return rc;
+  rc = run_mode(b, hd, mode, st);
+  if (rc != 0) return rc;
+  rc = run_mode(c, hd, mode, st);
+  if (rc != 0) return rc;
+  b.out = a.out; b.lse = a.lse;
+  return osk_attn::launch_merge_into2(b, c.ws_o, c.ws_lse, hd, 0.6931471805599453f, st);
+}
+
 extern "C" int osk_attention_fwd_ragged_bf16(const void* q, int64_t q_batch_stride, int64_t q_row_stride,
                                              const void* k, int64_t k_seg_stride, int64_t k_batch_stride, int64_t k_row_stride,
                                              const float* k_scale, const void* vt, int64_t vt_seg_stride, const float* v_scale,
@@ -795,6 +814,11 @@ extern "C" int64_t osk_attention_window_workspace_bytes(int B, int H, int Lq, in
   if (B <= 0 || H <= 0 || Lq <= 0 || hd <= 0) return 0;
   return ragged_partial_bytes(B, H, Lq, hd) + ragged_lse_bytes(B, H, Lq);
 }
+// anchored (osk_attention_fwd_window_anchor_bf16): two partial sets -- the prefix launch's and the suffix launch's -- and launch A's lse
+extern "C" int64_t osk_attention_window_anchor_workspace_bytes(int B, int H, int Lq, int hd) {
+  if (B <= 0 || H <= 0 || Lq <= 0 || hd <= 0) return 0;
+  return 2 * ragged_partial_bytes(B, H, Lq, hd) + ragged_lse_bytes(B, H, Lq);
+}
 
 // One function behind osk_attention_fwd_window_bf16 (mode OSK_ATTN_BF16, score_bound) and osk_attention_fwd_window_fp8_bf16 (the fp8
 // operands of osk_attention_fwd_pv8_bf16 -- OSK_ATTN_PV8: bf16 K in place, e4m3 V^T -- or of osk_attention_fwd_qk8_bf16 -- OSK_ATTN_QK8:
@@ -807,15 +831,27 @@ extern "C" int64_t osk_attention_window_workspace_bytes(int B, int H, int Lq, in
 // Launch A does not go through dispatch(): it keeps rows = 256, tail_first = 0x7fffffff, tail_split = 1 (the table is per 256 rows and a
 // windowed unit has a key run of its own; split_tail() would return at p.win anyway, and only launch_shape() -- bf16 mode -- ever picks
 // the wide layout).
+// n_suffix > 0 (osk_attention_fwd_window_anchor_bf16): the last n_suffix keys [s0, Lk), s0 = Lk - n_suffix a multiple of 64 beyond n_prefix,
+// are always attended as well.  The body -- and the table's tile axis -- then ends at s0 (whole tiles: launch A is never ragged), and
+// launch C walks the suffix for every query as a partial launch entered s0 keys in, exactly as launch A enters n_prefix keys in: the ragged
+// last tile of the tensor is the ragged last tile of a launch over n_suffix keys.  B and C fold into A's rows in ONE pass (run_triple());
+// without a prefix C alone does, through run_pair().  n_suffix == 0 is the code path from before, launch for launch.
 static int window_fwd(int mode, const void* q, int64_t q_batch_stride, int64_t q_row_stride, const void* k, int64_t k_batch_stride,
                       int64_t k_row_stride, const float* k_scale, const void* vt, const float* v_scale, void* out, int64_t o_batch_stride,
                       int64_t o_row_stride, float* lse, int B, int H, int Lq, int Lk, int n_prefix, int hd, float scale, int q_prescaled,
                       int kv_batches, float score_bound, const int32_t* windows, int n_windows, void* workspace, int64_t workspace_bytes,
-                      void* stream) {
+                      void* stream, int n_suffix = 0) {
   if (!windows || ((uintptr_t)windows & 3)) return OSK_EINVAL;
   if (Lq <= 0 || Lk <= 0 || n_windows != (Lq + 255) / 256 || n_prefix < 0 || (n_prefix & 63) || n_prefix >= Lk) return OSK_EINVAL;
-  // (n_prefix == 0: a single launch, no partials, no workspace)
-  if (n_prefix > 0 && !merge_args_ok(out, o_batch_stride, o_row_stride, lse, B, H, Lq, hd, workspace, workspace_bytes)) return OSK_EINVAL;
+  // the suffix starts on a tile of the whole tensor and leaves the body at least one tile (s0 <= n_prefix: a suffix that reaches the prefix)
+  if (n_suffix < 0 || (n_suffix > 0 && (((Lk - n_suffix) & 63) || Lk - n_suffix <= n_prefix))) return OSK_EINVAL;
+  const int s0 = Lk - n_suffix;
+  // (n_prefix == 0 and n_suffix == 0: a single launch, no partials, no workspace)
+  if ((n_prefix > 0 || n_suffix > 0) && !merge_args_ok(out, o_batch_stride, o_row_stride, lse, B, H, Lq, hd, workspace, workspace_bytes))
+    return OSK_EINVAL;
+  if (n_prefix > 0 && n_suffix > 0 && B > 0 && H > 0 && hd > 0 &&
+      workspace_bytes < 2 * ragged_partial_bytes(B, H, Lq, hd) + (lse ? 0 : ragged_lse_bytes(B, H, Lq)))
+    return OSK_EINVAL;
   AttnParams a;
   const int rc = mode_params(a, mode, k_scale, v_scale, 3, score_bound, q, q_batch_stride, q_row_stride, k, 0, k_batch_stride, k_row_stride, vt,
                              0, out, o_batch_stride, o_row_stride, lse, B, H, Lq, 1, Lk, hd, scale, q_prescaled, kv_batches, workspace,
@@ -828,7 +864,7 @@ static int window_fwd(int mode, const void* q, int64_t q_batch_stride, int64_t q
   // is the caller's batch stride of that one tensor (H * Lp * 128 when packed), which set_segments() does not touch -- the ragged entry
   // re-derives it only because its last segment is a tensor of its own with another Lp.
   const int64_t seg_lp = a.seg_lp;
-  AttnParams b = a;
+  AttnParams b = a, c = a;
   // launch A: the body, windowed, entered n_prefix keys in.  bf16 K: n_prefix rows of krs elements.  e4m3 K: n_prefix rows of 128
   // bytes inside every head's [Lp, 128] block.  V^T: n_prefix positions along the key axis of EVERY row -- in the e4m3 layout the hd dims
   // and the validity / denominator row hd alike, since all rows of a head share the one base pointer and the row stride seg_lp.  n_prefix
@@ -838,14 +874,23 @@ static int window_fwd(int mode, const void* q, int64_t q_batch_stride, int64_t q
   if (a.k8) a.k8 += (int64_t)n_prefix * 128;
   if (a.vt) a.vt += n_prefix;
   if (a.vt8) a.vt8 += n_prefix;
-  set_segments(a, 1, Lk - n_prefix);
+  set_segments(a, 1, s0 - n_prefix);
   a.seg_lp = (int)seg_lp;
   a.win = windows;
-  if (n_prefix == 0) return run_mode(a, hd, mode, (hipStream_t)stream);
+  if (n_prefix == 0 && n_suffix == 0) return run_mode(a, hd, mode, (hipStream_t)stream);
   // launch B: the prefix alone from the tensors' origin -- whole tiles (n_prefix % 64 == 0: never ragged), the same scales and bound
   set_segments(b, 1, n_prefix);
   b.seg_lp = (int)seg_lp;
-  return run_pair(a, b, hd, mode, /* dispatch_a */ false, workspace, workspace_bytes, (hipStream_t)stream);
+  if (n_suffix == 0) return run_pair(a, b, hd, mode, /* dispatch_a */ false, workspace, workspace_bytes, (hipStream_t)stream);
+  // launch C: the suffix alone, entered s0 keys in by the rule of launch A; its last tile is the tensor's (ragged where Lk % 64 != 0)
+  if (c.k) c.k += (int64_t)s0 * c.krs;
+  if (c.k8) c.k8 += (int64_t)s0 * 128;
+  if (c.vt) c.vt += s0;
+  if (c.vt8) c.vt8 += s0;
+  set_segments(c, 1, n_suffix);
+  c.seg_lp = (int)seg_lp;
+  if (n_prefix == 0) return run_pair(a, c, hd, mode, /* dispatch_a */ false, workspace, workspace_bytes, (hipStream_t)stream);
+  return run_triple(a, b, c, hd, mode, workspace, (hipStream_t)stream);
 }
 
 extern "C" int osk_attention_fwd_window_bf16(const void* q, int64_t q_batch_stride, int64_t q_row_stride,
@@ -871,3 +916,17 @@ extern "C" int osk_attention_fwd_window_fp8_bf16(const void* q, int64_t q_batch_
                     workspace_bytes, stream);
 }
 
+// The window entries with always-attended trailing keys as well (anchor frames: MMDiTModel.set_attention_window(anchors=...)); one entry
+// for the three operand kinds, as the ragged entry has.
+extern "C" int osk_attention_fwd_window_anchor_bf16(const void* q, int64_t q_batch_stride, int64_t q_row_stride,
+                                                    const void* k, int64_t k_batch_stride, int64_t k_row_stride, const float* k_scale,
+                                                    const void* vt, const float* v_scale, void* out, int64_t o_batch_stride,
+                                                    int64_t o_row_stride, float* lse, int B, int H, int Lq, int Lk, int n_prefix,
+                                                    int n_suffix, int hd, float scale, int q_prescaled, int kv_batches, float score_bound,
+                                                    int mode, const int32_t* windows, int n_windows, void* workspace,
+                                                    int64_t workspace_bytes, void* stream) {
+  if (mode != OSK_ATTN_BF16 && mode != OSK_ATTN_PV8 && mode != OSK_ATTN_QK8) return OSK_EINVAL;
+  return window_fwd(mode, q, q_batch_stride, q_row_stride, k, k_batch_stride, k_row_stride, k_scale, vt, v_scale, out, o_batch_stride,
+                    o_row_stride, lse, B, H, Lq, Lk, n_prefix, hd, scale, q_prescaled, kv_batches, mode == OSK_ATTN_BF16 ? score_bound : 0.f,
+                    windows, n_windows, workspace, workspace_bytes, stream, n_suffix);
+}

@@ -12,7 +12,10 @@
 //
 // osk_attention_merge_into_bf16 (attn_merge_into_kernel below): the two-part form that updates one finished (out, lse) pair IN
 // PLACE from the f32 partial of a second launch over other keys -- the last-segment launch of osk_attention_fwd_ragged_bf16.
+// osk_attention_merge_into2_bf16 (attn_merge_into2_kernel, attention_merge_into2.h): the same with TWO partials in one pass -- the prefix and suffix launches
+// of osk_attention_fwd_window_anchor_bf16.
 #include "attention_params.h"
+#include "attention_merge_into2.h"
 #include "../../include/osk.h"
 
 using osk_attn::AttnParams;
@@ -166,6 +169,24 @@ extern "C" int osk_attention_merge_into_bf16(void* out, int64_t o_batch_stride, 
   p.map = OSK_ATTN_ORDER_PLAIN;
   p.ws_o = const_cast<float*>(o_b); p.ws_lse = const_cast<float*>(lse_b);
   return osk_attn::launch_merge_into(p, hd, 1.0f, (hipStream_t)stream);
+}
+
+extern "C" int osk_attention_merge_into2_bf16(void* out, int64_t o_batch_stride, int64_t o_row_stride, float* lse, const float* o_b,
+                                              const float* lse_b, const float* o_c, const float* lse_c, int B, int H, int Lq, int hd,
+                                              void* stream) {
+  if (!out || !lse || !o_b || !lse_b || !o_c || !lse_c || B <= 0 || H <= 0 || Lq <= 0) return OSK_EINVAL;
+  if ((o_batch_stride & 7) || (o_row_stride & 7) || o_batch_stride < 0 || o_row_stride < (int64_t)H * hd) return OSK_EINVAL;
+  if (((uintptr_t)out & 15) || ((uintptr_t)o_b & 15) || ((uintptr_t)o_c & 15) || ((uintptr_t)lse & 3) || ((uintptr_t)lse_b & 3) ||
+      ((uintptr_t)lse_c & 3))
+    return OSK_EINVAL;
+  if (hd != 64 && hd != 72 && hd != 128) return OSK_EUNSUPPORTED;
+  AttnParams p{};
+  p.out = (unsigned short*)out; p.obs = o_batch_stride; p.ors = o_row_stride;
+  p.lse = lse; p.B = B; p.H = H; p.Lq = Lq;
+  p.rows = 256;
+  p.map = OSK_ATTN_ORDER_PLAIN;
+  p.ws_o = const_cast<float*>(o_b); p.ws_lse = const_cast<float*>(lse_b);
+  return osk_attn::launch_merge_into2(p, o_c, lse_c, hd, 1.0f, (hipStream_t)stream);
 }
 
 extern "C" int osk_attention_merge_bf16(const void* parts, int64_t part_stride, int64_t p_batch_stride, int64_t p_row_stride,

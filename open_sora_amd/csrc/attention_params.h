@@ -180,6 +180,7 @@ int launch_merge(const AttnParams& p, int hd, hipStream_t st);
 // unit_order: p.map's (the launch order of the attention kernels), or OSK_ATTN_ORDER_PLAIN = unit (b * H + h) * nqb + qb
 #define OSK_ATTN_ORDER_PLAIN 2
 int launch_merge_into(const AttnParams& p, int hd, float lse_b_mult, hipStream_t st);
+// (the same with a second partial in one pass: launch_merge_into2 of attention_merge_into2.h)
 
 // attention_asm72.hip: head_dim 72, 4 waves x 64 query rows, hand-scheduled (generated) main loop
 int launch_asm72(const AttnParams& p, hipStream_t st);

@@ -543,6 +543,10 @@ class _Workspace:
         self.attn_window = None
         self.win_ws = None
         self.sp_window = None   # sharded forward with the window on: (L_txt, L_img, window_frames, frame_tokens) of the FULL sequence
+        # anchor frames (set_attention_window(anchors=...)): (n_prefix, n_suffix) of this forward or None = the text prefix alone;
+        # the anchored entry's workspace (two partial sets) is a buffer of its own, sized once per geometry like win_ws
+        self.attn_anchor = None
+        self.win_anchor_ws = None
 
     def y_double(self, D):
         return self.y[: self.B * self.L * 3 * D].view(self.B, self.L, 3 * D)
@@ -694,7 +698,33 @@ def _bf16_operands(*xs) -> bool:
     return all(not isinstance(x, (tuple, Fp8Weight)) for x in xs)
 
 
-def attention_window_table(L_txt: int, L_img: int, frame_tokens: int, window_frames: int, *, row0: int = 0, n_rows: int | None = None) -> Tensor:
+def attention_window_bounds(L_txt: int, L_img: int, frame_tokens: int, anchor_head: int = 0, anchor_tail: int = 0) -> tuple[int, int]:
+    """(n_prefix, n_suffix) of frame-window attention with anchor frames: every query attends to the text, the first anchor_head and
+    the last anchor_tail frames.  Keys are [txt | frame 0 | ... | frame T - 1], L = L_txt + L_img, N = frame_tokens.  Both bounds
+    are tile-aligned, because V^T is laid out in 64-key tiles counted from key 0 and a launch can only enter the key axis at a
+    multiple of 64:  n_prefix = round_up(L_txt + anchor_head N, 64);  s0 = round_down(L - anchor_tail N, 64), n_suffix = L - s0 for
+    anchor_tail > 0, else 0.  Rounding OUTWARD makes this a superset of the stated frames: where N is no multiple of 64, up to 63
+    keys of frame anchor_head join the prefix and up to 63 keys of frame T - anchor_tail - 1 join the suffix.  Without anchors
+    (0, 0) the result is (L_txt, 0), whatever L_txt.  ValueError when the anchors leave no body (s0 <= n_prefix): that is the full
+    attention -- turn the window off instead."""
+    if L_txt < 0 or L_img <= 0 or frame_tokens <= 0 or anchor_head < 0 or anchor_tail < 0:
+        raise ValueError(f"attention_window_bounds: L_txt >= 0, L_img > 0, frame_tokens > 0, anchors >= 0 expected; got "
+                         f"{(L_txt, L_img, frame_tokens, anchor_head, anchor_tail)}")
+    if L_img % frame_tokens:
+        raise ValueError(f"attention_window_bounds: {L_img} image tokens are not whole frames of {frame_tokens}")
+    if anchor_head == 0 and anchor_tail == 0:
+        return L_txt, 0
+    L = L_txt + L_img
+    n_prefix = (L_txt + anchor_head * frame_tokens + 63) // 64 * 64
+    s0 = (L - anchor_tail * frame_tokens) // 64 * 64 if anchor_tail > 0 else L
+    if s0 <= n_prefix:
+        raise ValueError(f"attention_window_bounds: anchors ({anchor_head}, {anchor_tail}) of {L_img // frame_tokens} frames leave no "
+                         f"windowed keys (prefix [0, {n_prefix}), suffix [{s0}, {L})): that is the full attention, turn the window off")
+    return n_prefix, L - s0
+
+
+def attention_window_table(L_txt: int, L_img: int, frame_tokens: int, window_frames: int, *, row0: int = 0, n_rows: int | None = None,
+                           anchor_head: int = 0, anchor_tail: int = 0) -> Tensor:
     """The key ranges of frame-window attention on the joint [txt; img] sequence, for osk_attention_fwd_window_bf16 with
     n_prefix = L_txt: host int32 [ceil((L_txt + L_img) / 256), 2] of (first tile, tile count), one row per 256 query rows, in
     64-key tiles of the image keys.  Frame f is image rows [f N, (f + 1) N), N = frame_tokens, T = L_img / N frames, W =
@@ -704,7 +734,13 @@ def attention_window_table(L_txt: int, L_img: int, frame_tokens: int, window_fra
     the keys that share a tile with the range's ends -- up to 255 rows' worth of frames and 63 keys per side more than its own.
     row0 / n_rows (a sequence-parallel rank's share, seqpar.SeqPar): the table of query rows [row0, row0 + n_rows) of the joint axis
     alone, cut into 256-row blocks that START AT row0 -- [ceil(n_rows / 256), 2], the same rule per block, the key tiles still those
-    of all L_img image keys.  The defaults describe the whole axis."""
+    of all L_img image keys.  The defaults describe the whole axis.
+    anchor_head / anchor_tail (osk_attention_fwd_window_anchor_bf16 with attention_window_bounds' n_prefix, n_suffix): the tiles
+    are those of the BODY keys [n_prefix, s0) between the always-attended ends -- the same rule, frames f0 - W .. f1 + W rounded
+    outward, then clipped to the body.  A block holding a text row keeps every body tile.  A block whose run falls entirely inside
+    the anchors would have an empty run; the kernel reads a count of 0 as 1 (key_part() of csrc/attention_params.h clamps to >= 1),
+    so such a block gets the ONE body tile nearest its frames -- the first for a run inside the prefix, the last for one inside the
+    suffix: still a superset.  With (0, 0) the table is the one from before, bit for bit."""
     if L_txt < 0 or L_img <= 0 or frame_tokens <= 0 or window_frames < 0:
         raise ValueError(f"attention_window_table: L_txt >= 0, L_img > 0, frame_tokens > 0, window_frames >= 0 expected; got {(L_txt, L_img, frame_tokens, window_frames)}")
     if L_img % frame_tokens:
@@ -725,18 +761,63 @@ def attention_window_table(L_txt: int, L_img: int, frame_tokens: int, window_fra
         f0, f1 = (r0 - L_txt) // N, (r1 - L_txt) // N
         k0, k1 = max(0, f0 - W) * N, min(T, f1 + W + 1) * N
         rows.append((k0 // 64, (k1 + 63) // 64 - k0 // 64))
-    return torch.tensor(rows, dtype=torch.int32)
+    if anchor_head == 0 and anchor_tail == 0:
+        return torch.tensor(rows, dtype=torch.int32)
+    # anchored: the same runs as key ranges of the joint axis, clipped to the body [n_prefix, s0) and counted in ITS tiles
+    n_prefix, n_suffix = attention_window_bounds(L_txt, L_img, N, anchor_head, anchor_tail)
+    body = (L - n_suffix - n_prefix + 63) // 64
+    clipped = []
+    for t0, n in rows:
+        if (t0, n) == (0, tiles):                      # (a text block, or a window that spans every frame)
+            clipped.append((0, body))
+            continue
+        lo = (L_txt + t0 * 64 - n_prefix) // 64         # floor: outward; may be negative
+        hi = -((n_prefix - L_txt - (t0 + n) * 64) // 64)   # ceil of the run's end in body tiles
+        lo, hi = max(lo, 0), min(hi, body)
+        if hi <= lo:                                   # entirely inside an anchor: the nearest body tile (a count of 0 reads as 1)
+            lo = 0 if hi <= 0 else body - 1
+            hi = lo + 1
+        clipped.append((lo, hi - lo))
+    return torch.tensor(clipped, dtype=torch.int32)
 
 
-def window_tile_fraction(table: Tensor, L_txt: int, L_img: int) -> float:
-    """key tiles a windowed forward visits / those a full one does, over the query blocks of the table (text tiles included)"""
+def window_tile_fraction(table: Tensor, L_txt: int, L_img: int, bounds=None) -> float:
+    """key tiles a windowed forward visits / those a full one does, over the query blocks of the table (text tiles included).
+    bounds: (n_prefix, n_suffix) of an anchored table (attention_window_bounds) -- the always-attended tiles at both ends"""
     txt_tiles, tiles = (L_txt + 63) // 64, (L_img + 63) // 64
+    if bounds is not None:
+        fixed = bounds[0] // 64 + (bounds[1] + 63) // 64
+        return float((table[:, 1].double() + fixed).sum() / (table.shape[0] * ((L_txt + L_img + 63) // 64)))
     return float((table[:, 1].double() + txt_tiles).sum() / (table.shape[0] * (tiles + txt_tiles)))
 
 
 def _window_env_default():
     v = os.environ.get("OSK_ATTN_WINDOW_FRAMES", "").strip()
     return int(v) if v else None
+
+
+def parse_window_anchors(anchors, who: str = "anchors"):
+    """(head, tail) of always-attended leading / trailing frames from None, a pair of non-negative ints or the "h,t" text of
+    OSK_ATTN_WINDOW_ANCHORS; None for no anchors ((0, 0) included)"""
+    if anchors is None:
+        return None
+    if isinstance(anchors, str):
+        if not anchors.strip():
+            return None
+        anchors = anchors.split(",")
+    try:
+        h, t = (int(a) for a in anchors)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: (head, tail), two non-negative frame counts, expected; got {anchors!r}") from None
+    if h < 0 or t < 0:
+        raise ValueError(f"{who}: (head, tail), two non-negative frame counts, expected; got {(h, t)}")
+    return (h, t) if (h, t) != (0, 0) else None
+
+
+def _window_anchor_ok() -> bool:
+    """does the kernel table have the anchored frame-window entry?  (looked up like _window_fp8_ok: a substituted table from before
+    the entry keeps the calls it was written against and refuses anchors)"""
+    return hasattr(_OPS, "attention_fwd_window_anchor")
 
 
 def _window_fp8_ok() -> bool:
@@ -784,6 +865,27 @@ def _joint_attention(ws: _Workspace, q: Tensor, k: Tensor, v: Tensor, H: int, hd
         # where the plan's weight-derived bound admits it, else the general body (no auto-dispatched pair for this entry)
         if pv8 and not _window_fp8_ok():
             raise ValueError("frame-window attention has no fp8 kernels: disable enable_fp8() or set_attention_window(None)")
+        if getattr(ws, "attn_anchor", None) is not None:
+            # anchor frames: ONE call of the anchored entry in the mode the window would run in (the same operand preparation,
+            # the same bound rule); the prefix covers the text and the leading frames, the suffix the trailing ones
+            if not _window_anchor_ok():
+                raise ValueError("frame-window attention: this kernel table has no anchored entry (attention_fwd_window_anchor); "
+                                 "set_attention_window(..., anchors=None)")
+            if ws.win_anchor_ws is None:
+                ws.win_anchor_ws = torch.empty(_OPS.attention_window_anchor_workspace_bytes(q.shape[0], H, q.shape[1], hd),
+                                               dtype=torch.uint8, device=q.device)
+            kw = dict(n_prefix=ws.attn_anchor[0], n_suffix=ws.attn_anchor[1], windows=ws.attn_window, q_prescaled=True,
+                      workspace=ws.win_anchor_ws)
+            if pv8 and hd in (72, 128):
+                kk, sk, vt8, sv = _fp8_operands(ws, k, v, H, hd, qk8)
+                _OPS.attention_fwd_window_anchor(q, kk, vt8, v, H, hd, hd ** -0.5, mode=_window_mode(pv8, qk8, hd), k_scale=sk,
+                                                 v_scale=sv, Lk=k.shape[1], **kw)
+                return
+            if not vt_ready:
+                _OPS.v_transpose(v, ws.vt, H, hd)
+            _OPS.attention_fwd_window_anchor(q, k, ws.vt, v, H, hd, hd ** -0.5, mode="bf16",
+                                             score_bound=score_bound if 0.0 < score_bound <= SCORE_BOUND_LIMIT else 0.0, **kw)
+            return
         if ws.win_ws is None:
             ws.win_ws = torch.empty(_OPS.attention_window_workspace_bytes(q.shape[0], H, q.shape[1], hd), dtype=torch.uint8, device=q.device)
         if pv8 and hd in (72, 128):
@@ -1131,6 +1233,8 @@ class MMDiTModel(_OskState, nn.Module):
         self._sp = None  # set by open_sora_amd.seqpar.enable
         self._attn_window = None        # (window_frames, frame_tokens) or None: set_attention_window; a plain attribute, not in state_dict
         self._attn_window_table = None  # ((L_txt, L_img, window_frames, frame_tokens), host table) of the last windowed forward
+        self._attn_anchors = None       # (head, tail) anchor frames of the window or None: set_attention_window(anchors=...)
+        self._attn_window_bounds = None # (n_prefix, n_suffix) of the last ANCHORED windowed forward's table
         self.forward = self.forward_ckpt  # instance attribute, as the reference does (model.py:143-146)
 
     # ------------------------------------------------------------------ fp8 mode
@@ -1157,7 +1261,7 @@ class MMDiTModel(_OskState, nn.Module):
         return self
 
     # ------------------------------------------------------------------ frame-window attention
-    def set_attention_window(self, window_frames="env", frame_tokens: int | None = None):
+    def set_attention_window(self, window_frames="env", frame_tokens: int | None = None, anchors="env"):
         """Opt-in frame-window attention, off by default: text keys stay visible to every query, an image query block keeps the
         image keys of its own frames +- window_frames (attention_window_table: a block-granular superset of each row's window) and
         the attention runs osk_attention_fwd_window_bf16 -- in fp8 mode (enable_fp8, either order) osk_attention_fwd_window_fp8_bf16
@@ -1168,18 +1272,31 @@ class MMDiTModel(_OskState, nn.Module):
         sees the text).  Under sequence parallelism (seqpar.enable, either order) the bf16 attention runs it in both exchange modes:
         K and V travel token-major, osk_kv_join_bf16 lays the gathered segments out as one key segment and every rank runs the
         window entry on the table of its own rows (seqpar.SeqPar); refused there: enable_fp8, kv_chunks > 1, the step cache.
+        anchors = (head, tail): the first `head` and the last `tail` latent frames are attended by EVERY query in addition to the
+        text -- the conditioning frames of image-to-video -- through osk_attention_fwd_window_anchor_bf16 in every mode the window
+        runs in (bf16 FAST / general, pv8, qk8; bf16 under sequence parallelism).  The always-attended ends are tile-aligned
+        outward (attention_window_bounds): up to 63 keys of the neighbouring frame join each end where frame_tokens is no multiple
+        of 64.  None or (0, 0): no anchors, the calls from before; without the argument OSK_ATTN_WINDOW_ANCHORS ("h,t"; unset: none)
+        decides.  Anchors that leave no windowed keys are refused when a forward sees the geometry (that is the full attention).
         The setting is not part of state_dict."""
         if isinstance(window_frames, str) and window_frames == "env":
             window_frames = _window_env_default()
+        if isinstance(anchors, str) and anchors == "env":
+            anchors = os.environ.get("OSK_ATTN_WINDOW_ANCHORS", "")
         if window_frames is None:
             self._attn_window = None
+            self._attn_anchors = None
             return self
+        anchors = parse_window_anchors(anchors, "set_attention_window: anchors")
+        if anchors is not None and not _window_anchor_ok():
+            raise ValueError("set_attention_window: this kernel table has no anchored entry (attention_fwd_window_anchor)")
         if int(window_frames) < 0 or frame_tokens is None or int(frame_tokens) <= 0:
             raise ValueError(f"set_attention_window: window_frames >= 0 and frame_tokens > 0 expected; got {window_frames}, {frame_tokens}")
         if any(getattr(b, "_osk_fp8", False) for b in list(self.double_blocks) + list(self.single_blocks)) and not _window_fp8_ok():
             raise ValueError("set_attention_window: frame-window attention has no fp8 kernels; call enable_fp8(False) first")
         self._sp_window_check(getattr(self, "_sp", None), "set_attention_window")
         self._attn_window = (int(window_frames), int(frame_tokens))
+        self._attn_anchors = anchors
         return self
 
     def _sp_window_check(self, sp, who: str) -> None:
@@ -1205,9 +1322,13 @@ class MMDiTModel(_OskState, nn.Module):
         if L_txt % 64:
             raise ValueError(f"frame-window attention needs a text length that is a multiple of 64 (the key prefix of "
                              f"osk_attention_fwd_window_bf16); got L_txt = {L_txt}")
-        key = (L_txt, L_img) + self._attn_window
+        anchors = getattr(self, "_attn_anchors", None)
+        key = (L_txt, L_img) + self._attn_window + (anchors or ())      # (no anchors: the key and the table from before)
         if self._attn_window_table is None or self._attn_window_table[0] != key:
-            self._attn_window_table = (key, attention_window_table(L_txt, L_img, self._attn_window[1], self._attn_window[0]))
+            a, b = anchors or (0, 0)
+            self._attn_window_bounds = None if anchors is None else attention_window_bounds(L_txt, L_img, self._attn_window[1], a, b)
+            self._attn_window_table = (key, attention_window_table(L_txt, L_img, self._attn_window[1], self._attn_window[0],
+                                                                   anchor_head=a, anchor_tail=b))
         return self._attn_window_table[1]
 
     # ------------------------------------------------------------------ planning
@@ -1243,8 +1364,12 @@ class MMDiTModel(_OskState, nn.Module):
         if getattr(self, "_attn_window", None) is not None:
             # visited_tile_fraction: of the last windowed forward's geometry (None before the first one)
             t = self._attn_window_table
+            anchors = getattr(self, "_attn_anchors", None)
+            frac = None if t is None else window_tile_fraction(t[1], t[0][0], t[0][1], self._attn_window_bounds if len(t[0]) > 4 else None)
             window = {"attention_window": {"window_frames": self._attn_window[0], "frame_tokens": self._attn_window[1],
-                                           "visited_tile_fraction": None if t is None else window_tile_fraction(t[1], t[0][0], t[0][1])}}
+                                           "visited_tile_fraction": frac}}
+            if anchors is not None:     # (no anchors: the report from before)
+                window["attention_window"]["anchors"] = anchors
             # "mode": the operand kind of the windowed calls in fp8 mode, "pv8" | "qk8" (osk_attention_fwd_window_fp8_bf16).  bf16
             # attention reports no "mode" key: the entry is the one from before fp8 mode had a window, and so is its report
             mode = _window_mode(any(p.pv8 for p in plans), any(p.qk8 for p in plans), hd)
@@ -1441,7 +1566,10 @@ class MMDiTModel(_OskState, nn.Module):
         # one device: the table of the whole axis for _joint_attention.  Sharded: every rank builds the tables of its own rows
         # (seqpar.SeqPar.window_table) from the geometry -- ws holds this rank's rows, so ws.attn_window stays None there
         ws.attn_window = table if sp is None else None
-        ws.sp_window = None if (sp is None or table is None) else (txt.shape[1], img.shape[1]) + self._attn_window
+        anchors = None if table is None else getattr(self, "_attn_anchors", None)
+        ws.attn_anchor = self._attn_window_bounds if (sp is None and anchors is not None) else None
+        # (the spec carries the anchors only when there are some: without them it is the 4-tuple from before)
+        ws.sp_window = None if (sp is None or table is None) else (txt.shape[1], img.shape[1]) + self._attn_window + (anchors or ())
         p = self._plan
         mod = torch.empty(img.shape[0], p["mod_cols"], dtype=torch.float32, device=img.device)
         _OPS.gemv_tasks(vec, p["mod_tasks"], mod, act_in=1)

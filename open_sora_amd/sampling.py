@@ -136,6 +136,18 @@ def _window_default():
     return int(v) if v else None
 
 
+def cond_anchor_frames(masks: Tensor) -> tuple[int, int]:
+    """attn_window_anchors="cond": (head, tail) = the leading and the trailing latent frames on which `masks` ([B, 1, T, H, W],
+    1 on the conditioning frames: opensora/utils/inference.py:216-351) is 1 for EVERY sample -- i2v_head (1, 0), i2v_tail (0, 1),
+    i2v_loop (1, 1), text-to-video (0, 0).  A run of leading frames that reaches the last frame counts as head only.  One small
+    host read."""
+    on = (masks.reshape(masks.shape[0], masks.shape[1], masks.shape[2], -1) == 1).all(dim=3).all(dim=1).all(dim=0).cpu().tolist()
+    T = len(on)
+    head = next((i for i, v in enumerate(on) if not v), T)
+    tail = next((i for i, v in enumerate(reversed(on)) if not v), T)
+    return head, min(tail, T - head)
+
+
 def _step_cache_default():
     """OSK_STEP_CACHE, read at call time like OSK_CFG_PRUNE: the threshold as a float (unset or empty: off)"""
     v = os.environ.get("OSK_STEP_CACHE", "").strip()
@@ -188,6 +200,9 @@ class I2VDenoiser:
     this loop -- MMDiTModel.set_attention_window(W, frame_tokens) with frame_tokens from masked_ref's h, w and patch_size, also
     under hip_graph and cfg_prune; the model's previous setting is restored afterwards.  Results differ from the reference's
     (every query sees every key) by what the dropped keys carried; output quality on real checkpoints is not measured.
+    `attn_window_anchors=None | (head, tail) | "cond"` (with attn_window_frames; without it: ValueError): latent frames every query
+    keeps attending to -- "cond" takes them from `masks` (cond_anchor_frames: the reference frames the loop conditions on), one
+    small host read before step 0.  Composes with hip_graph, cfg_prune and step_cache as the window does.
 
     `step_cache=threshold` (default: OSK_STEP_CACHE, read at call time; unset = off) with `step_cache_coefficients=None`: opt-in
     step cache of the TeaCache kind.  Every step runs the model's head and measures how far block 0's modulated image input of
@@ -217,6 +232,9 @@ class I2VDenoiser:
         attn_window_frames = kwargs.pop("attn_window_frames", "env")
         if isinstance(attn_window_frames, str) and attn_window_frames == "env":
             attn_window_frames = _window_default()
+        anchors = kwargs.pop("attn_window_anchors", None)
+        if anchors is not None and attn_window_frames is None:
+            raise ValueError("attn_window_anchors needs attn_window_frames: anchor frames belong to frame-window attention")
         step_cache = kwargs.pop("step_cache", "env")
         if isinstance(step_cache, str) and step_cache == "env":
             step_cache = _step_cache_default()
@@ -240,7 +258,12 @@ class I2VDenoiser:
                 raise ValueError("attn_window_frames needs a model with set_attention_window (open_sora_amd.mmdit.MMDiTModel)")
             ps = patch_size
             previous = getattr(model, "_attn_window", None)
-            model.set_attention_window(int(attn_window_frames), (masked_ref.shape[-2] // ps) * (masked_ref.shape[-1] // ps))
+            previous_anchors = getattr(model, "_attn_anchors", None)
+            if isinstance(anchors, str) and anchors == "cond":
+                anchors = cond_anchor_frames(masks)
+            # (no anchors asked for: the call from before, in which the model reads OSK_ATTN_WINDOW_ANCHORS)
+            kw = {} if anchors is None else {"anchors": tuple(anchors)}
+            model.set_attention_window(int(attn_window_frames), (masked_ref.shape[-2] // ps) * (masked_ref.shape[-1] // ps), **kw)
             try:
                 return self.denoise(model, img=img, timesteps=timesteps, guidance=guidance, guidance_img=guidance_img, masks=masks,
                                     masked_ref=masked_ref, text_osci=text_osci, image_osci=image_osci,
@@ -248,7 +271,8 @@ class I2VDenoiser:
                                     cfg_prune=cfg_prune, attn_window_frames=None, step_cache=step_cache,
                                     step_cache_coefficients=coefficients, **kwargs)
             finally:
-                model.set_attention_window(*(previous if previous is not None else (None,)))
+                model.set_attention_window(*(previous if previous is not None else (None,)),
+                                           **({"anchors": previous_anchors} if previous is not None and hasattr(model, "_attn_anchors") else {}))
 
         n3 = img.shape[0]
         n = n3 // 3

@@ -50,6 +50,7 @@ Frame-window attention (MMDiTModel.set_attention_window, opt-in; bf16 attention,
 so K and V travel token-major through the same collectives, osk_kv_join_bf16 lays the gathered segments out as K [B, L, D] and
 V^T [B, H, hd, round_up(L, 64)], and the rank runs osk_attention_fwd_window_bf16 on the table of its own rows -- once per source
 rank in head-exchange mode.  A ragged split is the join's short last segment.  See "frame-window attention" below.
+With anchor frames (set_attention_window(anchors=...)) the spec carries them and the call is osk_attention_fwd_window_anchor_bf16.
 """
 from __future__ import annotations
 
@@ -641,33 +642,40 @@ class SeqPar:
     kv_window = True     # gather_kv_start takes window (mmdit asks before it passes the argument, like kv_qk8)
 
     def window_table(self, spec, row0: int, n_rows: int) -> Tensor:
-        """host table of query rows [row0, row0 + n_rows) for spec = (L_txt, L_img, window_frames, frame_tokens): built once per
-        (geometry, rows, W) and kept; the binding keeps its device copy by content (_C._window_on_device)"""
+        """host table of query rows [row0, row0 + n_rows) for spec = (L_txt, L_img, window_frames, frame_tokens) -- with anchor
+        frames (L_txt, L_img, window_frames, frame_tokens, anchor_head, anchor_tail), the table then over the body keys between
+        the always-attended ends: built once per (geometry, rows, W, anchors) and kept; the binding keeps its device copy by
+        content (_C._window_on_device)"""
         key = (*spec, row0, n_rows)
         tabs = self._win_tables
         t = tabs.get(key)
         if t is None:
             while len(tabs) >= 64:
                 tabs.pop(next(iter(tabs)))
-            L_txt, L_img, W, N = spec
-            t = tabs[key] = mmdit.attention_window_table(L_txt, L_img, N, W, row0=row0, n_rows=n_rows)
+            L_txt, L_img, W, N, *anchors = spec
+            kw = dict(anchor_head=anchors[0], anchor_tail=anchors[1]) if anchors else {}
+            t = tabs[key] = mmdit.attention_window_table(L_txt, L_img, N, W, row0=row0, n_rows=n_rows, **kw)
         return t
 
-    def _window_buffers(self, B: int, Lc: int, Ltail: int, Hl: int, hd: int, Lq: int, device, gather: bool):
+    def _window_buffers(self, B: int, Lc: int, Ltail: int, Hl: int, hd: int, Lq: int, device, gather: bool, anchored: bool = False):
         """per geometry, like the gather buffers: the joined K [B, L, Hl*hd] and V^T [B, Hl, hd, round_up(L, 64)] of the Hl heads this
         rank attends with, the window entry's workspace for calls of B batches of up to Lq rows, and (all-gather mode) the token-major
-        gather buffers of K and V -- P slots of Lc rows; the join never reads the pad rows of a short last slot, so nothing is zeroed"""
+        gather buffers of K and V -- P slots of Lc rows; the join never reads the pad rows of a short last slot, so nothing is zeroed.
+        anchored: the workspace of the anchored entry (two partial sets) instead -- a buffer set of its own per geometry"""
         def make():
             L = (self.P - 1) * Lc + Ltail
+            ops = mmdit.ops()
+            ws_bytes = (ops.attention_window_anchor_workspace_bytes if anchored else ops.attention_window_workspace_bytes)(B, Hl, Lq, hd)
             b = dict(kj=torch.empty(B, L, Hl * hd, dtype=BF16, device=device),
                      vtj=torch.empty(B, Hl, hd, (L + 63) // 64 * 64, dtype=BF16, device=device),
-                     ws=torch.empty(max(mmdit.ops().attention_window_workspace_bytes(B, Hl, Lq, hd), 16), dtype=torch.uint8, device=device))
+                     ws=torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=device))
             if gather:
                 b["k"] = torch.empty(self.P, B, Lc, Hl * hd, dtype=BF16, device=device)
                 b["v"] = torch.empty(self.P, B, Lc, Hl * hd, dtype=BF16, device=device)
             return b
 
-        return self._cached(("window", gather, B, Lc, Ltail, Hl, hd, Lq, str(device), mmdit._stream_key(device)), make)
+        key = ("window", gather, B, Lc, Ltail, Hl, hd, Lq, str(device), mmdit._stream_key(device))
+        return self._cached(key + (("anchored",) if anchored else ()), make)
 
     def _window_kv_start(self, k: Tensor, v: Tensor, H: int, hd: int, pv8: bool, vt_ready: bool, spec):
         if pv8:
@@ -686,7 +694,7 @@ class SeqPar:
             self._to_head_chunks(bufs["vs"], v)
             wv = self.tp.all_to_all(bufs["vr"].view(-1), bufs["vs"].view(-1))
             return "window", "heads", spec, (Lc, Ltail), bufs, wk, wv
-        bufs = self._window_buffers(B, Lc, Ltail, H, hd, Lloc, k.device, True)
+        bufs = self._window_buffers(B, Lc, Ltail, H, hd, Lloc, k.device, True, anchored=len(spec) > 4)
         ops = mmdit.ops()
         ops.copy_rows(k, bufs["k"][self.rank][:, :Lloc])
         wk = self.tp.all_gather(bufs["k"].view(-1), bufs["k"][self.rank].view(-1))
@@ -703,15 +711,22 @@ class SeqPar:
         ops = mmdit.ops()
         bound = score_bound if 0.0 < score_bound <= mmdit.SCORE_BOUND_LIMIT else 0.0
         kw = dict(n_prefix=spec[0], q_prescaled=True, score_bound=bound)
+        attend = ops.attention_fwd_window
+        if len(spec) > 4:
+            # anchor frames: the anchored entry on the joined K / V^T, its always-attended ends from the full sequence's geometry;
+            # nothing differs in the exchange or the join
+            n_prefix, n_suffix = mmdit.attention_window_bounds(spec[0], spec[1], spec[3], spec[4], spec[5])
+            kw = dict(n_prefix=n_prefix, n_suffix=n_suffix, mode="bf16", q_prescaled=True, score_bound=bound)
+            attend = ops.attention_fwd_window_anchor
         if kind == "gather":
             self._timed_wait(wk, "k")
             self._timed_wait(wv, "v")
             ops.kv_join(bufs["k"], bufs["v"], bufs["kj"], bufs["vtj"], H, hd, L)
-            ops.attention_fwd_window(q, bufs["kj"], bufs["vtj"], out, H, hd, hd ** -0.5, workspace=bufs["ws"],
-                                     windows=self.window_table(spec, self.rank * Lc, q.shape[1]), **kw)
+            attend(q, bufs["kj"], bufs["vtj"], out, H, hd, hd ** -0.5, workspace=bufs["ws"],
+                   windows=self.window_table(spec, self.rank * Lc, q.shape[1]), **kw)
             return
         B, Hg = q.shape[0], H // P
-        jb = self._window_buffers(B, Lc, Ltail, Hg, hd, Lc, q.device, False)
+        jb = self._window_buffers(B, Lc, Ltail, Hg, hd, Lc, q.device, False, anchored=len(spec) > 4)
         self._timed_wait(wq[0], "q")
         self._timed_wait(wk, "k")
         self._timed_wait(wv, "v")
@@ -720,8 +735,8 @@ class SeqPar:
         # slot the return all-to-all sends; the calls share the workspace (one stream, in order)
         for p_ in range(P):
             rows = Ltail if p_ == P - 1 else Lc
-            ops.attention_fwd_window(bufs["qr"][p_][:, :rows], jb["kj"], jb["vtj"], bufs["os"][p_][:, :rows], Hg, hd, hd ** -0.5,
-                                     workspace=jb["ws"], windows=self.window_table(spec, p_ * Lc, rows), **kw)
+            attend(bufs["qr"][p_][:, :rows], jb["kj"], jb["vtj"], bufs["os"][p_][:, :rows], Hg, hd, hd ** -0.5,
+                   workspace=jb["ws"], windows=self.window_table(spec, p_ * Lc, rows), **kw)
         self._timed_wait(self.tp.all_to_all(bufs["orr"].view(-1), bufs["os"].view(-1)), "o")
         self._from_head_chunks(out, bufs["orr"])
 

@@ -17,7 +17,12 @@ mode (osk_attention_fwd_pv8_bf16 / osk_attention_fwd_qk8_bf16 with the tail-spli
 alone on prepared operands and ("+pack") with the scale kernels, the V^T pack and in qk8 mode the K pack in front of it, which
 touch every key whatever the window.
 
-    python tools/attn_window_time.py [--mode bf16|pv8|qk8] [--repeats 7] [--out profiles/attn_window_time.jsonl]
+--anchors h,t (bf16 mode): anchor frames (osk_attention_fwd_window_anchor_bf16).  Per shape, at W in {1, 2} (headline) / {2} (long),
+three alternating arms -- the full call, the un-anchored window call of that W, the anchored call -- and, on the same rows, the
+one-pass three-part merge (osk_attention_merge_into2_bf16) against two passes of osk_attention_merge_into_bf16.  The anchored arm's
+ratios are printed against both other arms.  No threshold is set; output quality is not measured.
+
+    python tools/attn_window_time.py [--mode bf16|pv8|qk8] [--anchors h,t] [--repeats 7] [--out profiles/attn_window_time.jsonl]
 """
 from __future__ import annotations
 
@@ -55,6 +60,62 @@ def time_arms(arms, warmup, repeats, inner):
             e1.synchronize()
             ms[n_].append(e0.elapsed_time(e1) / inner)
     return ms
+
+
+ANCHOR_WINDOWS = {"headline": (1, 2), "long": (2,)}
+
+
+def time_anchors(a, s, _C, mmdit, dev, emit):
+    """--anchors: full / window / anchored window as alternating arms, and the one-pass merge against two two-part passes"""
+    head, tail = (int(x) for x in a.anchors.split(","))
+    B, H, hd, Lt, N, T = s["B"], s["H"], s["hd"], s["L_txt"], s["N"], s["T"]
+    L = Lt + N * T
+    g = torch.Generator(device=dev).manual_seed(7)
+    k = torch.randn(B, L, H * hd, device=dev, generator=g).to(torch.bfloat16)
+    v = torch.randn(B, L, H * hd, device=dev, generator=g).to(torch.bfloat16)
+    q = torch.randn(B, L, H * hd, device=dev, generator=g)
+    kn = k.float().reshape(B, L, H, hd).norm(dim=-1).max()
+    q = (q * (40.0 / float(q.reshape(B, L, H, hd).norm(dim=-1).max() * kn))).to(torch.bfloat16)   # prescaled, |q||k| <= ~40 < 56
+    bound = float(q.float().reshape(B, L, H, hd).norm(dim=-1).max() * kn) * 1.01
+    vt = torch.zeros(B, H, hd, (L + 63) // 64 * 64, dtype=torch.bfloat16, device=dev)
+    _C.v_transpose(v, vt, H, hd)
+    out = torch.empty_like(q)
+    ws_full = _C.attention_workspace(dev)
+    ws_win = _C.attention_window_workspace(B, H, L, hd, dev)
+    ws_anc = _C.attention_window_anchor_workspace(B, H, L, hd, dev)
+    n_prefix, n_suffix = mmdit.attention_window_bounds(Lt, N * T, N, head, tail)
+    arms = {"full": lambda: _C.attention_fwd(q, k, vt, out, H, hd, hd ** -0.5, q_prescaled=True, workspace=ws_full, score_bound=bound)}
+    fracs = {"full": 1.0}
+    for w in ANCHOR_WINDOWS.get(s["name"], s["windows"][:1]):
+        t = mmdit.attention_window_table(Lt, N * T, N, w)
+        ta = mmdit.attention_window_table(Lt, N * T, N, w, anchor_head=head, anchor_tail=tail)
+        arms[f"W{w}"] = (lambda t=t: _C.attention_fwd_window(q, k, vt, out, H, hd, hd ** -0.5, n_prefix=Lt, windows=t, q_prescaled=True,
+                                                             score_bound=bound, workspace=ws_win))
+        arms[f"W{w}a"] = (lambda ta=ta: _C.attention_fwd_window_anchor(q, k, vt, out, H, hd, hd ** -0.5, n_prefix=n_prefix, n_suffix=n_suffix,
+                                                                       windows=ta, q_prescaled=True, score_bound=bound, workspace=ws_anc))
+        fracs[f"W{w}"] = mmdit.window_tile_fraction(t, Lt, N * T)
+        fracs[f"W{w}a"] = mmdit.window_tile_fraction(ta, Lt, N * T, (n_prefix, n_suffix))
+    # the merge alone, on rows of this shape: one three-part pass against two two-part passes (values do not matter to the time)
+    Lqp = (L + 255) // 256 * 256
+    lse = torch.zeros(B, H, L, device=dev)
+    ob, oc = torch.zeros(B, H, Lqp, hd, device=dev), torch.zeros(B, H, Lqp, hd, device=dev)
+    lb, lc = torch.zeros(B, H, Lqp, device=dev), torch.zeros(B, H, Lqp, device=dev)
+    arms["merge_2x_into"] = lambda: (_C.attention_merge_into(out, lse, ob, lb, H, hd), _C.attention_merge_into(out, lse, oc, lc, H, hd))
+    arms["merge_into2"] = lambda: _C.attention_merge_into2(out, lse, ob, lb, oc, lc, H, hd)
+    ms = time_arms(arms, a.warmup, a.repeats, s["inner"])
+    med = {n_: statistics.median(x) for n_, x in ms.items()}
+    for n_ in arms:
+        row = dict(what="attn_window_anchor_time", shape=s["name"], B=B, H=H, hd=hd, L_txt=Lt, frame_tokens=N, frames=T, anchors=[head, tail],
+                   n_prefix=n_prefix, n_suffix=n_suffix, arm=n_, repeats=a.repeats, calls_per_timing=s["inner"], ms=[round(x, 4) for x in ms[n_]],
+                   median_ms=round(med[n_], 4), spread_ms=round(max(ms[n_]) - min(ms[n_]), 4), score_bound=round(bound, 3))
+        if n_.startswith("merge"):
+            row["time_ratio_to_two_passes"] = round(med[n_] / med["merge_2x_into"], 4)
+        else:
+            row["tile_fraction"] = round(fracs[n_], 4)
+            row["time_ratio_to_full"] = round(med[n_] / med["full"], 4)
+            if n_.endswith("a"):
+                row["time_ratio_to_window"] = round(med[n_] / med[n_[:-1]], 4)
+        emit(row)
 
 
 def time_fp8(a, s, _C, mmdit, dev, emit):
@@ -115,6 +176,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--shapes", default=None, help="comma list; default: every shape of the mode")
     ap.add_argument("--mode", default="bf16", choices=("bf16", "pv8", "qk8"))
+    ap.add_argument("--anchors", default=None, help="h,t: anchor frames (bf16 mode): anchored against un-anchored and full, merge A/B")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert a.repeats >= 3, "at least 3 rounds of every arm"
@@ -136,7 +198,11 @@ def main():
         if a.shapes and s["name"] not in a.shapes.split(","):
             continue
         if a.mode != "bf16":
+            assert a.anchors is None, "--anchors is timed in bf16 mode"
             time_fp8(a, s, _C, mmdit, dev, emit)
+            continue
+        if a.anchors:
+            time_anchors(a, s, _C, mmdit, dev, emit)
             continue
         B, H, hd, Lt, N, T = s["B"], s["H"], s["hd"], s["L_txt"], s["N"], s["T"]
         L = Lt + N * T
