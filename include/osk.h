@@ -238,6 +238,44 @@ int osk_kv_join_bf16(const void* k_seg, const void* v_seg,
                      void* vt_out,
                      int B, int H, int hd, int n_seg, int seg_len, int L, void* stream);
 
+/* ---- the e4m3 counterparts of the join, for frame-window attention under sequence parallelism in fp8 mode (additive entries, the
+ * version stays 2).  The operands the fp8 kernels consume as e4m3 travel as e4m3, token-major, at one byte per element; the join
+ * lays the gathered segments out as the operands of one key segment.  Nothing in the reference corresponds to either.
+ *
+ * osk_kv_quant_rows_fp8: x bf16 [B, L, H*hd] view (batch / row strides in elements, multiples of 8; 16-byte aligned pointer; last
+ *   dim contiguous), scales f32 [B, H] -> out, e4m3 bytes [B, L, H*hd] token-major with batch / row strides of its own in BYTES (a
+ *   rank's slot of a gather buffer): out[b, l, h*hd + d] = e4m3(clamp(x[b, l, h*hd + d] / scales[b, h], -448, 448)) -- the IEEE f32
+ *   division, the clamp and the v_cvt_pk_fp8_f32 rounding of osk_k_pack_fp8 / osk_v_transpose_fp8, so every byte is the one those
+ *   calls produce for the same element and scale.  hd 128: 16-byte stores (out 16-byte aligned, its strides multiples of 16);
+ *   hd 72: a head of 72 bytes is no multiple of 16, so 8-byte stores (out 8-byte aligned, its strides multiples of 8).  Any other
+ *   hd: OSK_EUNSUPPORTED.  OSK_EINVAL: a NULL pointer, a pointer or stride off the alignment above, B, H or L <= 0 (or B, H > 65535).
+ *
+ * osk_kv_join_fp8: the gathered segments (key j < L in segment s = j / seg_len, row r = j % seg_len; (n_seg - 1)*seg_len < L <=
+ *   n_seg*seg_len; the rows of a short last segment behind key L - 1 are never read) -> the operands of one key segment of L keys:
+ *   v_seg: e4m3 bytes at v_seg + s*v_seg_stride + b*v_batch_stride + r*v_row_stride + h*hd (bytes; hd 128: multiples of 16 and a
+ *     16-byte aligned pointer, hd 72: multiples of 8 and an 8-byte aligned pointer) -> vt8_out [B, H, vt8_rows(hd), round_up(L, 64)],
+ *     bit for bit what osk_v_transpose_fp8 writes for the contiguous V of the same keys with the scales the bytes were quantised
+ *     with: the key order inside each 64-key tile, the ones / key-validity row (0x38 for keys < L, 0 behind them), the zero rows.
+ *   k_kind OSK_KV_JOIN_K_E4M3 (hd 128 only, else OSK_EUNSUPPORTED): k_seg e4m3 bytes, strides in bytes (multiples of 16) ->
+ *     k_out = k8 [B, H, round_up(L, 64), 128] contiguous, bit for bit what osk_k_pack_fp8 writes: rows L .. Lp-1 repeat row L-1.
+ *     ko_batch_stride / ko_row_stride are not used.
+ *   k_kind OSK_KV_JOIN_K_BF16 (K stays bf16: pv8): k_seg bf16, strides in elements (multiples of 8) -> k_out the [B, L, H*hd] bf16
+ *     view of osk_kv_join_bf16 (ko strides in elements, multiples of 8).
+ *   k_seg, k_out and vt8_out 16-byte aligned.  The argument checks are those of osk_kv_join_bf16 (OSK_EINVAL; a k_kind other than
+ *   the two: OSK_EINVAL); hd in {72, 128}, else OSK_EUNSUPPORTED.  A refused call launches nothing.
+ * Every byte of the outputs, key padding included, is written by the launch: nothing relies on a zeroed buffer.  No allocation, no
+ * memset, no atomics on global memory, no host synchronisation: both are capturable in a hipGraph. */
+#define OSK_KV_JOIN_K_BF16 0
+#define OSK_KV_JOIN_K_E4M3 1
+int osk_kv_quant_rows_fp8(const void* x, int64_t batch_stride, int64_t row_stride, const float* scales,
+                          void* out, int64_t o_batch_stride, int64_t o_row_stride,      /* bytes */
+                          int B, int L, int H, int hd, void* stream);
+int osk_kv_join_fp8(const void* k_seg, int64_t k_seg_stride, int64_t k_batch_stride, int64_t k_row_stride, int k_kind,
+                    const void* v_seg, int64_t v_seg_stride, int64_t v_batch_stride, int64_t v_row_stride,
+                    void* k_out, int64_t ko_batch_stride, int64_t ko_row_stride,
+                    void* vt8_out,
+                    int B, int H, int hd, int n_seg, int seg_len, int L, void* stream);
+
 /* ---- flash attention forward, non-causal: out = softmax(q k^T * scale) v, bf16 I/O, f32 softmax.
  * replaces flash_attn_func (math.py:16-19,33) and _flash_attn_forward with LSE
  * (distributed.py:148-161).

@@ -46,6 +46,8 @@ SIGNATURES = {
                              _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp],
     "osk_v_transpose_bf16": [_vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _vp],
     "osk_kv_join_bf16": [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
+    "osk_kv_quant_rows_fp8": [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp],
+    "osk_kv_join_fp8": [_vp, _i64, _i64, _i64, _i32, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "osk_attention_fwd_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp,
                                _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _vp],
     "osk_attention_fwd_ws_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp,
@@ -985,6 +987,52 @@ def k_pack_fp8(k: torch.Tensor, scales: torch.Tensor, k8: torch.Tensor, H: int, 
     _check(lib.osk_k_pack_fp8(k.data_ptr(), k.stride(0), k.stride(1), scales.data_ptr(), k8.data_ptr(), B, L, H, hd, _stream()),
            "osk_k_pack_fp8")
     return k8
+
+
+def kv_quant_rows_fp8(x: torch.Tensor, scales: torch.Tensor, out: torch.Tensor, H: int, hd: int) -> torch.Tensor:
+    """x bf16 [B, L, H*hd] view, scales f32 [B, H] -> out uint8 [B, L, H*hd] view (its own batch / row strides: a slot of a gather
+    buffer): the e4m3 bytes of x / scale, token-major, each byte the one k_pack_fp8 / v_transpose_fp8 produce for that element
+    (osk_kv_quant_rows_fp8).  head_dim 72 / 128."""
+    assert x.dim() == 3 and out.dim() == 3, (x.shape, out.shape)
+    B, L, C_ = x.shape
+    al = 16 if hd == 128 else 8
+    assert x.dtype == torch.bfloat16 and C_ == H * hd and hd in (72, 128), (x.dtype, x.shape, H, hd)
+    assert x.stride(2) == 1 and x.stride(0) % 8 == 0 and x.stride(1) % 8 == 0 and x.data_ptr() % 16 == 0, (x.stride(), x.data_ptr() % 16)
+    assert out.dtype == torch.uint8 and tuple(out.shape) == (B, L, C_) and out.device == x.device, (out.dtype, out.shape)
+    assert out.stride(2) == 1 and out.stride(0) % al == 0 and out.stride(1) % al == 0 and out.data_ptr() % al == 0, (out.stride(), out.data_ptr() % al)
+    assert scales.dtype == torch.float32 and scales.is_contiguous() and scales.numel() == B * H, (scales.dtype, scales.shape)
+    _check(lib.osk_kv_quant_rows_fp8(x.data_ptr(), x.stride(0), x.stride(1), scales.data_ptr(), out.data_ptr(), out.stride(0),
+                                     out.stride(1), B, L, H, hd, _stream()), "osk_kv_quant_rows_fp8")
+    return out
+
+
+def kv_join_fp8(k_seg: torch.Tensor, v_seg: torch.Tensor, k_out: torch.Tensor, vt8_out: torch.Tensor, H: int, hd: int, L: int):
+    """the gathered segments [n_seg, B, seg_len, H*hd] (key j in segment j // seg_len, row j % seg_len; (n_seg - 1) * seg_len < L <=
+    n_seg * seg_len) -> the fp8 operands of one key segment of L keys (osk_kv_join_fp8): v_seg uint8 (kv_quant_rows_fp8 bytes) ->
+    vt8_out uint8 [B, H, vt8_rows(hd), round_up(L, 64)], bit for bit v_transpose_fp8 of the L keys as one contiguous V; k_seg uint8
+    (head_dim 128) -> k_out = k8 uint8 [B, H, round_up(L, 64), 128], bit for bit k_pack_fp8; k_seg bf16 -> k_out the bf16 [B, L, H*hd]
+    view kv_join writes.  The K kind is k_seg's dtype."""
+    n_seg, B, seg_len, D = v_seg.shape
+    k8 = k_seg.dtype == torch.uint8
+    al = 16 if hd == 128 else 8
+    assert hd in (72, 128) and D == H * hd and (hd == 128 or not k8), (D, H, hd, k_seg.dtype)
+    assert v_seg.dtype == torch.uint8 and v_seg.stride(3) == 1 and all(s % al == 0 for s in v_seg.stride()[:3]) and v_seg.data_ptr() % al == 0, (v_seg.dtype, v_seg.stride())
+    assert k_seg.dtype in (torch.uint8, torch.bfloat16) and tuple(k_seg.shape) == (n_seg, B, seg_len, D) and k_seg.stride(3) == 1, (k_seg.dtype, k_seg.shape)
+    assert all(s % (16 if k8 else 8) == 0 for s in k_seg.stride()[:3]) and k_seg.data_ptr() % 16 == 0, k_seg.stride()
+    Lp = (L + 63) // 64 * 64
+    if k8:
+        assert k_out.dtype == torch.uint8 and tuple(k_out.shape) == k8_shape(B, H, L, hd) and k_out.is_contiguous(), (k_out.dtype, k_out.shape)
+        kobs = kors = 0
+    else:
+        assert k_out.dtype == torch.bfloat16 and tuple(k_out.shape) == (B, L, D) and k_out.stride(2) == 1, (k_out.dtype, k_out.shape, k_out.stride())
+        assert k_out.stride(0) % 8 == 0 and k_out.stride(1) % 8 == 0, k_out.stride()
+        kobs, kors = k_out.stride(0), k_out.stride(1)
+    assert k_out.data_ptr() % 16 == 0 and vt8_out.data_ptr() % 16 == 0
+    assert vt8_out.dtype == torch.uint8 and tuple(vt8_out.shape) == (B, H, vt8_rows(hd), Lp) and vt8_out.is_contiguous(), (vt8_out.dtype, vt8_out.shape)
+    assert (n_seg - 1) * seg_len < L <= n_seg * seg_len, (n_seg, seg_len, L)
+    _check(lib.osk_kv_join_fp8(k_seg.data_ptr(), k_seg.stride(0), k_seg.stride(1), k_seg.stride(2), int(k8), v_seg.data_ptr(),
+                               v_seg.stride(0), v_seg.stride(1), v_seg.stride(2), k_out.data_ptr(), kobs, kors, vt8_out.data_ptr(),
+                               B, H, hd, n_seg, seg_len, L, _stream()), "osk_kv_join_fp8")
 
 
 def attention_fwd_qk8(q: torch.Tensor, k8: torch.Tensor, k_scale: torch.Tensor, vt8: torch.Tensor, v_scale: torch.Tensor,

@@ -827,6 +827,13 @@ def _window_fp8_ok() -> bool:
     return hasattr(_OPS, "attention_fwd_window_fp8")
 
 
+def _sp_window_fp8_ok(sp) -> bool:
+    """can fp8 mode run frame-window attention under this sp object?  The kernel table needs the e4m3 join and the row quantisation
+    (looked up like _window_fp8_ok: a substituted table from before them keeps its refusal) and the sp object has to take the
+    window together with pv8 / qk8 (seqpar.SeqPar.kv_window_fp8, asked like kv_qk8 and kv_window)"""
+    return hasattr(_OPS, "kv_join_fp8") and hasattr(_OPS, "kv_quant_rows_fp8") and bool(getattr(sp, "kv_window_fp8", False))
+
+
 def _window_mode(pv8: bool, qk8: bool, hd: int) -> str:
     """operand kind of a windowed attention call: what the unwindowed path picks for the same plan and head dim"""
     if not (pv8 and hd in (72, 128)):
@@ -1249,11 +1256,17 @@ class MMDiTModel(_OskState, nn.Module):
         one max-reduction over a [2, B, H] buffer (K's and V's, osk_kv_scale_fp8) makes equal on every rank; in head-exchange mode
         K is packed after the all-to-all, with no collective.  Recommended for head_dim 128: the attention launch takes
         0.77 - 0.79 of the pv8 time with the K pack counted (A/B spread under 2 %) at the same model-level error; DESIGN.md
-        section 4, profiles/attn_qk8.md, profiles/attn_qk8_sp.md (a rank's launch at the sharded shape)."""
+        section 4, profiles/attn_qk8.md, profiles/attn_qk8_sp.md (a rank's launch at the sharded shape).
+        With frame-window attention on (set_attention_window, either order) the attention is the fp8 window entry in the same
+        mode, under sequence parallelism too (the e4m3 exchange and join of seqpar.SeqPar._window_kv_start; profiles/sp_window.md);
+        ValueError only for a substituted kernel table without the fp8 window / join entries or an sp object of the caller's own
+        without kv_window_fp8."""
         if on and getattr(self, "_attn_window", None) is not None and not _window_fp8_ok():
             raise ValueError("enable_fp8: frame-window attention (set_attention_window) has no fp8 kernels; turn it off first")
-        if on and getattr(self, "_attn_window", None) is not None and getattr(self, "_sp", None) is not None:
-            raise ValueError("enable_fp8: frame-window attention under sequence parallelism has no fp8 path; set_attention_window(None) first")
+        sp = getattr(self, "_sp", None)
+        if on and getattr(self, "_attn_window", None) is not None and sp is not None and not _sp_window_fp8_ok(sp):
+            raise ValueError("enable_fp8: frame-window attention under sequence parallelism has no fp8 path with this kernel table / sp "
+                             "object (kv_join_fp8, kv_quant_rows_fp8, seqpar.SeqPar.kv_window_fp8); set_attention_window(None) first")
         for b in list(self.double_blocks) + list(self.single_blocks):
             object.__setattr__(b, "_osk_fp8", bool(on))
             object.__setattr__(b, "_osk_qk8", bool(on and qk8))
@@ -1269,12 +1282,15 @@ class MMDiTModel(_OskState, nn.Module):
         None turns it off; without the argument the environment's OSK_ATTN_WINDOW_FRAMES decides (unset: off).  Exact with respect
         to the mask it states; the reference attends to every key, so outputs DIFFER from it by what the dropped keys carried, and
         the quality of that on real checkpoints is not measured.  L_txt % 64 == 0 (checked when a forward
-        sees the text).  Under sequence parallelism (seqpar.enable, either order) the bf16 attention runs it in both exchange modes:
-        K and V travel token-major, osk_kv_join_bf16 lays the gathered segments out as one key segment and every rank runs the
-        window entry on the table of its own rows (seqpar.SeqPar); refused there: enable_fp8, kv_chunks > 1, the step cache.
+        sees the text).  Under sequence parallelism (seqpar.enable, either order) it runs in both exchange modes: K and V travel
+        token-major, osk_kv_join_bf16 lays the gathered segments out as one key segment and every rank runs the window entry on
+        the table of its own rows (seqpar.SeqPar).  In fp8 mode there (enable_fp8, either order; pv8 and qk8) the operands the
+        kernels consume as e4m3 travel as e4m3 -- osk_kv_quant_rows_fp8 on the sender's side with the scales of the unwindowed fp8
+        exchange -- and osk_kv_join_fp8 writes the e4m3 V^T and K of the whole key axis for osk_attention_fwd_window_fp8_bf16.
+        Refused under sequence parallelism: kv_chunks > 1, the step cache.
         anchors = (head, tail): the first `head` and the last `tail` latent frames are attended by EVERY query in addition to the
         text -- the conditioning frames of image-to-video -- through osk_attention_fwd_window_anchor_bf16 in every mode the window
-        runs in (bf16 FAST / general, pv8, qk8; bf16 under sequence parallelism).  The always-attended ends are tile-aligned
+        runs in (bf16 FAST / general, pv8, qk8; all three under sequence parallelism).  The always-attended ends are tile-aligned
         outward (attention_window_bounds): up to 63 keys of the neighbouring frame join each end where frame_tokens is no multiple
         of 64.  None or (0, 0): no anchors, the calls from before; without the argument OSK_ATTN_WINDOW_ANCHORS ("h,t"; unset: none)
         decides.  Anchors that leave no windowed keys are refused when a forward sees the geometry (that is the full attention).
@@ -1300,15 +1316,17 @@ class MMDiTModel(_OskState, nn.Module):
         return self
 
     def _sp_window_check(self, sp, who: str) -> None:
-        """what frame-window attention under sequence parallelism still refuses (sp: the model's seqpar object or None)"""
+        """what frame-window attention under sequence parallelism still refuses (sp: the model's seqpar object or None); fp8 mode
+        only where the kernel table or the sp object lacks the fp8 join path (_sp_window_fp8_ok)"""
         if sp is None:
             return
         if not getattr(sp, "kv_window", False):    # (guarded like kv_qk8: a caller's own sp object from before the window path)
             raise ValueError(f"{who}: frame-window attention does not run under sequence parallelism with this sp object "
                              f"(seqpar.SeqPar.kv_window)")
-        if any(getattr(b, "_osk_fp8", False) for b in list(self.double_blocks) + list(self.single_blocks)):
-            raise ValueError(f"{who}: frame-window attention under sequence parallelism has no fp8 path (the packed e4m3 K gathers per "
-                             f"segment and needs a join of its own); call enable_fp8(False) or set_attention_window(None)")
+        if any(getattr(b, "_osk_fp8", False) for b in list(self.double_blocks) + list(self.single_blocks)) and not _sp_window_fp8_ok(sp):
+            raise ValueError(f"{who}: frame-window attention under sequence parallelism has no fp8 path with this kernel table / sp object "
+                             f"(the e4m3 operands need a join of their own: kv_join_fp8, kv_quant_rows_fp8, seqpar.SeqPar.kv_window_fp8); "
+                             f"call enable_fp8(False) or set_attention_window(None)")
         if getattr(sp, "kv_chunks", 1) > 1:
             raise ValueError(f"{who}: frame-window attention under sequence parallelism takes one gather; kv_chunks = {sp.kv_chunks} "
                              f"is refused (seqpar.enable(kv_chunks=1))")

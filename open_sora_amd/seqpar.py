@@ -46,11 +46,17 @@ only its Ltail rows -- so the collectives do not change; token-wise work runs on
 Lc keys and one of Ltail, which the kernels take as two launches and an in-place merge (osk_attention_fwd_ragged_bf16, bf16 / pv8 / qk8);
 the gathered prediction [P, B, Lc, C] is cut to L rows.  P | L never takes that path.  kv_chunks is ignored on a ragged split.
 
-Frame-window attention (MMDiTModel.set_attention_window, opt-in; bf16 attention, both modes): the window entry takes one key segment,
+Frame-window attention (MMDiTModel.set_attention_window, opt-in; both modes; bf16 here, fp8 mode below): the window entry takes one key segment,
 so K and V travel token-major through the same collectives, osk_kv_join_bf16 lays the gathered segments out as K [B, L, D] and
 V^T [B, H, hd, round_up(L, 64)], and the rank runs osk_attention_fwd_window_bf16 on the table of its own rows -- once per source
 rank in head-exchange mode.  A ragged split is the join's short last segment.  See "frame-window attention" below.
 With anchor frames (set_attention_window(anchors=...)) the spec carries them and the call is osk_attention_fwd_window_anchor_bf16.
+In fp8 mode (enable_fp8: pv8, and qk8 at head_dim 128) what the kernels consume as e4m3 travels as e4m3, token-major: with the scales
+of the unwindowed fp8 exchange (all-gather mode: one reducing collective per block) osk_kv_quant_rows_fp8 writes the rank's rows into
+its slot of a byte gather buffer -- V always, K under qk8; under pv8 K travels bf16 -- and osk_kv_join_fp8 lays the gathered segments
+out as vt8 [B, H, vt8_rows(hd), round_up(L, 64)] and k8 [B, H, round_up(L, 64), 128] (pv8: the bf16 K), bit for bit what
+osk_v_transpose_fp8 / osk_k_pack_fp8 write for the contiguous tensors; then osk_attention_fwd_window_fp8_bf16 (or the anchored entry)
+in that mode.  Head-exchange mode sends bf16 as without a window and quantises what it received, its scales without a collective.
 """
 from __future__ import annotations
 
@@ -379,7 +385,7 @@ class SeqPar:
         pv8 = pv8 and hd in (72, 128)
         qk8 = qk8 and pv8 and hd == 128
         if window is not None:     # frame-window attention (mmdit passes the argument only with the window on)
-            return self._window_kv_start(k, v, H, hd, pv8, vt_ready, window)
+            return self._window_kv_start(k, v, H, hd, pv8, vt_ready, window, qk8)
         if self.head_parallel(H):
             return self._heads_kv_start(k, v, H, hd, pv8, qk8)
         B, Lloc, _ = k.shape
@@ -632,13 +638,14 @@ class SeqPar:
         self._timed_wait(self.tp.all_to_all(bufs["orr"].view(-1), bufs["os"].view(-1)), "o")
         self._from_head_chunks(out, bufs["orr"])
 
-    # ------------------------------------------------------------------ frame-window attention (bf16, both exchange modes)
+    # ------------------------------------------------------------------ frame-window attention (bf16 and fp8 mode, both exchange modes)
     # osk_attention_fwd_window_bf16 takes ONE key segment with the text prefix at keys [0, L_txt); the exchange buffers are
     # segment-major with segments that are no multiple of 64 keys.  K and V therefore travel token-major through the same collectives
     # (V instead of V^T: the same bytes), osk_kv_join_bf16 turns the gathered segments into K [B, L, D] and V^T [B, H, hd,
     # round_up(L, 64)] in one HBM-bound launch, and the window entry runs on the table of the query rows in hand (row0 = the owning
     # rank's first row): once in all-gather mode, once per source rank in head-exchange mode.  A ragged split is the join's short last
-    # segment: the ragged two-launch entry is not used here.  No attention kernel and no generated loop differs for it.
+    # segment: the ragged two-launch entry is not used here.  No attention kernel and no generated loop differs for it.  fp8 mode:
+    # _window_kv_start / _window_attention_fp8 -- the e4m3 operands travel as bytes, osk_kv_join_fp8 is the join.
     kv_window = True     # gather_kv_start takes window (mmdit asks before it passes the argument, like kv_qk8)
 
     def window_table(self, spec, row0: int, n_rows: int) -> Tensor:
@@ -677,9 +684,43 @@ class SeqPar:
         key = ("window", gather, B, Lc, Ltail, Hl, hd, Lq, str(device), mmdit._stream_key(device))
         return self._cached(key + (("anchored",) if anchored else ()), make)
 
-    def _window_kv_start(self, k: Tensor, v: Tensor, H: int, hd: int, pv8: bool, vt_ready: bool, spec):
-        if pv8:
-            raise ValueError("frame-window attention under sequence parallelism has no fp8 path: enable_fp8(False) or set_attention_window(None)")
+    def _window_buffers8(self, B: int, Lc: int, Ltail: int, Hl: int, hd: int, Lq: int, device, gather: bool, fmode: str, anchored: bool = False):
+        """_window_buffers in fp8 mode (fmode "pv8" | "qk8"): the joined e4m3 V^T [B, Hl, vt8_rows(hd), round_up(L, 64)] and K -- k8
+        [B, Hl, round_up(L, 64), 128] under qk8, else the bf16 [B, L, Hl*hd] -- the window entry's workspace, and the token-major
+        byte buffers the join reads: all-gather mode the gather buffers (V as e4m3; K as e4m3 under qk8, else bf16) and under qk8
+        the [2, B, Hl] scale buffer of the block's one reducing collective; head-exchange mode the quantised received chunks.  The
+        join writes every byte of its outputs and never reads the pad rows of a short last slot: nothing is zeroed."""
+        def make():
+            L = (self.P - 1) * Lc + Ltail
+            ops = mmdit.ops()
+            U8 = torch.uint8
+            qk8 = fmode == "qk8"
+            ws_bytes = (ops.attention_window_anchor_workspace_bytes if anchored else ops.attention_window_workspace_bytes)(B, Hl, Lq, hd)
+            seg = lambda dt: torch.empty(self.P, B, Lc, Hl * hd, dtype=dt, device=device)
+            b = dict(kj=torch.empty(ops.k8_shape(B, Hl, L, hd), dtype=U8, device=device) if qk8 else torch.empty(B, L, Hl * hd, dtype=BF16, device=device),
+                     vtj=torch.empty(B, Hl, ops.vt8_rows(hd), (L + 63) // 64 * 64, dtype=U8, device=device),
+                     ws=torch.empty(max(ws_bytes, 16), dtype=U8, device=device), v=seg(U8))
+            if gather or qk8:        # (head-exchange mode under pv8: K is joined from the received bf16 chunks)
+                b["k"] = seg(U8 if qk8 else BF16)
+            if gather and qk8:
+                b["s2"] = torch.empty(2, B, Hl, dtype=torch.float32, device=device)
+            return b
+
+        key = ("window8", fmode, gather, B, Lc, Ltail, Hl, hd, Lq, str(device), mmdit._stream_key(device))
+        return self._cached(key + (("anchored",) if anchored else ()), make)
+
+    kv_window_fp8 = True   # gather_kv_start takes window together with pv8 / qk8 (mmdit asks before it lets fp8 mode through)
+
+    def _window_kv_start(self, k: Tensor, v: Tensor, H: int, hd: int, pv8: bool, vt_ready: bool, spec, qk8: bool = False):
+        """fp8 mode (pv8; qk8 at head_dim 128): what the kernels consume as e4m3 travels as e4m3 -- token-major, quantised by
+        osk_kv_quant_rows_fp8 straight into this rank's slot with the scales of the unwindowed fp8 exchange (one reducing collective
+        per block) -- and osk_kv_join_fp8 lays the gathered segments out.  Head-exchange mode sends bf16 as ever (_heads_kv_start)
+        and quantises what it received.  The handle's fourth element carries (Lc, Ltail, mode, k_scale, v_scale)."""
+        ops = mmdit.ops()
+        if pv8 and not (hasattr(ops, "kv_join_fp8") and hasattr(ops, "kv_quant_rows_fp8")):
+            raise ValueError("frame-window attention under sequence parallelism: this kernel table has no fp8 join (kv_join_fp8 / "
+                             "kv_quant_rows_fp8): enable_fp8(False) or set_attention_window(None)")
+        fmode = "qk8" if qk8 else "pv8" if pv8 else "bf16"
         if self.kv_chunks > 1:
             raise ValueError(f"frame-window attention under sequence parallelism takes one gather: kv_chunks = {self.kv_chunks} is refused")
         assert not vt_ready, "local_vt() is not asked for with the window on: the projection writes V token-major"
@@ -693,22 +734,46 @@ class SeqPar:
             wk = self.tp.all_to_all(bufs["kr"].view(-1), bufs["ks"].view(-1))
             self._to_head_chunks(bufs["vs"], v)
             wv = self.tp.all_to_all(bufs["vr"].view(-1), bufs["vs"].view(-1))
-            return "window", "heads", spec, (Lc, Ltail), bufs, wk, wv
+            return "window", "heads", spec, (Lc, Ltail, fmode, None, None), bufs, wk, wv
+        r = self.rank
+        if fmode != "bf16":
+            bufs = self._window_buffers8(B, Lc, Ltail, H, hd, Lloc, k.device, True, fmode, anchored=len(spec) > 4)
+            own = lambda t: t[r][:, :Lloc]
+            if qk8:
+                # (the co-residency rule of gather_kv_start's qk8 branch: the block's only REDUCING collective, both quantisations
+                #  need its result, so the compute stream runs nothing under it)
+                s2 = bufs["s2"]
+                ops.kv_scale_fp8(k, v, H, hd, out=s2)
+                self._timed_wait(self.tp.all_reduce_max(s2), "kvmax")
+                k_scale, v_scale = s2[0], s2[1]
+                ops.kv_quant_rows_fp8(k, k_scale, own(bufs["k"]), H, hd)
+                wk = self.tp.all_gather(bufs["k"].view(-1), bufs["k"][r].view(-1))
+            else:
+                # (as gather_kv_start's pv8 branch: until the wait() the compute stream runs the K copy only)
+                k_scale, v_scale = None, mmdit.v_scale_fp8(v, H, hd)
+                wmax = self.tp.all_reduce_max(v_scale)
+                ops.copy_rows(k, own(bufs["k"]))
+                wk = self.tp.all_gather(bufs["k"].view(-1), bufs["k"][r].view(-1))
+                self._timed_wait(wmax, "vmax")
+            ops.kv_quant_rows_fp8(v, v_scale, own(bufs["v"]), H, hd)
+            wv = self.tp.all_gather(bufs["v"].view(-1), bufs["v"][r].view(-1))
+            return "window", "gather", spec, (Lc, Ltail, fmode, k_scale, v_scale), bufs, wk, wv
         bufs = self._window_buffers(B, Lc, Ltail, H, hd, Lloc, k.device, True, anchored=len(spec) > 4)
-        ops = mmdit.ops()
-        ops.copy_rows(k, bufs["k"][self.rank][:, :Lloc])
-        wk = self.tp.all_gather(bufs["k"].view(-1), bufs["k"][self.rank].view(-1))
-        ops.copy_rows(v, bufs["v"][self.rank][:, :Lloc])
-        wv = self.tp.all_gather(bufs["v"].view(-1), bufs["v"][self.rank].view(-1))
-        return "window", "gather", spec, (Lc, Ltail), bufs, wk, wv
+        ops.copy_rows(k, bufs["k"][r][:, :Lloc])
+        wk = self.tp.all_gather(bufs["k"].view(-1), bufs["k"][r].view(-1))
+        ops.copy_rows(v, bufs["v"][r][:, :Lloc])
+        wv = self.tp.all_gather(bufs["v"].view(-1), bufs["v"][r].view(-1))
+        return "window", "gather", spec, (Lc, Ltail, fmode, None, None), bufs, wk, wv
 
     def _window_attention(self, pending, q: Tensor, out: Tensor, H: int, hd: int, score_bound: float):
         """join, then the window entry: FAST body where the block's bound admits it, else the general one (the rule of
         mmdit._joint_attention's window path)"""
         pending = self.q_exchange_start(pending, q, H, hd)     # (head-exchange mode, a caller that did not start it earlier)
-        _, kind, spec, (Lc, Ltail), bufs, wk, wv, *wq = pending
+        _, kind, spec, (Lc, Ltail, fmode, k_scale, v_scale), bufs, wk, wv, *wq = pending
         P, L = self.P, (self.P - 1) * Lc + Ltail
         ops = mmdit.ops()
+        if fmode != "bf16":
+            return self._window_attention_fp8(pending, q, out, H, hd)
         bound = score_bound if 0.0 < score_bound <= mmdit.SCORE_BOUND_LIMIT else 0.0
         kw = dict(n_prefix=spec[0], q_prescaled=True, score_bound=bound)
         attend = ops.attention_fwd_window
@@ -737,6 +802,55 @@ class SeqPar:
             rows = Ltail if p_ == P - 1 else Lc
             attend(bufs["qr"][p_][:, :rows], jb["kj"], jb["vtj"], bufs["os"][p_][:, :rows], Hg, hd, hd ** -0.5,
                    workspace=jb["ws"], windows=self.window_table(spec, p_ * Lc, rows), **kw)
+        self._timed_wait(self.tp.all_to_all(bufs["orr"].view(-1), bufs["os"].view(-1)), "o")
+        self._from_head_chunks(out, bufs["orr"])
+
+    def _window_attention_fp8(self, pending, q: Tensor, out: Tensor, H: int, hd: int):
+        """_window_attention in fp8 mode: one osk_kv_join_fp8, then the fp8 window entry (the anchored entry with anchors set) in
+        mode "pv8" | "qk8" with Lk = L and the scales every rank agrees on.  Head-exchange mode: the scales of the received chunks
+        with no collective, as _heads_attention takes them (the zero pad rows of a ragged split move no maximum), the chunks
+        quantised token-major, then the join and one call per source rank."""
+        _, kind, spec, (Lc, Ltail, fmode, k_scale, v_scale), bufs, wk, wv, *wq = pending
+        P, L = self.P, (self.P - 1) * Lc + Ltail
+        ops = mmdit.ops()
+        anchored = len(spec) > 4
+        if anchored:
+            n_prefix, n_suffix = mmdit.attention_window_bounds(spec[0], spec[1], spec[3], spec[4], spec[5])
+
+        def attend(q_, jb, k_sc, v_sc, out_, Hl, table):
+            if anchored:
+                return ops.attention_fwd_window_anchor(q_, jb["kj"], jb["vtj"], out_, Hl, hd, hd ** -0.5, n_prefix=n_prefix, n_suffix=n_suffix,
+                                                       windows=table, mode=fmode, k_scale=k_sc, v_scale=v_sc, q_prescaled=True,
+                                                       workspace=jb["ws"], Lk=L)
+            return ops.attention_fwd_window_fp8(q_, jb["kj"], k_sc, jb["vtj"], v_sc, out_, Hl, hd, hd ** -0.5, n_prefix=spec[0], windows=table,
+                                                mode=fmode, q_prescaled=True, workspace=jb["ws"], Lk=L)
+
+        if kind == "gather":
+            self._timed_wait(wk, "k")
+            self._timed_wait(wv, "v")
+            ops.kv_join_fp8(bufs["k"], bufs["v"], bufs["kj"], bufs["vtj"], H, hd, L)
+            attend(q, bufs, k_scale, v_scale, out, H, self.window_table(spec, self.rank * Lc, q.shape[1]))
+            return
+        B, Hg = q.shape[0], H // P
+        Dg = Hg * hd
+        jb = self._window_buffers8(B, Lc, Ltail, Hg, hd, Lc, q.device, False, fmode, anchored=anchored)
+        self._timed_wait(wq[0], "q")
+        self._timed_wait(wk, "k")
+        self._timed_wait(wv, "v")
+        kr3, vr3 = bufs["kr"].view(P * B, Lc, Dg), bufs["vr"].view(P * B, Lc, Dg)
+        k_seg = bufs["kr"]
+        if fmode == "qk8":
+            s2 = ops.kv_scale_fp8(kr3, vr3, Hg, hd).view(2, P, B, Hg).amax(1).contiguous()                     # [2, B, Hg]
+            k_scale, v_scale = s2[0], s2[1]
+            ops.kv_quant_rows_fp8(kr3, k_scale.repeat(P, 1).contiguous(), jb["k"].view(P * B, Lc, Dg), Hg, hd)
+            k_seg = jb["k"]
+        else:
+            v_scale = ops.v_scale_fp8(vr3, Hg, hd).view(P, B, Hg).amax(0).contiguous()                        # [B, Hg]
+        ops.kv_quant_rows_fp8(vr3, v_scale.repeat(P, 1).contiguous(), jb["v"].view(P * B, Lc, Dg), Hg, hd)
+        ops.kv_join_fp8(k_seg, jb["v"], jb["kj"], jb["vtj"], Hg, hd, L)
+        for p_ in range(P):
+            rows = Ltail if p_ == P - 1 else Lc
+            attend(bufs["qr"][p_][:, :rows], jb, k_scale, v_scale, bufs["os"][p_][:, :rows], Hg, self.window_table(spec, p_ * Lc, rows))
         self._timed_wait(self.tp.all_to_all(bufs["orr"].view(-1), bufs["os"].view(-1)), "o")
         self._from_head_chunks(out, bufs["orr"])
 
