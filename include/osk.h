@@ -679,6 +679,15 @@ int64_t osk_step_delta_workspace_bytes(int B, int L, int C);
 int osk_step_delta_bf16(const void* cur, int64_t cur_batch_stride, int64_t cur_row_stride, void* prev, float* sums, int B, int L, int C,
                         void* workspace, int64_t workspace_bytes, void* stream);
 
+/* The step cache under sequence parallelism (open_sora_amd/mmdit.py, MMDiTModel.step_head on a sharded model).  Additive under ABI
+ * version 2.  Every rank's osk_step_delta_bf16 gives the pair of its own rows; after one all-gather every rank holds
+ * pairs f32 [P, 2] (slot r: rank r's (sum |cur - prev|, sum |prev|)).  This entry adds them in rank order 0 .. P-1 with plain f32
+ * adds on one lane:  sums[j] = ((pairs[0][j] + pairs[1][j]) + ...) + pairs[P-1][j], at most P - 1 roundings; NaN and infinity
+ * propagate.  Equal gathered bits give equal sums on every rank, which is the whole synchronisation of the decision.  pairs and sums
+ * 4-byte aligned, P >= 1; a NULL pointer, P < 1 or a misaligned pointer is OSK_EINVAL with nothing launched.  sums must not
+ * overlap pairs.  No allocation, memset or synchronisation: capturable. */
+int osk_step_sums_combine_f32(const float* pairs, int P, float* sums, void* stream);
+
 /* Residual store and apply over strided bf16 [B, L, C] views (strides multiples of 8, unit channel stride, 16-byte aligned,
  * C % 8 == 0):  out = bf16(f32(a) - f32(b))  /  out = bf16(f32(a) + f32(b)), the exact difference / sum rounded once.  out may be a
  * or b (same strides) -- the sampler stores R = Y - X over the X it saved, and applies Y = X + R over X. */

@@ -88,6 +88,7 @@ SIGNATURES = {
     "osk_copy_rows_bf16": [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp],
     "osk_step_delta_workspace_bytes": [_i32, _i32, _i32],
     "osk_step_delta_bf16": [_vp, _i64, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp],
+    "osk_step_sums_combine_f32": [_vp, _i32, _vp, _vp],
     "osk_residual_sub_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp],
     "osk_residual_add_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp],
     "osk_causal_conv3d_ndhwc_bf16": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32,
@@ -1164,6 +1165,21 @@ def step_delta(cur: torch.Tensor, prev: torch.Tensor, sums: torch.Tensor, worksp
         raise ValueError(f"{what}: cur and prev overlap")
     _check(lib.osk_step_delta_bf16(cur.data_ptr(), cur.stride(0), cur.stride(1), prev.data_ptr(), sums.data_ptr(), B, L, Cc,
                                    workspace.data_ptr(), workspace.numel(), _stream()), what)
+    return sums
+
+
+def step_sums_combine(pairs: torch.Tensor, sums: torch.Tensor) -> torch.Tensor:
+    """sums f32 [2] = the P rows of pairs f32 [P, 2] added in row order with plain f32 adds on one lane: osk_step_sums_combine_f32.
+    The ranks of a sharded step cache each hold the same gathered pairs, so they get the same bits.  Deterministic, capturable."""
+    what = "osk_step_sums_combine_f32"
+    if not (torch.is_tensor(pairs) and pairs.is_cuda and pairs.dtype == torch.float32 and pairs.ndim == 2 and pairs.shape[0] >= 1
+            and pairs.shape[1] == 2 and pairs.is_contiguous()):
+        raise ValueError(f"{what}: pairs must be a contiguous f32 [P, 2] tensor on the GPU with P >= 1")
+    if not (torch.is_tensor(sums) and sums.is_cuda and sums.dtype == torch.float32 and sums.numel() == 2 and sums.is_contiguous()):
+        raise ValueError(f"{what}: sums must be a contiguous f32 [2] tensor on the GPU")
+    if sums.data_ptr() < pairs.data_ptr() + 4 * pairs.numel() and pairs.data_ptr() < sums.data_ptr() + 8:
+        raise ValueError(f"{what}: sums and pairs overlap")
+    _check(lib.osk_step_sums_combine_f32(pairs.data_ptr(), pairs.shape[0], sums.data_ptr(), _stream()), what)
     return sums
 
 

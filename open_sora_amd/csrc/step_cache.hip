@@ -110,6 +110,30 @@ extern "C" int osk_step_delta_bf16(const void* cur, int64_t cur_batch_stride, in
 }
 
 // =============================================================================================
+// Sums combine (the step cache under sequence parallelism): every rank's osk_step_delta_bf16 gives the pair of its own rows; the P
+// pairs, gathered as f32 [P, 2], are added in rank order 0 .. P-1 by ONE lane with plain f32 adds: sums[0] = ((p[0][0] + p[1][0]) +
+// ...) + p[P-1][0], sums[1] likewise.  Every rank holds the same gathered bits and runs the same P - 1 adds, so the sums -- and the
+// decision the host takes from them -- are equal bit for bit on all ranks.  A NaN or an infinity in any pair reaches the sum.
+// =============================================================================================
+__global__ void __launch_bounds__(64) step_sums_combine_kernel(const float* __restrict__ pairs, int P, float* __restrict__ sums) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  float num = pairs[0], den = pairs[1];
+  for (int r = 1; r < P; ++r) {
+    num += pairs[2 * r];
+    den += pairs[2 * r + 1];
+  }
+  sums[0] = num;
+  sums[1] = den;
+}
+
+extern "C" int osk_step_sums_combine_f32(const float* pairs, int P, float* sums, void* stream) {
+  if (!pairs || !sums || P < 1) return OSK_EINVAL;
+  if (((uintptr_t)pairs & 3) || ((uintptr_t)sums & 3)) return OSK_EINVAL;
+  hipLaunchKernelGGL(step_sums_combine_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, pairs, P, sums);
+  return (int)hipGetLastError();
+}
+
+// =============================================================================================
 // Residual store / apply: out = bf16(f32(a) - f32(b)) or bf16(f32(a) + f32(b)) over strided bf16 [B, L, C] views.  The f32 sum of
 // two bf16 values is exact unless their exponents are 16 or more apart, and then the smaller one is far below half a bf16 step of
 // the larger: the result is the exact sum rounded once.  out may be a or b themselves (same strides): a lane reads its 8

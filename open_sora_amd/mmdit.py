@@ -594,13 +594,18 @@ class _StepState:
 
 class _StepCache:
     """buffers of the sampler's step cache (MMDiTModel.step_cache_begin): prev = M_{i-1}[:n] bf16 [n, L_img, D], res = R bf16
-    [rows, L_img, D], sums f32 [2], the delta kernel's partials; have[row]: does the row hold a residual (host)"""
+    [rows, L_img, D], sums f32 [2], the delta kernel's partials; have[row]: does the row hold a residual (host).
+    Under sequence parallelism (shard = (lo, hi), this rank's rows of the joint sequence; ranks = P) L_img is the rank's OWN image
+    rows -- prev and res are 1 / P of the single-device buffers -- and pairs f32 [P, 2] holds every rank's pair of sums: slot
+    `rank` is written by this rank's delta kernel, the others arrive by one all-gather, osk_step_sums_combine_f32 adds them into
+    sums.  shard None: one device (or a declined split), no pairs."""
 
-    def __init__(self, key, n, rows, L_img, D, device):
-        self.key, self.n, self.rows, self.L_img = key, n, rows, L_img
+    def __init__(self, key, n, rows, L_img, D, device, shard=None, ranks=1):
+        self.key, self.n, self.rows, self.L_img, self.shard = key, n, rows, L_img, shard
         self.prev = torch.zeros(n, L_img, D, dtype=BF16, device=device)
         self.res = torch.empty(rows, L_img, D, dtype=BF16, device=device)
         self.sums = torch.zeros(2, dtype=torch.float32, device=device)
+        self.pairs = None if shard is None else torch.zeros(ranks, 2, dtype=torch.float32, device=device)
         self.partials = torch.empty(max(_OPS.step_delta_workspace_bytes(n, L_img, D), 8), dtype=torch.uint8, device=device)
         self.have = [False] * rows
 
@@ -1287,7 +1292,7 @@ class MMDiTModel(_OskState, nn.Module):
         the table of its own rows (seqpar.SeqPar).  In fp8 mode there (enable_fp8, either order; pv8 and qk8) the operands the
         kernels consume as e4m3 travel as e4m3 -- osk_kv_quant_rows_fp8 on the sender's side with the scales of the unwindowed fp8
         exchange -- and osk_kv_join_fp8 writes the e4m3 V^T and K of the whole key axis for osk_attention_fwd_window_fp8_bf16.
-        Refused under sequence parallelism: kv_chunks > 1, the step cache.
+        Refused under sequence parallelism: kv_chunks > 1, the step cache (the step cache alone runs sharded; the three together do not).
         anchors = (head, tail): the first `head` and the last `tail` latent frames are attended by EVERY query in addition to the
         text -- the conditioning frames of image-to-video -- through osk_attention_fwd_window_anchor_bf16 in every mode the window
         runs in (bf16 FAST / general, pv8, qk8; all three under sequence parallelism).  The always-attended ends are tile-aligned
@@ -1621,21 +1626,49 @@ class MMDiTModel(_OskState, nn.Module):
         return out.to(st.dtype) if st.dtype != BF16 else out
 
     # ------------------------------------------------------------------ step cache (driven by sampling.I2VDenoiser)
-    def step_cache_begin(self, n: int, rows: int, L_img: int, device) -> "_StepCache":
+    def _sp_step_cache_check(self, refusal: str):
+        """the model's seqpar object when the step cache may run sharded, None on one device.  Refused: an sp object that does not
+        declare the capability (seqpar.SeqPar.step_cache; guarded like kv_qk8 -- `refusal` is the caller's message from before the
+        sharded cache), and the triple frame-window attention + sequence parallelism + step cache, which no test or measurement
+        covers (each pair of the three runs)."""
+        sp = getattr(self, "_sp", None)
+        if sp is None:
+            return None
+        if not getattr(sp, "step_cache", False):
+            raise ValueError(refusal)
+        if getattr(self, "_attn_window", None) is not None:
+            raise ValueError("step_cache: frame-window attention, sequence parallelism and the step cache do not run together (any two "
+                             "of them do); call set_attention_window(None), run without seqpar.enable or leave step_cache off")
+        return sp
+
+    def step_cache_begin(self, n: int, rows: int, L_img: int, device, L_txt: int | None = None) -> "_StepCache":
         """The buffers of one step-cached sampling loop of `n` samples whose steps run up to `rows` batch rows of L_img image tokens:
         M_{i-1}[:n], the residual R of every row, the two sums and the delta kernel's partials.  They belong to the loop's
         geometry, not to one batch size -- the three batch sizes of a pruned loop share them -- and are kept, like the activation
         workspaces, per (geometry, device, stream): the last loop's set is reused, another geometry replaces it.  Which rows hold
-        a residual starts empty on every call."""
-        if getattr(self, "_sp", None) is not None:
-            raise ValueError("step_cache: a model under sequence parallelism is out of scope for the step cache (every rank would "
-                             "need the same distance); run it without seqpar.enable or leave step_cache off")
+        a residual starts empty on every call.
+        Under sequence parallelism (seqpar.enable; L_txt, the text length of the loop, is then required) the buffers are sharded:
+        this rank's rows of the joint sequence come from the split the forward itself makes (SeqPar.shard_range), prev and res hold
+        the rank's own image rows only -- 1 / P of the single-device cache per rank -- and the rank's row range and the rank count
+        are part of the key.  A geometry whose split is declined gets the single-device set.  Refused: an sp object without
+        SeqPar.step_cache, and a frame window on a sharded model."""
+        sp = self._sp_step_cache_check("step_cache: a model under sequence parallelism is out of scope for the step cache (every rank would "
+                                       "need the same distance); run it without seqpar.enable or leave step_cache off")
         if len(self.double_blocks) == 0:
             raise ValueError("step_cache: the distance is taken at double block 0's image stream; this model has no double block")
         key = (n, rows, L_img, self.hidden_size, str(device), _stream_key(device), id(_OPS))
+        shard, L_loc = None, L_img
+        if sp is not None:
+            if L_txt is None:
+                raise ValueError("step_cache: a model under sequence parallelism needs L_txt to find this rank's rows")
+            shard = sp.shard_range(L_txt + L_img, L_txt)      # None: the split is declined, every rank runs the whole step
+        if shard is not None:
+            lo, hi = shard
+            L_loc = (hi - lo) - (min(hi, L_txt) - min(lo, L_txt))      # the rank's rows minus its text rows (rank 0 holds all of those)
+            key += (lo, hi, sp.P)
         sc = getattr(self, "_osk_step_cache", None)
         if sc is None or sc.key != key:
-            sc = _StepCache(key, n, rows, L_img, self.hidden_size, device)
+            sc = _StepCache(key, n, rows, L_loc, self.hidden_size, device, shard, 1 if shard is None else sp.P)
             object.__setattr__(self, "_osk_step_cache", sc)
         sc.have = [False] * rows
         return sc
@@ -1644,22 +1677,39 @@ class MMDiTModel(_OskState, nn.Module):
                   cond: Tensor = None, guidance: Tensor | None = None, **kwargs) -> "_StepState":
         """The head of a step plus its distance: the forward's own head, then block 0's image-stream LN + modulate of the n
         conditional rows (M_i[:n], into the slot block 0 itself writes it to a moment later) and osk_step_delta_bf16 against the
-        previous step's, which it also replaces.  sc.sums then holds the two sums in stream order; nothing is read back here."""
-        if getattr(self, "_sp", None) is not None:
-            raise ValueError("step_cache: a model under sequence parallelism is out of scope for the step cache")
-        st = self._forward_head(None, None, img, img_ids, txt, txt_ids, timesteps, y_vec, cond, guidance)
-        ws, D, Lt = st.ws, self.hidden_size, st.ws.L_txt
+        previous step's, which it also replaces.  sc.sums then holds the two sums in stream order; nothing is read back here.
+        Under sequence parallelism the head is forward_ckpt's sharded head (the same shard_range decision; a declined split runs
+        the single-device step) and all of the above runs over this rank's own image rows: the delta kernel writes the rank's pair
+        into slot `rank` of sc.pairs, one all-gather of 8 bytes per rank (SeqPar.gather_step_sums) fills the other slots, and
+        osk_step_sums_combine_f32 adds the P pairs in rank order into sc.sums -- the same bits on every rank, so step_distance
+        and the decision taken from it are the same everywhere without any broadcast."""
+        sp = self._sp_step_cache_check("step_cache: a model under sequence parallelism is out of scope for the step cache")
+        shard = None
+        if sp is not None:
+            shard = sp.shard_range(txt.shape[1] + img.shape[1], txt.shape[1])
+            if shard is None:
+                sp = None
+        if shard != sc.shard:
+            raise ValueError(f"step_head: this step's rows {shard} of the joint sequence are not the step cache's {sc.shard}")
+        st = self._forward_head(sp, shard, img, img_ids, txt, txt_ids, timesteps, y_vec, cond, guidance)
+        ws, D, Lt = st.ws, self.hidden_size, st.ws.L_txt            # (sharded: ws holds this rank's rows, Lt its text rows)
         if ws.L_img != sc.L_img or st.B > sc.rows or st.B < sc.n:
             raise ValueError(f"step_head: {st.B} rows of {ws.L_img} image tokens do not fit the step cache of {sc.n} samples, {sc.rows} rows of {sc.L_img}")
         (sh1, sc1), mbs = _mod_views(st.mod, st.plan["col_double"][0][0], 2, D)
         m_cur = ws.xm[:sc.n, Lt:]
         _OPS.ln_modulate(ws.x[:sc.n, Lt:], sh1, sc1, m_cur, mbs)
-        _OPS.step_delta(m_cur, sc.prev, sc.sums, sc.partials)
+        if sp is None:
+            _OPS.step_delta(m_cur, sc.prev, sc.sums, sc.partials)
+        else:
+            _OPS.step_delta(m_cur, sc.prev, sc.pairs[sp.rank], sc.partials)
+            sp.gather_step_sums(sc.pairs)
+            _OPS.step_sums_combine(sc.pairs, sc.sums)
         return st
 
     def step_run(self, sc: "_StepCache", st: "_StepState") -> Tensor:
         """a computed step: X_i of the rows it runs is saved, the blocks run, R[row] = bf16(f32(Y) - f32(X_i)) replaces the saved
-        rows; the other rows keep their older residual"""
+        rows; the other rows keep their older residual.  Sharded: the same over this rank's image rows; the blocks and the tail
+        get the sp object the head carried, so the tail gathers the prediction as the uncached forward does"""
         ws, m = st.ws, st.B
         x_img, r = ws.x[:, ws.L_txt:], sc.res[:m]
         _OPS.copy_rows(x_img, r)
@@ -1669,7 +1719,8 @@ class MMDiTModel(_OskState, nn.Module):
         return self._forward_tail(st)
 
     def step_skip(self, sc: "_StepCache", st: "_StepState") -> Tensor:
-        """a skipped step: Y = bf16(f32(X_i) + f32(R[rows])) in place of the block stack, then the final layer; no block is launched"""
+        """a skipped step: Y = bf16(f32(X_i) + f32(R[rows])) in place of the block stack, then the final layer; no block is launched
+        (sharded: over this rank's image rows; the one exchange left in the step is the tail's gather of the prediction)"""
         ws, m = st.ws, st.B
         if not all(sc.have[:m]):
             raise ValueError(f"step_skip: rows {[r for r in range(m) if not sc.have[r]]} hold no residual yet")

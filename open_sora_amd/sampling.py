@@ -209,9 +209,15 @@ class I2VDenoiser:
     the conditional rows moved since the previous step (relative L1, osk_step_delta_bf16); while the accumulated, polynomial-
     rescaled movement stays under the threshold (step_cache_decide) the block stack is skipped and the last computed residual
     of each row is added to the embedded latents instead (DESIGN.md section 4 states the rule).  Works with cfg_prune (residuals
-    are kept per row of the triple) and attn_window_frames; refused with hip_graph, under sequence parallelism and for models
-    without the head / blocks / tail split.  One 8-byte read back per step.  `last_step_cache` holds (d, acc, computed) per step
-    of the last run (None when off).  No calibrated polynomial ships (default: the identity), and neither the skip rate nor the
+    are kept per row of the triple) and attn_window_frames; refused with hip_graph and for models without the head / blocks /
+    tail split.  One 8-byte read back per step.  `last_step_cache` holds (d, acc, computed) per step of the last run (None when
+    off).  Under sequence parallelism (seqpar.enable) every rank measures the distance over its own image rows, the P pairs of
+    sums travel in one 8-byte all-gather per step and are added in rank order on every rank (osk_step_sums_combine_f32): the
+    same bits, hence the same decisions and the same `last_step_cache` on all ranks, with no broadcast; the cache's buffers are
+    cut to the rank's rows (1 / P of the memory per rank).  All exchange modes, ragged splits, kv_chunks, fp8 / qk8 and cfg_prune
+    are accepted; still refused there: a frame window together with the step cache, and an sp object without SeqPar.step_cache.
+    The exchange of the sums on a multi-GPU node is not measured.
+    No calibrated polynomial ships (default: the identity), and neither the skip rate nor the
     output quality on real checkpoints is measured: a skipped step's result DIFFERS from the reference's."""
 
     def denoise(self, model, **kwargs) -> Tensor:
@@ -247,10 +253,14 @@ class I2VDenoiser:
             if not all(hasattr(model, a) for a in ("step_cache_begin", "step_head", "step_run", "step_skip", "step_distance")):
                 raise ValueError("step_cache needs a model with the head / blocks / tail split (open_sora_amd.mmdit.MMDiTModel); "
                                  f"{type(model).__name__} has none")
-            if getattr(model, "_sp", None) is not None:
+            sp = getattr(model, "_sp", None)
+            if sp is not None and not getattr(sp, "step_cache", False):      # (an sp object from before the sharded step cache)
                 raise ValueError("step_cache does not run under sequence parallelism (every rank would have to take the same decision)")
             if hip_graph:
                 raise ValueError("step_cache and hip_graph=True do not combine: the decision sits on the host between the head and the blocks")
+            if sp is not None and (attn_window_frames is not None or getattr(model, "_attn_window", None) is not None):
+                raise ValueError("step_cache: frame-window attention, sequence parallelism and the step cache do not run together (any two "
+                                 "of them do); leave attn_window_frames off, run without seqpar.enable or leave step_cache off")
         if attn_window_frames is not None:
             # opt-in frame-window attention for this loop (MMDiTModel.set_attention_window): a latent frame is (h / patch) * (w / patch)
             # tokens of the packed sequence; the model's previous setting comes back afterwards, whatever the loop does
@@ -418,7 +428,10 @@ class I2VDenoiser:
         their order are those of the loop it stands for, so a run that computes every step gives that loop's bits."""
         n = x.shape[0]
         n_steps = len(timesteps) - 1
-        sc = model.step_cache_begin(n, max(counts, default=3) * n, img3.shape[1], dev)
+        # (a sharded model cuts the buffers to its rank's rows and needs the text length for that; every rank then measures its share
+        # of the distance and all of them read the same combined sums, so the decisions below are the same on every rank)
+        sharded = {} if getattr(model, "_sp", None) is None else {"L_txt": kwargs["txt"].shape[1]}
+        sc = model.step_cache_begin(n, max(counts, default=3) * n, img3.shape[1], dev, **sharded)
         inputs = {}    # branch count -> the model's keyword arguments for it (views made once, as in _loop_pruned)
         acc = 0.0
         for i, (t_curr, t_prev) in enumerate(zip(timesteps[:-1], timesteps[1:])):

@@ -854,6 +854,15 @@ class SeqPar:
         self._timed_wait(self.tp.all_to_all(bufs["orr"].view(-1), bufs["os"].view(-1)), "o")
         self._from_head_chunks(out, bufs["orr"])
 
+    # ------------------------------------------------------------------ step cache
+    step_cache = True    # gather_step_sums exists (mmdit._sp_step_cache_check asks before it lets the step cache run sharded, like kv_qk8)
+
+    def gather_step_sums(self, pairs: Tensor) -> None:
+        """pairs f32 [P, 2]: slot `rank` holds this rank's (sum |M_i - M_{i-1}|, sum |M_{i-1}|) in stream order; on return (stream
+        order) every slot holds its rank's pair -- one all-gather of 8 bytes per rank, the step cache's only exchange of its own.
+        Every rank then holds the same bits; osk_step_sums_combine_f32 adds them in rank order (MMDiTModel.step_head)."""
+        self._timed_wait(self.tp.all_gather(pairs.view(-1), pairs[self.rank].view(-1)), "sums")
+
     # ------------------------------------------------------------------ output
     def gather_output(self, ws, project, C_out: int, L_txt: int) -> Tensor:
         """project(dst) writes this rank's [B, L/P, C_out] rows; returns the full image prediction
