@@ -698,6 +698,20 @@ int osk_residual_add_bf16(const void* a, int64_t a_batch_stride, int64_t a_row_s
                           int64_t b_row_stride, void* out, int64_t out_batch_stride, int64_t out_row_stride, int B, int L, int C,
                           void* stream);
 
+/* ---- attention broadcast of the sampler (not in the reference; open_sora_amd/sampling.py, I2VDenoiser.denoise(attn_broadcast=...)).
+ * Additive under ABI version 2.  The store and the load of one block's attention output: a copy of bf16 [B, L, C] between two
+ * strided views (element strides, multiples of 8; unit channel stride; 16-byte aligned; C % 8 == 0; B L C / 8 < 2^31), one of which
+ * is a cache slot of `cache_rows` batch rows:
+ *   to_cache != 0 (store):  dst[row_map[b], l, 0:C] = src[b, l, 0:C]         dst is the slot
+ *   to_cache == 0 (load):   dst[b, l, 0:C]          = src[row_map[b], l, 0:C]  src is the slot
+ * row_map: int32 [B] on the DEVICE (a captured graph replays it), distinct entries, or NULL for the identity (then B <= cache_rows).
+ * A batch item whose map entry lies outside [0, cache_rows) is skipped, nothing read or written.  The two views must not overlap.
+ * Anything else (a NULL view, a stride that lets batch items overlap, ...) is OSK_EINVAL with nothing launched.  No allocation,
+ * memset or synchronisation: capturable. */
+int osk_attn_cache_copy_bf16(const void* src, int64_t src_batch_stride, int64_t src_row_stride, void* dst, int64_t dst_batch_stride,
+                             int64_t dst_row_stride, const int32_t* row_map, int cache_rows, int to_cache, int B, int L, int C,
+                             void* stream);
+
 /* =====================================================================================================
  * Causal 3-D VAE (HunyuanVideo VAE, /root/reference/opensora/models/hunyuan_vae).  Activations are channels-last
  * NDHWC bf16 ([B, T, H, W, C] contiguous); the NCTHW <-> NDHWC conversion happens once at the module boundary.

@@ -91,6 +91,7 @@ SIGNATURES = {
     "osk_step_sums_combine_f32": [_vp, _i32, _vp, _vp],
     "osk_residual_sub_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp],
     "osk_residual_add_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp],
+    "osk_attn_cache_copy_bf16": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "osk_causal_conv3d_ndhwc_bf16": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32,
                                      _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp],
     "osk_causal_conv3d_gn_ndhwc_bf16": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32,
@@ -1205,6 +1206,40 @@ def residual_sub(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor) -> torch.T
 def residual_add(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     """out = bf16(f32(a) + f32(b)) over bf16 [B, L, C] views, one rounding; out may be a or b"""
     return _residual(lib.osk_residual_add_bf16, "osk_residual_add_bf16", a, b, out)
+
+
+# ----------------------------------------------------------------------------------------------
+# attention broadcast of the sampler (csrc/attn_cache.hip)
+# ----------------------------------------------------------------------------------------------
+def attn_cache_copy(src: torch.Tensor, dst: torch.Tensor, row_map: torch.Tensor | None, to_cache: bool) -> torch.Tensor:
+    """osk_attn_cache_copy_bf16 over bf16 [., L, C] views.  to_cache (store): src [B, L, C] is the step's attention output, dst the
+    cache slot [cache_rows, L, C], dst[row_map[b]] = src[b].  Otherwise (load): src is the slot, dst [B, L, C], dst[b] =
+    src[row_map[b]].  row_map: int32 [B] on the device with distinct entries in [0, cache_rows), or None for the identity.  The
+    map is read on the device (a captured graph replays it); its values are the caller's to get right -- an entry outside the
+    slot makes the kernel skip that batch item.  Capturable."""
+    what = "osk_attn_cache_copy_bf16"
+    _step_view(src, "src", what)
+    _step_view(dst, "dst", what)
+    step, slot = (src, dst) if to_cache else (dst, src)
+    B, L, Cc = step.shape
+    if slot.shape[1:] != step.shape[1:]:
+        raise ValueError(f"{what}: the slot {tuple(slot.shape)} and the step's view {tuple(step.shape)} differ in L or C")
+    if row_map is None:
+        if B > slot.shape[0]:
+            raise ValueError(f"{what}: {B} batch items do not fit a slot of {slot.shape[0]} rows")
+    elif not (torch.is_tensor(row_map) and row_map.is_cuda and row_map.dtype == torch.int32 and row_map.ndim == 1 and row_map.numel() == B
+              and row_map.is_contiguous()):
+        raise ValueError(f"{what}: row_map must be a contiguous int32 [{B}] tensor on the GPU (or None)")
+    for t, name in ((src, "src"), (dst, "dst")):
+        if t.shape[0] > 1 and t.stride(0) < L * t.stride(1) or t.stride(1) < Cc:
+            raise ValueError(f"{what}: {name}'s rows or batch items overlap (strides {t.stride()})")
+    ext = lambda t: (t.data_ptr(), t.data_ptr() + 2 * ((t.shape[0] - 1) * t.stride(0) + (L - 1) * t.stride(1) + Cc))
+    (s0, s1), (d0, d1) = ext(src), ext(dst)
+    if s0 < d1 and d0 < s1:
+        raise ValueError(f"{what}: src and dst overlap")
+    _check(lib.osk_attn_cache_copy_bf16(src.data_ptr(), src.stride(0), src.stride(1), dst.data_ptr(), dst.stride(0), dst.stride(1),
+                                        _p(row_map), slot.shape[0], 1 if to_cache else 0, B, L, Cc, _stream()), what)
+    return dst
 
 
 # ----------------------------------------------------------------------------------------------

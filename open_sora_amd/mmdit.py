@@ -590,6 +590,7 @@ class _StepState:
     L_txt: int
     dtype: torch.dtype
     device: object
+    shard: object = None    # (lo, hi): this rank's rows of the joint sequence under sequence parallelism
 
 
 class _StepCache:
@@ -608,6 +609,67 @@ class _StepCache:
         self.pairs = None if shard is None else torch.zeros(ranks, 2, dtype=torch.float32, device=device)
         self.partials = torch.empty(max(_OPS.step_delta_workspace_bytes(n, L_img, D), 8), dtype=torch.uint8, device=device)
         self.have = [False] * rows
+
+
+ATTN_CACHE_MODES = ("store", "reuse")
+
+
+class _AttnCache:
+    """buffers of the sampler's attention broadcast (MMDiTModel.attention_broadcast_begin): slots bf16 [blocks, rows, L, D], one slot
+    per double and single block in the forward's order, each the block's attention output over the joint [txt; img] rows; have[row]:
+    does the row hold an entry (host; one flag per row, the blocks of a forward are stored together).  Under sequence parallelism
+    (shard = (lo, hi), this rank's rows of the joint sequence) L is the rank's OWN rows.  Row maps (which cache row a batch item of
+    the step belongs to) are int32 device arrays made once per row tuple and kept, so a captured graph finds them where they were."""
+
+    def __init__(self, key, blocks, rows, L, D, device, shard=None):
+        self.key, self.rows, self.L, self.shard = key, rows, L, shard
+        self.slots = torch.empty(blocks, rows, L, D, dtype=BF16, device=device)
+        self.have = [False] * rows
+        self._maps = {}
+
+    def row_map(self, rows: tuple):
+        """None where the step's batch items are the cache's leading rows in order (the kernel's identity), else the device array"""
+        if rows == tuple(range(len(rows))):
+            return None
+        m = self._maps.get(rows)
+        if m is None:
+            m = self._maps[rows] = torch.tensor(rows, dtype=torch.int32).to(self.slots.device)
+        return m
+
+    def mark(self, rows) -> None:
+        for r in rows:
+            self.have[r] = True
+
+    def clear(self) -> None:
+        self.have = [False] * self.rows
+
+
+@dataclass
+class _AttnStep:
+    """one block's share of an attention-broadcast forward: its slot bf16 [rows, L, D], the mode, the step's rows and their map"""
+    slot: Tensor
+    mode: str
+    rows: tuple
+    row_map: object
+
+    def view(self):
+        """the slot's rows of this step as a [B, L, D] view where they are evenly spaced (a GEMM's A operand reads it in place),
+        else None"""
+        r = self.rows
+        if len(r) == 1:
+            return self.slot[r[0]: r[0] + 1]
+        step = r[1] - r[0]
+        if step > 0 and all(b - a == step for a, b in zip(r, r[1:])):
+            return self.slot[r[0]: r[-1] + 1: step]
+        return None
+
+
+def _attn_store(attn: "_AttnStep", v: Tensor) -> None:
+    _OPS.attn_cache_copy(v, attn.slot, attn.row_map, True)
+
+
+def _attn_load(attn: "_AttnStep", v: Tensor) -> None:
+    _OPS.attn_cache_copy(attn.slot, v, attn.row_map, False)
 
 
 # =============================================================================================
@@ -953,8 +1015,11 @@ def _sp_window(ws) -> dict:
 
 
 def run_double_block(plan: _DoublePlan, ws: _Workspace, mod: Tensor, col_img: int, col_txt: int, rope: _RopeTable,
-                     H: int, hd: int, sp=None, x_in=None, x_out=None):
+                     H: int, hd: int, sp=None, x_in=None, x_out=None, attn=None):
     """DoubleStreamBlockProcessor.__call__ (layers.py:195-253) on the workspace's joint buffers.
+    attn (an _AttnStep, attention broadcast; None = the block as ever): "store" copies the attention output into the block's cache
+    slot right after the attention; "reuse" launches nothing in front of the two attention projections -- no first LN + modulate, no
+    q | k | v projection, no QK-norm / RoPE, no attention, under sp no exchange -- and hands them the slot's rows as their A operand.
     Residual streams live in ws.x ([:, :L_txt] txt, [:, L_txt:] img) and are updated in place.
     sp: a seqpar.SeqPar when the token axis is sharded (ws then holds this rank's rows; either stream may be
     empty on a rank) — K/V are projected first and all-gathered while the Q projection runs.
@@ -979,10 +1044,29 @@ def run_double_block(plan: _DoublePlan, ws: _Workspace, mod: Tensor, col_img: in
     if Lt:
         streams.append((plan.txt, r_txt, xm_txt, y[:, :Lt], t_sh1, t_sc1))
 
-    acts = [_ln_modulate_for(aw.qkv_w, x_s, sh1, sc1, xm_s, mbs) for aw, x_s, xm_s, y_s, sh1, sc1 in streams]
     q, k, v = y[:, :, :D], y[:, :, D: 2 * D], y[:, :, 2 * D:]
     scales = (plan.txt.q_scale, plan.txt.k_scale, plan.img.q_scale, plan.img.k_scale)
     paired = sp is None and len(streams) == 2      # both streams on this rank: their Linear layers go out in pairs
+    if attn is not None and attn.mode == "reuse":
+        # attention broadcast: the stored attention output stands for this step's.  Evenly spaced rows are read where they lie;
+        # any other row set is brought into the v columns by the cache copy first
+        v = attn.view()
+        if v is None:
+            v = y[:, :, 2 * D:]
+            _attn_load(attn, v)
+    else:
+        _double_block_attention(plan, ws, streams, q, k, v, scales, paired, mbs, rope, csb, Lt, H, hd, sp)
+        if attn is not None:
+            _attn_store(attn, v)
+    _double_block_rest(plan, ws, v, paired, Li, Lt, x_img, x_txt, r_img, r_txt, xm_img, xm_txt, mbs,
+                       (i_g1, i_sh2, i_sc2, i_g2), (t_g1, t_sh2, t_sc2, t_g2))
+
+
+def _double_block_attention(plan, ws, streams, q, k, v, scales, paired, mbs, rope, csb, Lt, H, hd, sp):
+    """run_double_block up to and including the attention: first LN + modulate, q | k | v projection, QK-norm + RoPE, attention (under
+    sp with the K / V exchange); the output lands in the v columns"""
+    D = H * hd
+    acts = [_ln_modulate_for(aw.qkv_w, x_s, sh1, sc1, xm_s, mbs) for aw, x_s, xm_s, y_s, sh1, sc1 in streams]
     vt_ready = False
     if (paired and ws.vt_group and not plan.pv8 and Lt % 64 == 0 and _bf16_operands(*acts, plan.img.qkv_w, plan.txt.qkv_w)):
         # ONE launch for the block's four projection problems: q | k of each stream into the row buffer, V of each stream straight
@@ -1031,6 +1115,12 @@ def run_double_block(plan: _DoublePlan, ws: _Workspace, mod: Tensor, col_img: in
             _linear(act, aw.qkv_w[:D], None if aw.qkv_b is None else aw.qkv_b[:D], y_s[:, :, :D])
         _OPS.qknorm_rope(q, None, *scales, Lt, rope.cos, rope.sin, csb, H, hd, rope.mode, q_mult=q_mult(hd))
         sp.attention(ws, pending, q, v, H, hd, plan.score_bound)
+
+
+def _double_block_rest(plan, ws, v, paired, Li, Lt, x_img, x_txt, r_img, r_txt, xm_img, xm_txt, mbs, mod_img, mod_txt):
+    """run_double_block behind the attention: the two attention projections with their gate / residual epilogue, second LN + modulate,
+    MLP.  v: the attention output bf16 [B, L, D], joint [txt; img] rows -- the workspace's v columns, or a cache slot's rows"""
+    (i_g1, i_sh2, i_sc2, i_g2), (t_g1, t_sh2, t_sc2, t_g2) = mod_img, mod_txt
     if paired:   # layers.py:247-252 for both streams, Linear by Linear
         _linear_pair(dict(a=v[:, Lt:], w=plan.img.proj_w, bias=plan.img.proj_b, out=x_img, res=r_img, gate=i_g1, gate_batch_stride=mbs),
                      dict(a=v[:, :Lt], w=plan.txt.proj_w, bias=plan.txt.proj_b, out=x_txt, res=r_txt, gate=t_g1, gate_batch_stride=mbs))
@@ -1054,9 +1144,11 @@ def run_double_block(plan: _DoublePlan, ws: _Workspace, mod: Tensor, col_img: in
 
 
 def run_single_block(plan: _SinglePlan, ws: _Workspace, mod: Tensor, col: int, rope: _RopeTable, H: int, hd: int,
-                     R: int, sp=None, x_in=None, x_out=None):
+                     R: int, sp=None, x_in=None, x_out=None, attn=None):
     """SingleStreamBlockProcessor.__call__ (layers.py:309-334).  linear1's output row is [q|k|v|mlp]; attention
     writes into the v slot so linear2 reads the contiguous [attn | gelu(mlp)] columns: no torch.cat.
+    attn (an _AttnStep, attention broadcast; None = the block as ever): see run_double_block.  A "reuse" block runs three launches
+    in front of linear2: LN + modulate, the MLP-up columns of linear1, the copy of the cache slot into the v columns.
     sp: see run_double_block — the K/V all-gather overlaps the Q and MLP-up projections.
     x_in / x_out (stand-alone processor calls): read the stream from x_in, write the block's result into x_out."""
     D = H * hd
@@ -1068,7 +1160,13 @@ def run_single_block(plan: _SinglePlan, ws: _Workspace, mod: Tensor, col: int, r
     act = _ln_modulate_for(plan.w1, x_src, shift, scale, ws.xm, mbs)
     q, k, v = y[:, :, :D], y[:, :, D: 2 * D], y[:, :, 2 * D: 3 * D]
     scales = (plan.q_scale, plan.k_scale, plan.q_scale, plan.k_scale)
-    if sp is None:
+    if attn is not None and attn.mode == "reuse":
+        # attention broadcast: linear1's MLP-up columns alone (the call the sequence-parallel path below makes), the stored
+        # attention output into the v columns beside them; linear2 then reads [attn | gelu(mlp)] as ever
+        b1 = plan.b1
+        _linear(act, plan.w1[3 * D:], None if b1 is None else b1[3 * D:], y[:, :, 3 * D:], gelu_from=0)
+        _attn_load(attn, v)
+    elif sp is None:
         vt_ready = False
         if ws.vt_group and not plan.pv8 and (2 * D) % 256 == 0 and _bf16_operands(act, plan.w1):
             # linear1 WITHOUT its V columns (row layout [q | k | . | gelu(mlp)]) and V straight into ws.vt, one launch
@@ -1108,6 +1206,8 @@ def run_single_block(plan: _SinglePlan, ws: _Workspace, mod: Tensor, col: int, r
             pending = sp.q_exchange_start(pending, q, H, hd)
             mlp_up()
         sp.attention(ws, pending, q, v, H, hd, plan.score_bound)
+    if attn is not None and attn.mode == "store":
+        _attn_store(attn, v)
     _linear(y[:, :, 2 * D:], plan.w2, plan.b2, x_dst, res=x_src, gate=gate, gate_batch_stride=mbs)
 
 
@@ -1148,13 +1248,21 @@ def _direct_ok(*ts) -> bool:
     return all(t.dtype == BF16 and t.is_contiguous() and t.data_ptr() % 16 == 0 for t in ts)
 
 
+def _processor_attn_cache_check(attn_cache) -> None:
+    """attention broadcast belongs to a step of a sampling loop; a stand-alone processor call has no step identity and no slot"""
+    if attn_cache is not None:
+        raise ValueError("attn_cache: attention broadcast is not available to stand-alone block processor calls (no step identity, no "
+                         "cache slot per block); drive an open_sora_amd.mmdit.MMDiTModel through forward_ckpt(attn_cache=...)")
+
+
 class HipDoubleStreamBlockProcessor:
     """Drop-in for DoubleStreamBlockProcessor (layers.py:195-253): `(block, img, txt, vec, pe) -> (img, txt)`.
     bf16 callers (the reference's inference dtype): the kernels read the caller's img / txt in place (LayerNorm input, residual of
     the attention-projection GEMM) and the residual stream continues in two fresh output tensors that are returned as they are
     -- no copy in, no clone out; other dtypes are staged through the workspace."""
 
-    def __call__(self, attn: nn.Module, img: Tensor, txt: Tensor, vec: Tensor, pe) -> tuple[Tensor, Tensor]:
+    def __call__(self, attn: nn.Module, img: Tensor, txt: Tensor, vec: Tensor, pe, attn_cache=None) -> tuple[Tensor, Tensor]:
+        _processor_attn_cache_check(attn_cache)
         H, hd = attn.num_heads, attn.head_dim
         D = H * hd
         plan = plan_double(attn)
@@ -1179,7 +1287,8 @@ class HipSingleStreamBlockProcessor:
     """Drop-in for SingleStreamBlockProcessor (layers.py:309-334): `(block, x, vec, pe) -> x` (bf16 callers: x is read in place,
     the result is written straight into the returned tensor)."""
 
-    def __call__(self, attn: nn.Module, x: Tensor, vec: Tensor, pe) -> Tensor:
+    def __call__(self, attn: nn.Module, x: Tensor, vec: Tensor, pe, attn_cache=None) -> Tensor:
+        _processor_attn_cache_check(attn_cache)
         H, hd = attn.num_heads, attn.head_dim
         D = H * hd
         plan = plan_single(attn)
@@ -1564,10 +1673,12 @@ class MMDiTModel(_OskState, nn.Module):
         return ws, vec, rope
 
     def forward_ckpt(self, img: Tensor, img_ids: Tensor, txt: Tensor, txt_ids: Tensor, timesteps: Tensor,
-                     y_vec: Tensor, cond: Tensor = None, guidance: Tensor | None = None, **kwargs) -> Tensor:
+                     y_vec: Tensor, cond: Tensor = None, guidance: Tensor | None = None, attn_cache=None, **kwargs) -> Tensor:
         """MMDiTModel.forward_ckpt (model.py:208-233); inference only.  With sequence parallelism enabled
         (open_sora_amd.seqpar.enable) this is mmdit_model_forward (distributed.py:580-683): every rank gets the
-        full inputs, works on its contiguous token chunk and returns the full [B, L_img, C] prediction."""
+        full inputs, works on its contiguous token chunk and returns the full [B, L_img, C] prediction.
+        attn_cache = (cache, "store" | "reuse", rows): attention broadcast (attention_broadcast_begin; rows = the cache row of each
+        batch item).  None: the call as ever."""
         sp = getattr(self, "_sp", None)
         L_img, L_txt = img.shape[1], txt.shape[1]
         shard = None
@@ -1575,8 +1686,13 @@ class MMDiTModel(_OskState, nn.Module):
             shard = sp.shard_range(L_txt + L_img, L_txt)  # None when a rank would hold no image tokens
             if shard is None:
                 sp = None
+        if attn_cache is not None:
+            self._attn_cache_check(attn_cache, img.shape[0], L_txt + L_img if shard is None else shard[1] - shard[0], shard)   # (before any launch)
         st = self._forward_head(sp, shard, img, img_ids, txt, txt_ids, timesteps, y_vec, cond, guidance)
-        self._forward_blocks(st)
+        if attn_cache is None:
+            self._forward_blocks(st)
+        else:
+            self._forward_blocks_broadcast(st, attn_cache)
         return self._forward_tail(st)
 
     # The forward in three parts (head / blocks / tail), the launches of forward_ckpt in its order; the sampler's step cache drives
@@ -1596,7 +1712,7 @@ class MMDiTModel(_OskState, nn.Module):
         p = self._plan
         mod = torch.empty(img.shape[0], p["mod_cols"], dtype=torch.float32, device=img.device)
         _OPS.gemv_tasks(vec, p["mod_tasks"], mod, act_in=1)
-        return _StepState(ws, rope, mod, p, sp, img.shape[0], txt.shape[1], img.dtype, img.device)
+        return _StepState(ws, rope, mod, p, sp, img.shape[0], txt.shape[1], img.dtype, img.device, shard)
 
     def _forward_blocks(self, st: "_StepState") -> None:
         D, H = self.hidden_size, self.num_heads
@@ -1607,6 +1723,71 @@ class MMDiTModel(_OskState, nn.Module):
             run_double_block(plan, st.ws, st.mod, ci, ct, st.rope, H, hd, st.sp)
         for plan, c in zip(p["single"], p["col_single"]):
             run_single_block(plan, st.ws, st.mod, c, st.rope, H, hd, R, st.sp)
+
+    # ------------------------------------------------------------------ attention broadcast (driven by sampling.I2VDenoiser)
+    def attention_broadcast_begin(self, rows: int, L_txt: int, L_img: int, device) -> "_AttnCache":
+        """The cache of one attention-broadcast sampling loop whose steps run up to `rows` batch rows of L_txt + L_img tokens: one
+        slot bf16 [rows, L, D] per double and single block, holding the block's attention output (joint [txt; img] order) of the
+        last "store" forward of each row.  blocks x rows x L x D x 2 bytes.  Kept, like the activation workspaces, per (geometry,
+        device, stream): the last loop's set is reused and never moves (a captured graph replays into it), another geometry
+        replaces it.  Which rows hold an entry starts empty on every call.  Under sequence parallelism the slots hold this
+        rank's rows of the split the forward itself makes (SeqPar.shard_range) -- 1 / P of the memory per rank -- and the rank's
+        row range and the rank count are part of the key; a geometry whose split is declined gets the single-device set."""
+        blocks = len(self.double_blocks) + len(self.single_blocks)
+        if rows < 1 or L_txt < 0 or L_img < 1 or blocks == 0:
+            raise ValueError(f"attention_broadcast_begin: rows >= 1, L_txt >= 0, L_img >= 1 and a model with blocks expected; got {(rows, L_txt, L_img, blocks)}")
+        L = L_txt + L_img
+        key = (blocks, rows, L_txt, L_img, self.hidden_size, str(device), _stream_key(device), id(_OPS))
+        sp = getattr(self, "_sp", None)
+        shard = None if sp is None else sp.shard_range(L, L_txt)
+        if shard is not None:
+            key += (shard[0], shard[1], sp.P)
+            L = shard[1] - shard[0]
+        ac = getattr(self, "_osk_attn_cache", None)
+        if ac is None or ac.key != key:
+            if ac is not None:
+                object.__delattr__(self, "_osk_attn_cache")      # (the old set goes before the new one is allocated)
+                del ac
+            ac = _AttnCache(key, blocks, rows, L, self.hidden_size, device, shard)
+            object.__setattr__(self, "_osk_attn_cache", ac)
+        ac.clear()
+        return ac
+
+    def _attn_cache_check(self, attn_cache, B: int, Lloc: int, shard):
+        """(cache, mode, rows) of a forward_ckpt / step_run call, checked against this forward (B batch rows of Lloc local tokens, the
+        rank's row range or None): ValueError, in forward_ckpt before any launch"""
+        try:
+            ac, mode, rows = attn_cache
+            rows = tuple(int(r) for r in rows)
+        except (TypeError, ValueError):
+            raise ValueError(f"attn_cache: (cache, 'store' | 'reuse', rows) expected; got {attn_cache!r}") from None
+        if not isinstance(ac, _AttnCache) or mode not in ATTN_CACHE_MODES:
+            raise ValueError(f"attn_cache: (cache of attention_broadcast_begin, 'store' | 'reuse', rows) expected; got mode {mode!r}, "
+                             f"cache {type(ac).__name__}")
+        if len(rows) != B or len(set(rows)) != B or min(rows) < 0 or max(rows) >= ac.rows:
+            raise ValueError(f"attn_cache: rows {rows} are not {B} distinct rows of a cache of {ac.rows}")
+        if shard != ac.shard or Lloc != ac.L or ac.slots.shape[0] != len(self.double_blocks) + len(self.single_blocks):
+            raise ValueError(f"attn_cache: this forward's rows {shard} ({Lloc} tokens) of the joint sequence are not the cache's "
+                             f"{ac.shard} ({ac.L} tokens)")
+        if mode == "reuse" and not all(ac.have[r] for r in rows):
+            raise ValueError(f"attn_cache: reuse of rows {[r for r in rows if not ac.have[r]]}, which hold no entry yet")
+        return ac, mode, rows
+
+    def _forward_blocks_broadcast(self, st: "_StepState", attn_cache) -> None:
+        """_forward_blocks with every block's attention output stored to ("store") or taken from ("reuse") its cache slot"""
+        D, H = self.hidden_size, self.num_heads
+        hd = D // H
+        R = int(D * self.config.mlp_ratio)
+        p = st.plan
+        ac, mode, rows = self._attn_cache_check(attn_cache, st.B, st.ws.L, st.shard)
+        row_map = ac.row_map(rows)
+        slots = iter(ac.slots)
+        for plan, (ci, ct) in zip(p["double"], p["col_double"]):
+            run_double_block(plan, st.ws, st.mod, ci, ct, st.rope, H, hd, st.sp, attn=_AttnStep(next(slots), mode, rows, row_map))
+        for plan, c in zip(p["single"], p["col_single"]):
+            run_single_block(plan, st.ws, st.mod, c, st.rope, H, hd, R, st.sp, attn=_AttnStep(next(slots), mode, rows, row_map))
+        if mode == "store":
+            ac.mark(rows)
 
     def _forward_tail(self, st: "_StepState") -> Tensor:
         # LastLayer (layers.py:398-402): (shift, scale) order
@@ -1706,14 +1887,18 @@ class MMDiTModel(_OskState, nn.Module):
             _OPS.step_sums_combine(sc.pairs, sc.sums)
         return st
 
-    def step_run(self, sc: "_StepCache", st: "_StepState") -> Tensor:
+    def step_run(self, sc: "_StepCache", st: "_StepState", attn_cache=None) -> Tensor:
         """a computed step: X_i of the rows it runs is saved, the blocks run, R[row] = bf16(f32(Y) - f32(X_i)) replaces the saved
         rows; the other rows keep their older residual.  Sharded: the same over this rank's image rows; the blocks and the tail
-        get the sp object the head carried, so the tail gathers the prediction as the uncached forward does"""
+        get the sp object the head carried, so the tail gathers the prediction as the uncached forward does.
+        attn_cache: forward_ckpt's argument, for a loop that runs the step cache and attention broadcast together"""
         ws, m = st.ws, st.B
         x_img, r = ws.x[:, ws.L_txt:], sc.res[:m]
         _OPS.copy_rows(x_img, r)
-        self._forward_blocks(st)
+        if attn_cache is None:
+            self._forward_blocks(st)
+        else:
+            self._forward_blocks_broadcast(st, attn_cache)
         _OPS.residual_sub(x_img, r, r)
         sc.have[:m] = [True] * m
         return self._forward_tail(st)

@@ -176,6 +176,59 @@ def step_cache_decide(i: int, n_steps: int, d: float, acc: float, threshold: flo
     return True, 0.0
 
 
+def _attn_broadcast_default():
+    """OSK_ATTN_BROADCAST, read at call time like OSK_CFG_PRUNE: the interval as an int (unset or empty: off)"""
+    v = os.environ.get("OSK_ATTN_BROADCAST", "").strip()
+    return int(v) if v else None
+
+
+# The band of the published pyramid-attention-broadcast schedule, [100, 800] of 1000 diffusion timesteps, transcribed onto the
+# rectified-flow time of this sampler (t runs from 1 to 0).  NOT validated on a checkpoint.
+ATTN_BROADCAST_RANGE = (0.1, 0.8)
+
+
+def attn_broadcast_plan(timesteps, interval, t_range=ATTN_BROADCAST_RANGE) -> list[str]:
+    """The attention-broadcast mode of every step of a loop over `timesteps` (the schedule denoise() takes: N + 1 values, step i runs
+    at t = timesteps[i]) -- N entries of "plain" | "store" | "reuse" (DESIGN.md section 4), from the step index and Python floats
+    alone: no device value, no collective, the same list on every rank.
+    Step 0 and the last step are plain; so is every step whose t lies outside [lo, hi] (both ends inclusive).  The steps inside
+    cycle through one computed step followed by interval - 1 reuse steps; leaving the range ends the cycle.  A computed step is
+    "store" iff the step after it is "reuse", else "plain".  interval <= 1: all plain."""
+    n = len(timesteps) - 1
+    lo, hi = (float(v) for v in t_range)
+    interval = int(interval)
+    modes = ["plain"] * max(n, 0)
+    if interval <= 1:
+        return modes
+    pos = 0
+    for i in range(n):
+        if not (0 < i < n - 1 and lo <= float(timesteps[i]) <= hi):
+            pos = 0
+            continue
+        modes[i] = "reuse" if pos else "computed"
+        pos = (pos + 1) % interval
+    return [("store" if i + 1 < n and modes[i + 1] == "reuse" else "plain") if m == "computed" else m for i, m in enumerate(modes)]
+
+
+def attn_broadcast_effective(plan, counts, n: int = 1) -> list[str]:
+    """what the steps of a loop actually run: the plan, with the cache's per-row entries followed on the host.  Step i runs the
+    counts[i] * n leading rows.  A computed step ("plain" or "store") drops every entry -- an entry is only ever reused inside the
+    cycle that stored it -- and a "store" step then leaves one for each of its rows; a "reuse" step that needs a row without an
+    entry (a pruned loop whose step runs more branches than the cycle's store did) becomes a "store" step.  Static, like the plan."""
+    have = [False] * (max(counts, default=0) * n)
+    out = []
+    for mode, nb in zip(plan, counts):
+        m = nb * n
+        if mode == "reuse" and not all(have[:m]):
+            mode = "store"
+        if mode != "reuse":
+            have = [False] * len(have)
+        if mode == "store":
+            have[:m] = [True] * m
+        out.append(mode)
+    return out
+
+
 class I2VDenoiser:
     """sampling.py:158-245.  `denoise(model, img=..., timesteps=[...], guidance=..., guidance_img=..., masks=...,
     masked_ref=..., img_ids=..., txt=..., txt_ids=..., y_vec=..., [text_osci, image_osci, scale_temporal_osci,
@@ -218,7 +271,22 @@ class I2VDenoiser:
     are accepted; still refused there: a frame window together with the step cache, and an sp object without SeqPar.step_cache.
     The exchange of the sums on a multi-GPU node is not measured.
     No calibrated polynomial ships (default: the identity), and neither the skip rate nor the
-    output quality on real checkpoints is measured: a skipped step's result DIFFERS from the reference's."""
+    output quality on real checkpoints is measured: a skipped step's result DIFFERS from the reference's.
+
+    `attn_broadcast=interval` (default: OSK_ATTN_BROADCAST, read at call time; unset or <= 1 = off) with
+    `attn_broadcast_range=(lo, hi)`: opt-in attention broadcast of the pyramid-attention-broadcast kind.  Inside the range of the
+    rectified-flow time every interval-th step computes its attention and stores each block's attention output
+    (osk_attn_cache_copy_bf16 into a slot per block); the interval - 1 steps behind it run their own modulation, projections and MLPs
+    but take the attention output from the slot: no q | k | v projection, QK-norm / RoPE or attention launch, and under sequence
+    parallelism no K / V exchange (attn_broadcast_plan states the schedule, DESIGN.md section 4 the rule).  The schedule depends on
+    the step index alone: no read back, no collective, and with hip_graph one graph per (batch size, mode) in use.  Composes
+    with cfg_prune (entries are kept per row; a reuse step that needs a row without one computes and stores instead:
+    attn_broadcast_effective), attn_window_frames / anchors, fp8 / qk8, sequence parallelism and step_cache (a step the step
+    cache skips launches no block: it neither stores nor reuses).  `last_attn_broadcast` holds the mode each step of the last run
+    took (None when off).  Memory: blocks x rows x L x D x 2 bytes (under sequence parallelism 1 / P of it per rank).  The
+    default range (0.1, 0.8) is the published method's [100, 800]-of-1000 band transcribed onto this schedule; it is NOT
+    validated on a checkpoint, and the output quality on real checkpoints is not measured: a reuse step's result DIFFERS from the
+    reference's.  Refused for models without the head / blocks / tail split."""
 
     def denoise(self, model, **kwargs) -> Tensor:
         img = kwargs.pop("img")
@@ -245,6 +313,21 @@ class I2VDenoiser:
         if isinstance(step_cache, str) and step_cache == "env":
             step_cache = _step_cache_default()
         coefficients = kwargs.pop("step_cache_coefficients", None)
+        attn_broadcast = kwargs.pop("attn_broadcast", "env")
+        if isinstance(attn_broadcast, str) and attn_broadcast == "env":
+            attn_broadcast = _attn_broadcast_default()
+        ab_range = kwargs.pop("attn_broadcast_range", None)
+        self.last_attn_broadcast = None
+        if attn_broadcast is not None:
+            attn_broadcast = int(attn_broadcast)
+            ab_range = ATTN_BROADCAST_RANGE if ab_range is None else tuple(float(v) for v in ab_range)
+            if len(ab_range) != 2 or not ab_range[0] <= ab_range[1]:
+                raise ValueError(f"attn_broadcast_range: (lo, hi) with lo <= hi expected; got {ab_range}")
+            if not all(hasattr(model, a) for a in ("attention_broadcast_begin", "forward_ckpt", "step_run")):
+                raise ValueError("attn_broadcast needs a model with the head / blocks / tail split and a cache slot per block "
+                                 f"(open_sora_amd.mmdit.MMDiTModel); {type(model).__name__} has none")
+            if attn_broadcast <= 1:
+                attn_broadcast = None                    # every step plain: the loop from before, launch for launch
         self.last_step_cache = None
         if step_cache is not None:
             step_cache = float(step_cache)
@@ -279,7 +362,8 @@ class I2VDenoiser:
                                     masked_ref=masked_ref, text_osci=text_osci, image_osci=image_osci,
                                     scale_temporal_osci=scale_temporal_osci, patch_size=patch_size, hip_graph=hip_graph,
                                     cfg_prune=cfg_prune, attn_window_frames=None, step_cache=step_cache,
-                                    step_cache_coefficients=coefficients, **kwargs)
+                                    step_cache_coefficients=coefficients, attn_broadcast=attn_broadcast, attn_broadcast_range=ab_range,
+                                    **kwargs)
             finally:
                 model.set_attention_window(*(previous if previous is not None else (None,)),
                                            **({"anchors": previous_anchors} if previous is not None and hasattr(model, "_attn_anchors") else {}))
@@ -305,11 +389,18 @@ class I2VDenoiser:
         x_next = torch.empty_like(x)
         img3 = torch.empty(n3, *x.shape[1:], device=dev, dtype=dt)
         t_vec = torch.empty(n3, dtype=dt, device=dev)
+        ab = {}
+        if attn_broadcast is not None:
+            # the static schedule of this loop; the loops below follow the cache's entries from it
+            self.last_attn_broadcast = []
+            ab = {"ab": (attn_broadcast_plan(timesteps, attn_broadcast, ab_range), self.last_attn_broadcast)}
         if step_cache is not None:
             self.last_step_cache = []
             return self._loop_step_cache(model, kwargs, x, x_next, img3, t_vec, cond3, guidance_vec, timesteps, guidance, guidance_img,
                                          text_osci, image_osci, scale_temporal_osci, patch_size, b, c, t, h_, w_, dev, counts, cfg_prune,
-                                         step_cache, coefficients, self.last_step_cache).to(dt)
+                                         step_cache, coefficients, self.last_step_cache, **ab).to(dt)
+        if ab:
+            loop, tail = self._loop_attn_broadcast, (counts, cfg_prune) + ab["ab"]
         graph, pred = None, None
         if hip_graph:
             # capture needs a non-default stream, and the model's workspaces are keyed on the stream: run the WHOLE loop (the
@@ -421,13 +512,17 @@ class I2VDenoiser:
     @staticmethod
     def _loop_step_cache(model, kwargs, x, x_next, img3, t_vec, cond3, guidance_vec, timesteps, guidance, guidance_img, text_osci,
                          image_osci, scale_temporal_osci, patch_size, b, c, t, h_, w_, dev, counts, pruned, threshold, coefficients,
-                         record):
+                         record, ab=None):
         """_loop (pruned: _loop_pruned) with the step cache: the model's forward is driven in its three parts.  Every step runs the
         head on its counts[i] leading branches and the distance of the conditional rows; step_cache_decide then picks the block
         stack (step_run: the rows' residuals are stored) or the stored residuals (step_skip).  The inputs, the combine kernel and
-        their order are those of the loop it stands for, so a run that computes every step gives that loop's bits."""
+        their order are those of the loop it stands for, so a run that computes every step gives that loop's bits.
+        ab = (plan, record) with attention broadcast on as well: the plan is indexed by step; a computed step runs its blocks in the
+        plan's mode (a reuse step that lacks an entry stores instead), a skipped step launches no block and touches no entry --
+        except that a skipped step the plan wanted computed drops the entries, so the reuse steps behind it compute."""
         n = x.shape[0]
         n_steps = len(timesteps) - 1
+        ac = None if ab is None else model.attention_broadcast_begin(max(counts, default=3) * n, kwargs["txt"].shape[1], img3.shape[1], dev)
         # (a sharded model cuts the buffers to its rank's rows and needs the text length for that; every rank then measures its share
         # of the distance and all of them read the same combined sums, so the decisions below are the same on every rank)
         sharded = {} if getattr(model, "_sp", None) is None else {"L_txt": kwargs["txt"].shape[1]}
@@ -451,8 +546,80 @@ class I2VDenoiser:
             st = model.step_head(sc, **kw)
             d = math.inf if i == 0 else model.step_distance(sc)       # the one host synchronisation of a step
             computed, acc = step_cache_decide(i, n_steps, d, acc, threshold, coefficients, all(sc.have[:m]))
-            pred = model.step_run(sc, st) if computed else model.step_skip(sc, st)
+            if ab is None:
+                pred = model.step_run(sc, st) if computed else model.step_skip(sc, st)
+            else:
+                mode = ab[0][i]
+                if computed and mode == "reuse" and not all(ac.have[:m]):
+                    mode = "store"
+                if mode != "reuse":
+                    ac.clear()
+                pred = (model.step_run(sc, st, None if mode == "plain" else (ac, mode, tuple(range(m)))) if computed else
+                        model.step_skip(sc, st))
+                ab[1].append(mode if computed else "skipped")
             record.append((d, acc, computed))
+            text_gs = get_oscillation_gs(guidance, i) if text_osci else guidance
+            image_gs = get_oscillation_gs(guidance_img, i) if image_osci else guidance_img
+            gvec = None
+            if nb == 3 and image_gs > 1.0 and scale_temporal_osci:
+                upper = torch.linspace(image_gs, 1.0, len(timesteps))[i]
+                ramp = torch.linspace(1.0, float(upper), t)[None, None, :, None, None].repeat(b, c, 1, h_, w_)
+                gvec = pack(ramp, patch_size=patch_size).to(dev, torch.float32).contiguous()
+                image_gs = 1.0
+            pred = pred.to(torch.bfloat16).contiguous()
+            if pruned:
+                _ops().cfg_euler_nb(pred, nb, x, x_next, float(text_gs), float(image_gs), float(t_prev - t_curr), gvec)
+            else:
+                _ops().cfg_euler(pred, x, x_next, float(text_gs), float(image_gs), float(t_prev - t_curr), gvec)
+            x, x_next = x_next, x
+        return x
+
+    @staticmethod
+    def _loop_attn_broadcast(model, kwargs, x, x_next, img3, t_vec, cond3, guidance_vec, timesteps, guidance, guidance_img, text_osci,
+                             image_osci, scale_temporal_osci, patch_size, b, c, t, h_, w_, dev, hip_graph, side, counts, pruned, plan,
+                             record):
+        """_loop (pruned: _loop_pruned) with attention broadcast: step i runs the model on its counts[i] leading branches in the mode
+        attn_broadcast_effective gives it -- "plain": the forward as ever; "store" / "reuse": forward_ckpt(attn_cache=...) on the
+        loop's cache, rows = the leading rows of the triple.  The inputs, the combine kernel and their order are those of the loop
+        it stands for.  hip_graph: as in _loop_pruned, the first step of every (branch count, mode) runs eagerly and is captured
+        for the later ones -- the modes are known up front, the row maps and the cache never move."""
+        n = x.shape[0]
+        modes = attn_broadcast_effective(plan, counts, n)
+        ac = model.attention_broadcast_begin(max(counts, default=3) * n, kwargs["txt"].shape[1], img3.shape[1], dev)
+        inputs = {}    # branch count -> the model's keyword arguments for it
+        graphs = {}    # (branch count, mode) -> (hipGraph of the forward, its output tensor)
+        keys = list(zip(counts, modes))
+        for i, (t_curr, t_prev) in enumerate(zip(timesteps[:-1], timesteps[1:])):
+            nb, mode = keys[i]
+            m = nb * n
+            kw = inputs.get(nb)
+            if kw is None:
+                kw = inputs[nb] = {k: (v[:m] if torch.is_tensor(v) and v.ndim >= 1 and v.shape[0] == 3 * n else v) for k, v in kwargs.items()}
+                kw.update(img=img3[:m], cond=cond3[:m], timesteps=t_vec[:m], guidance=guidance_vec[:m])
+            t_vec.fill_(t_curr)
+            dst = kw["img"]
+            if _ops().copy_rows_ok(x, dst[:n]):
+                for j in ([None] if n == 1 else range(nb)):
+                    _ops().copy_rows(x, dst if j is None else dst[j * n:(j + 1) * n])
+            else:
+                dst.view(nb, *x.shape).copy_(x.unsqueeze(0).expand(nb, *x.shape))
+            rows = tuple(range(m))
+            if mode != "reuse":
+                ac.clear()
+            if (nb, mode) in graphs:
+                graphs[(nb, mode)][0].replay()
+                pred = graphs[(nb, mode)][1]
+                if mode == "store":
+                    ac.mark(rows)                 # (an eager store forward marks its rows itself)
+            else:
+                extra = {} if mode == "plain" else {"attn_cache": (ac, mode, rows)}
+                pred = model(**kw, **extra)
+                if hip_graph and (nb, mode) in keys[i + 1:]:
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g, stream=side):
+                        pred_g = model(**kw, **extra)
+                    graphs[(nb, mode)] = (g, pred_g)
+            record.append(mode)
             text_gs = get_oscillation_gs(guidance, i) if text_osci else guidance
             image_gs = get_oscillation_gs(guidance_img, i) if image_osci else guidance_img
             gvec = None
@@ -492,6 +659,10 @@ class DistilledDenoiser:
         guidance = kwargs.pop("guidance")
         hip_graph = bool(kwargs.pop("hip_graph", False))
         kwargs.pop("step_cache_coefficients", None)
+        kwargs.pop("attn_broadcast_range", None)
+        if kwargs.pop("attn_broadcast", None) is not None:
+            # (the keyword only, as for step_cache below: OSK_ATTN_BROADCAST is I2VDenoiser's default)
+            raise ValueError("attn_broadcast is out of scope for DistilledDenoiser: its loop has no step schedule to broadcast over")
         if kwargs.pop("step_cache", None) is not None:
             # (the keyword only: OSK_STEP_CACHE is I2VDenoiser's default and leaves the image stage of a t2i2v run alone)
             raise ValueError("step_cache is out of scope for DistilledDenoiser: its loop has no head / blocks / tail split")
