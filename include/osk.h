@@ -748,13 +748,39 @@ int osk_causal_conv3d_ndhwc_bf16(const void* x, int B, int T, int H, int W, int 
  *   f64 atomics across tiles) -- feed it to osk_groupnorm_apply_ndhwc_bf16.  The waves of a tile add their partials with
  *   LDS float atomics: the result is reproducible to f32 rounding of a tile's partial (~1e-7 relative), not bit for bit.
  * Only the large-tile kernels carry this epilogue: returns OSK_EUNSUPPORTED -- and launches NOTHING -- unless
- * Cin % 128 == 0, Cout >= 128, Cout % 32 == 0, Cout / gn_groups in {4, 8, 16}, >= 256 output voxels, out 16-byte aligned and
+ * Cin % 128 == 0, Cout >= 128, Cout % 32 == 0, Cout / gn_groups in {4, 8, 16}, >= 256 output voxels, out and res 16-byte aligned and
  * (B == 1 or To*Ho*Wo % 256 == 0); the caller then runs the plain conv + osk_groupnorm_stats_ndhwc_bf16. */
 int osk_causal_conv3d_gn_ndhwc_bf16(const void* x, int B, int T, int H, int W, int Cin,
                                     const void* w, int64_t w_row_stride, const float* bias, int Cout, int ksize,
                                     int stride_t, int stride_h, int stride_w, int up_t, int up_hw,
                                     const void* res, void* out, int To, int Ho, int Wo,
                                     double* gn_sums, int gn_groups, void* stream);
+
+/* ---- which kernel serves a causal conv call (host only: launches nothing, needs no device).  The three entry points launch by
+ * switching on the value this reports (one selection function, csrc/conv_params.h), so report and launch cannot drift.
+ *   the shape arguments of osk_causal_conv3d_ndhwc_bf16;
+ *   out_align / res_align: the byte alignment of out / res as a power of two (8, 16, ...; res_align 0 = no residual);
+ *   gn_groups > 0: as osk_causal_conv3d_gn_ndhwc_bf16 with that many groups (gn_sums != NULL);  gn_in != 0: as
+ *   osk_causal_conv3d_gnin_ndhwc_bf16 (that entry point has no upsample; with up_t or up_hw set the report is OSK_EUNSUPPORTED).
+ * Returns the negative status the entry point would return -- OSK_EUNSUPPORTED where gn_sums / gn_in is asked of a shape whose
+ * kernel does not carry it, nothing launched -- or OSK_CONV_* | (OSK_CONV_FUSED_STATS when the fused-statistics epilogue is on).
+ * The fused statistics need out AND res 16-byte aligned (they ride in the epilogue's 16-byte path). */
+#define OSK_CONV_TILE128 0       /* conv3d_kernel<false>: 128 x 128 implicit-GEMM tile, Cin % 64 != 0 */
+#define OSK_CONV_TILE128_BIGC 1  /* conv3d_kernel<true>: the same tile, Cin % 64 == 0 */
+#define OSK_CONV_FEWOUT 2        /* conv_fewout_kernel<Cout>, Cout <= 4 */
+#define OSK_CONV_X4 3            /* conv256x_kernel<4>: 256 voxels x 128 channels, table-driven implicit GEMM */
+#define OSK_CONV_X8 4            /* conv256x_kernel<8>: 256 x 256 */
+#define OSK_CONV_SW4 5           /* convsw_kernel<4>: sliding window, 128 channels per tile */
+#define OSK_CONV_SW8 6           /* convsw_kernel<8>: 256 channels per tile */
+#define OSK_CONV_SW4_UP 7        /* convsw_kernel<4, UP>: the nearest upsample folded into the halo */
+#define OSK_CONV_SW8_UP 8        /* convsw_kernel<8, UP> */
+#define OSK_CONV_SW8_GN 9        /* convsw_kernel<8, false, GN>: input GroupNorm + SiLU folded in */
+#define OSK_CONV_SW2 10          /* convsw2_kernel: two-frame tiles, Cout == 128 */
+#define OSK_CONV_SW2_GN 11       /* convsw2_kernel<GN> */
+#define OSK_CONV_FUSED_STATS 0x100
+int osk_causal_conv3d_kernel_class(int B, int T, int H, int W, int Cin, int64_t w_row_stride, int Cout, int ksize,
+                                   int stride_t, int stride_h, int stride_w, int up_t, int up_hw, int To, int Ho, int Wo,
+                                   int out_align, int res_align, int gn_groups, int gn_in);
 
 /* =====================================================================================================
  * Flux 2-D autoencoder (/root/reference/opensora/models/vae/autoencoder_2d.py, the image stage of the t2i2v pipeline).

@@ -96,6 +96,8 @@ SIGNATURES = {
                                      _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp],
     "osk_causal_conv3d_gn_ndhwc_bf16": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32,
                                         _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp],
+    "osk_causal_conv3d_kernel_class": [_i32, _i32, _i32, _i32, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                                       _i32, _i32, _i32, _i32, _i32],
     "osk_causal_conv3d_gnin_ndhwc_bf16": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i32, _i32, _i32, _i32,
                                           _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp],
     "osk_conv2d_nhwc_bf16": [_vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32,
@@ -1288,6 +1290,24 @@ def causal_conv3d(x: torch.Tensor, w: torch.Tensor, bias, out: torch.Tensor, ksi
         ev1.record()
         prof.append((ev0, ev1, 2.0 * Cin * Cout * ksize ** 3 * B * To * Ho * Wo))
     return out if gn_sums is None else (out, fused)
+
+
+CONV_KERNEL_CLASSES = ("tile128", "tile128_bigc", "fewout", "conv256x4", "conv256x8", "convsw4", "convsw8", "convsw4_up", "convsw8_up",
+                       "convsw8_gn", "convsw2", "convsw2_gn")     # OSK_CONV_* of include/osk.h, by value
+
+
+def conv_kernel_class(B: int, T: int, H: int, W: int, Cin: int, Cout: int, ksize: int, stride=(1, 1, 1), up=(False, False), *,
+                      w_row_stride: int | None = None, out_align: int = 16, res_align: int = 0, gn_groups: int = 0,
+                      gn_in: bool = False):
+    """Host only: the kernel osk_causal_conv3d*_ndhwc_bf16 launch for this call, from the selection code the launch itself switches
+    on -> (name in CONV_KERNEL_CLASSES, fused statistics on), or the negative status the entry point would return (nothing
+    launched).  out_align / res_align: byte alignment of out / res (res_align 0 = no residual); gn_groups > 0 = gn_sums given."""
+    To, Ho, Wo = conv_out_dims(T, H, W, stride, up)
+    if w_row_stride is None:
+        w_row_stride = (ksize ** 3 * Cin + 63) // 64 * 64
+    rc = lib.osk_causal_conv3d_kernel_class(B, T, H, W, Cin, w_row_stride, Cout, ksize, stride[0], stride[1], stride[2], int(up[0]),
+                                            int(up[1]), To, Ho, Wo, out_align, res_align, gn_groups, int(gn_in))
+    return rc if rc < 0 else (CONV_KERNEL_CLASSES[rc & 0xFF], bool(rc & 0x100))
 
 
 def causal_conv3d_gn_in(x: torch.Tensor, table: torch.Tensor, w: torch.Tensor, bias, out: torch.Tensor, ksize: int,

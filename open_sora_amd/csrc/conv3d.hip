@@ -187,24 +187,20 @@ __global__ void __launch_bounds__(256, 2) conv_fewout_kernel(const ConvParams p)
   }
 }
 
-bool fewout_supported(const ConvParams& p) {
-  return p.ks == 3 && p.st == 1 && p.sh == 1 && p.sw == 1 && !p.up_t && !p.up_hw && p.Cin == 128 && p.Cout <= 4 && (p.Wo & 63) == 0 &&
-         !p.gn_sums;
-}
-
 }  // namespace
 
-static int conv_entry(const void* x, int B, int T, int H, int W, int Cin, const void* w, int64_t w_row_stride,
-                      const float* bias, int Cout, int ksize, int stride_t, int stride_h, int stride_w, int up_t, int up_hw,
-                      const void* res, void* out, int To, int Ho, int Wo, double* gn_sums, int gn_groups, void* stream,
-                      const float* gn_in = nullptr) {
+// argument checks + geometry of a call + the kernel that serves it (osk_conv::conv_kernel_class): shared by the entry points, which
+// launch *choice, and by osk_causal_conv3d_kernel_class, which reports it.  Of the pointers only null-ness and alignment are used.
+static int conv_plan(ConvParams& p, osk_conv::ConvChoice* choice, const void* x, int B, int T, int H, int W, int Cin, const void* w,
+                     int64_t w_row_stride, const float* bias, int Cout, int ksize, int stride_t, int stride_h, int stride_w, int up_t,
+                     int up_hw, const void* res, void* out, int To, int Ho, int Wo, double* gn_sums, int gn_groups,
+                     const float* gn_in) {
   if (!x || !w || !out || B <= 0 || T <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return OSK_EINVAL;
   if (ksize != 1 && ksize != 3) return OSK_EUNSUPPORTED;
   if (stride_t < 1 || stride_h < 1 || stride_w < 1 || stride_t > 2 || stride_h > 2 || stride_w > 2) return OSK_EINVAL;
   if ((Cin & 7) || (Cin & (Cin - 1))) return OSK_EUNSUPPORTED;  // Cin = 8 * 2^j (pad 3 -> 8 at the boundary)
   if (((uintptr_t)x & 15) || ((uintptr_t)w & 15) || ((uintptr_t)bias & 15) || ((uintptr_t)out & 7) || ((uintptr_t)res & 7))
     return OSK_EINVAL;
-  ConvParams p;
   p.x = (const unsigned short*)x; p.w = (const unsigned short*)w; p.bias = bias;
   p.res = (const unsigned short*)res; p.out = (unsigned short*)out;
   p.B = B; p.T = T; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
@@ -223,36 +219,44 @@ static int conv_entry(const void* x, int B, int T, int H, int W, int Cin, const 
   p.ntaps = ksize * ksize * ksize;
   if (conv_k_layout(Cin, p.ntaps, w_row_stride, &p.lg_cpt, &p.nk) != OSK_OK) return OSK_EINVAL;
   p.wrs = w_row_stride;
+  if (gn_sums) {
+    p.gn_sums = gn_sums;
+    p.gn_G = gn_groups;
+  }
+  p.gn_in = gn_in;
+  return osk_conv::conv_kernel_class(p, choice);
+}
+
+static int conv_entry(const void* x, int B, int T, int H, int W, int Cin, const void* w, int64_t w_row_stride,
+                      const float* bias, int Cout, int ksize, int stride_t, int stride_h, int stride_w, int up_t, int up_hw,
+                      const void* res, void* out, int To, int Ho, int Wo, double* gn_sums, int gn_groups, void* stream,
+                      const float* gn_in = nullptr) {
+  ConvParams p;
+  osk_conv::ConvChoice choice;
+  const int rc = conv_plan(p, &choice, x, B, T, H, W, Cin, w, w_row_stride, bias, Cout, ksize, stride_t, stride_h, stride_w, up_t,
+                           up_hw, res, out, To, Ho, Wo, gn_sums, gn_groups, gn_in);
+  if (rc != OSK_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
-  {
-    // large-tile kernels with the hand-scheduled K loop (conv3d_256.hip) wherever the shape qualifies
-    const int64_t x_bytes = (int64_t)B * T * H * W * Cin * 2;
-    const bool big = osk_conv::conv256_supported(p, x_bytes, (int64_t)Cout * w_row_stride * 2);
-    if (gn_sums) {   // fused statistics live in the large-tile kernels' epilogue only; nothing is launched otherwise
-      p.gn_sums = gn_sums;
-      p.gn_G = gn_groups;
-      // (the statistics ride in the 16-byte-store path of the epilogue: the output must be 16-byte aligned)
-      if (!big || !osk_conv::conv256_gn_supported(p) || ((uintptr_t)out & 15)) return OSK_EUNSUPPORTED;
+  switch (choice.cls) {
+    case osk_conv::CONV_FEWOUT: {
+      const dim3 g((unsigned)(B * To * ((Ho + 3) / 4) * (Wo >> 6))), blk(256);
+      if (Cout == 1) hipLaunchKernelGGL((conv_fewout_kernel<1>), g, blk, 0, s, p);
+      else if (Cout == 2) hipLaunchKernelGGL((conv_fewout_kernel<2>), g, blk, 0, s, p);
+      else if (Cout == 3) hipLaunchKernelGGL((conv_fewout_kernel<3>), g, blk, 0, s, p);
+      else hipLaunchKernelGGL((conv_fewout_kernel<4>), g, blk, 0, s, p);
+      return (int)hipGetLastError();
     }
-    if (gn_in) {     // input GroupNorm + SiLU folded into the halo refill: sliding-window kernels only; nothing is launched otherwise
-      p.gn_in = gn_in;
-      if (!big || !osk_conv::conv256_gn_in_supported(p)) return OSK_EUNSUPPORTED;
+    case osk_conv::CONV_TILE128:
+    case osk_conv::CONV_TILE128_BIGC: {
+      const int nblk = ((p.M + BM - 1) / BM) * ((Cout + BN - 1) / BN);
+      dim3 grid(nblk), block(256);
+      if (choice.cls == osk_conv::CONV_TILE128_BIGC) hipLaunchKernelGGL((conv3d_kernel<true>), grid, block, SMEM_BYTES, s, p);
+      else hipLaunchKernelGGL((conv3d_kernel<false>), grid, block, SMEM_BYTES, s, p);
+      return (int)hipGetLastError();
     }
-    if (big) return osk_conv::launch_conv256(p, s);
+    default:   // the large-tile kernels with the hand-scheduled K loop (conv3d_256.hip)
+      return osk_conv::launch_conv256(p, choice.cls, s);
   }
-  if (fewout_supported(p)) {
-    const dim3 g((unsigned)(B * To * ((Ho + 3) / 4) * (Wo >> 6))), blk(256);
-    if (Cout == 1) hipLaunchKernelGGL((conv_fewout_kernel<1>), g, blk, 0, s, p);
-    else if (Cout == 2) hipLaunchKernelGGL((conv_fewout_kernel<2>), g, blk, 0, s, p);
-    else if (Cout == 3) hipLaunchKernelGGL((conv_fewout_kernel<3>), g, blk, 0, s, p);
-    else hipLaunchKernelGGL((conv_fewout_kernel<4>), g, blk, 0, s, p);
-    return (int)hipGetLastError();
-  }
-  const int nblk = ((p.M + BM - 1) / BM) * ((Cout + BN - 1) / BN);
-  dim3 grid(nblk), block(256);
-  if (Cin % 64 == 0) hipLaunchKernelGGL((conv3d_kernel<true>), grid, block, SMEM_BYTES, s, p);
-  else hipLaunchKernelGGL((conv3d_kernel<false>), grid, block, SMEM_BYTES, s, p);
-  return (int)hipGetLastError();
 }
 
 extern "C" int osk_causal_conv3d_ndhwc_bf16(const void* x, int B, int T, int H, int W, int Cin, const void* w,
@@ -281,4 +285,21 @@ extern "C" int osk_causal_conv3d_gnin_ndhwc_bf16(const void* x, const float* gn_
   if (gn_sums && (gn_groups <= 0 || ((uintptr_t)gn_sums & 7))) return OSK_EINVAL;
   return conv_entry(x, B, T, H, W, Cin, w, w_row_stride, bias, Cout, ksize, stride_t, stride_h, stride_w, 0, 0, res, out, To, Ho, Wo,
                     gn_sums, gn_sums ? gn_groups : 0, stream, gn_in_table);
+}
+
+extern "C" int osk_causal_conv3d_kernel_class(int B, int T, int H, int W, int Cin, int64_t w_row_stride, int Cout, int ksize,
+                                              int stride_t, int stride_h, int stride_w, int up_t, int up_hw, int To, int Ho, int Wo,
+                                              int out_align, int res_align, int gn_groups, int gn_in) {
+  if (out_align <= 0 || (out_align & (out_align - 1)) || res_align < 0 || (res_align & (res_align - 1)) || gn_groups < 0) return OSK_EINVAL;
+  // stand-in addresses: 2^20 + the stated alignment, so the low bits are those of a pointer aligned to exactly that (for alignments
+  // below 2^20); conv_plan and the selection look at null-ness and the low 4 bits only
+  const uintptr_t al = (uintptr_t)1 << 20;
+  ConvParams p;
+  osk_conv::ConvChoice choice;
+  const int rc = conv_plan(p, &choice, (const void*)al, B, T, H, W, Cin, (const void*)al, w_row_stride, (const float*)al, Cout, ksize,
+                           stride_t, stride_h, stride_w, up_t, up_hw, res_align ? (const void*)(al + (uintptr_t)res_align) : nullptr,
+                           (void*)(al + (uintptr_t)out_align), To, Ho, Wo, gn_groups ? (double*)al : nullptr, gn_groups,
+                           gn_in ? (const float*)al : nullptr);
+  if (rc != OSK_OK) return rc;
+  return (int)choice.cls | (choice.stats ? OSK_CONV_FUSED_STATS : 0);
 }

@@ -631,7 +631,8 @@ int launch_sw2(const ConvParams& p0, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
-// sliding-window form: 3 x 3 x 3, stride 1, whole 16 x 16 output bricks, whole pairs of 32-channel blocks; the tensor as stored or
+// sliding-window form: 3 x 3 x 3, stride 1, whole 16 x 16 output bricks, any Cout >= 128 (a ragged last channel tile clamps its weight
+// rows and masks its stores: Cout 136, 160 and 288 are audited in tests/test_gpu_vae_audit.py); the tensor as stored or
 // under the decoder's upsample (H and W together, T optionally); per-lane byte offsets inside one frame / the weight tensor
 // are 32-bit (conv256_supported)
 bool convsw_supported(const ConvParams& p) {
@@ -674,25 +675,61 @@ bool conv256_gn_supported(const ConvParams& p) {
   return p.B == 1 || per_b % 256 == 0;
 }
 
+// One selection for every conv call (conv_params.h).  The predicates of the sliding-window and fused forms live in this file; the
+// few-output reduction and the 128 x 128 tile of conv3d.hip are what is left when the large-tile family does not take the shape.
+int conv_kernel_class(const ConvParams& p, ConvChoice* c) {
+  const int64_t x_bytes = (int64_t)p.B * p.T * p.H * p.W * p.Cin * 2;
+  const bool big = conv256_supported(p, x_bytes, (int64_t)p.Cout * p.wrs * 2);
+  c->stats = false;
+  if (p.gn_sums) {   // fused statistics live in the large-tile kernels' epilogue only; nothing is launched otherwise
+    // (the statistics ride in the 16-byte path of the epilogue: the output AND the residual must be 16-byte aligned -- with a residual
+    // that is not, the epilogue takes its generic path, which accumulates nothing)
+    if (!big || !conv256_gn_supported(p) || ((uintptr_t)p.out & 15) || ((uintptr_t)p.res & 15)) return OSK_EUNSUPPORTED;
+    c->stats = true;
+  }
+  if (p.gn_in) {     // input GroupNorm + SiLU folded into the halo refill: sliding-window kernels only; nothing is launched otherwise
+    if (!big || !conv256_gn_in_supported(p)) return OSK_EUNSUPPORTED;
+    c->cls = p.Cout >= 256 ? CONV_SW8_GN : CONV_SW2_GN;
+    return OSK_OK;
+  }
+  if (big) {
+#ifndef OSK_CONV_NO_SW   // (A/B builds of tools/: -DOSK_CONV_NO_SW keeps every layer on the implicit-GEMM kernel)
+    if (convsw_supported(p)) {
+      if (p.up_hw) c->cls = p.Cout >= 256 ? CONV_SW8_UP : CONV_SW4_UP;
+#ifndef OSK_CONV_NO_SW2
+      else if (p.Cout == 128 && p.To >= 2) c->cls = CONV_SW2;
+#endif
+      else c->cls = p.Cout >= 256 ? CONV_SW8 : CONV_SW4;
+      return OSK_OK;
+    }
+#endif
+    c->cls = p.Cout >= 256 ? CONV_X8 : CONV_X4;
+    return OSK_OK;
+  }
+  // Cout <= 4 reduction (conv3d.hip): 3 x 3 x 3, stride 1, no upsample, Cin == 128, Wo % 64 == 0 (the row of a wave never wraps)
+  if (p.ks == 3 && p.st == 1 && p.sh == 1 && p.sw == 1 && !p.up_t && !p.up_hw && p.Cin == 128 && p.Cout <= 4 && (p.Wo & 63) == 0)
+    c->cls = CONV_FEWOUT;
+  else
+    c->cls = p.Cin % 64 == 0 ? CONV_TILE128_BIGC : CONV_TILE128;
+  return OSK_OK;
+}
+
 // linear 256-voxel tiles (the 16 x 16-brick tile order measured in round 2 -- same time, 12 % more fabric-side reads,
 // profiles/r02_pmc_gemm_conv.txt -- stays a ConvParams field the kernel honours, never set)
-int launch_conv256(const ConvParams& p0, hipStream_t st) {
-  ConvParams p = p0;
-#ifndef OSK_CONV_NO_SW   // (A/B builds of tools/: -DOSK_CONV_NO_SW keeps every layer on the implicit-GEMM kernel)
-  if (p.gn_in) {
-    if (!conv256_gn_in_supported(p)) return OSK_EUNSUPPORTED;
-    return p.Cout >= 256 ? launch_sw<8, false, true>(p, st) : launch_sw2<true>(p, st);
+// (brick stays 0 for the conv256x kernels; launch_sw / launch_sw2 set their own)
+int launch_conv256(const ConvParams& p, ConvKernelClass cls, hipStream_t st) {
+  switch (cls) {
+    case CONV_SW8_GN: return launch_sw<8, false, true>(p, st);
+    case CONV_SW2_GN: return launch_sw2<true>(p, st);
+    case CONV_SW8_UP: return launch_sw<8, true>(p, st);
+    case CONV_SW4_UP: return launch_sw<4, true>(p, st);
+    case CONV_SW2: return launch_sw2<false>(p, st);
+    case CONV_SW8: return launch_sw<8, false>(p, st);
+    case CONV_SW4: return launch_sw<4, false>(p, st);
+    case CONV_X8: return launch_x<8>(p, st);
+    case CONV_X4: return launch_x<4>(p, st);
+    default: return OSK_EINVAL;
   }
-  if (convsw_supported(p)) {
-    if (p.up_hw) return p.Cout >= 256 ? launch_sw<8, true>(p, st) : launch_sw<4, true>(p, st);
-#ifndef OSK_CONV_NO_SW2
-    if (p.Cout == 128 && p.To >= 2) return launch_sw2<false>(p, st);
-#endif
-    return p.Cout >= 256 ? launch_sw<8, false>(p, st) : launch_sw<4, false>(p, st);
-  }
-#endif
-  p.brick = 0;
-  return p.Cout >= 256 ? launch_x<8>(p, st) : launch_x<4>(p, st);
 }
 
 }  // namespace osk_conv
